@@ -9,6 +9,12 @@ GPU; rounds 1-3: 116^3 cells -- 120 layers split into 2, 4 and 8 z-slabs of EQUA
 against a mean of 14.5; `--cells 116 116 116` is the old mesh, same DoF/s at N = 1: profiles/r4).  W warm-up iterations, then a solve of exactly K iterations is timed between barrier + synchronize pairs,
 max over ranks (the reference times the whole cg.solve too: bp5/step-64.cu:442-463).  Prints ONE JSON line on rank 0.
 
+A plain run does only that: set-up, warm-up, the K timed iterations, the line (`ms_per_step` = milliseconds of one timed iteration).
+`--full` adds the reporting legs after the timed region: sustained solves (the reference's protocol), the unfused operator kernel,
+the N > 1 exchange A/B, the 116^3 mesh of rounds 1-3, the copy stream, the config-4 degree sweep, the rocprofv3 traffic passes and the
+CPU baseline.  `--dump-outputs DIR` writes what the timed solve computed (solution at a fixed, seeded sample of the DoFs, residual norms)
+as .npy files: the inputs are the same from run to run, so two builds can be compared output for output.
+
 N > 1: one rank per GPU, RCCL over xGMI.  Either the caller starts the ranks (torch.distributed.run sets
 RANK/WORLD_SIZE), or this script starts them itself -- as a CHILD process, before anything here touches a GPU.
 Default = STRONG scaling: the SAME 116x116x120 problem split into N z-slabs (the reference reports the throughput of one
@@ -27,6 +33,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HEADLINE_CELLS = (116, 116, 120)  # BASELINE config 3 ("p = 4, ~1e8 DoFs"): 465 x 465 x 481 = 104 004 225 DoFs; 120 cell layers = 2 x 60 = 4 x 30 = 8 x 15
+DUMP_SAMPLE, DUMP_SEED = 1 << 21, 64   # --dump-outputs: the solution at up to 2^21 global DoFs (seeded sample; all DoFs of smaller problems): 2 x 16 MiB
 
 
 def algorithmic_bytes_per_dof(p, n_cells, n_dofs, G=6, I=1, operator_only=False):
@@ -69,7 +76,7 @@ def live_traffic(kernel, workload_args, timeout_s=90):
         try:
             # the program after `--` is the running interpreter itself (a real ELF binary: no shim that would exec under the profiler's preload)
             cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "-d", d, "-o", "p", "--output-format", "csv", "--", os.path.realpath(sys.executable),
-                   os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-mesh-116", "--sustained-iters", "0",
+                   os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-mesh-116", "--sustained-iters", "0",
                    "--no-traffic-pass"] + workload_args
             child = subprocess.Popen(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                      start_new_session=True)
@@ -186,9 +193,15 @@ def main():
                          "0 0 0 = lexicographic cell order -> pencil kernel with atomics)")
     ap.add_argument("--numbering", type=int, choices=[0, 1, 2], default=None,
                     help="bp5_mesh_desc.dof_numbering: 0 lexicographic, 1 block-major (needs cell bricks), 2 cell interiors first; default: 1 with bricks, 2 at p = 8")
-    ap.add_argument("--sustained-iters", type=int, default=200, help="reference protocol: iterations per repetition (bp5/step-64.cu:729); 0 = skip")
-    ap.add_argument("--sustained-reps", type=int, default=3, help="reference protocol: repetitions, best one reported (bp5/step-64.cu:457-463)")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU work for the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run the reporting legs too (sustained solves, unfused operator kernel, N > 1 exchange A/B, 116^3 mesh, "
+                         "copy stream, config-4 sweep, rocprofv3 traffic passes, CPU baseline); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed solve computed as DIR/<name>.npy (float64): solution.npy = x at the global DoFs of solution_dofs.npy "
+                         f"(lexicographic numbering; a fixed, seeded sample of {DUMP_SAMPLE} on larger problems), residual_norms.npy = initial, final")
+    ap.add_argument("--sustained-iters", type=int, default=200, help="--full, reference protocol: iterations per repetition (bp5/step-64.cu:729); 0 = skip")
+    ap.add_argument("--sustained-reps", type=int, default=3, help="--full, reference protocol: repetitions, best one reported (bp5/step-64.cu:457-463)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="--full: seconds of CPU work for the cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep-other-quadrature", action="store_true", help="--config 4: only the quadrature of --quadrature per degree (default: both, the other one under its name)")
     ap.add_argument("--no-mesh-116", action="store_true", help="N = 1, default mesh: skip the extra solve on the 116^3 mesh of rounds 1-3 (reported as mesh_116_cubed)")
@@ -369,6 +382,31 @@ def main():
     n_global = int(mesh.n_global_dofs)
     value = n_global * iters / dt
 
+    if args.dump_outputs:
+        # what the timed solve hands its caller (x0 = 0, exactly `steps` iterations; nothing after this point may touch x first): the solution,
+        # written in the lexicographic global numbering (mesh.global_ids) so that builds numbering the DoFs differently compare entry for entry
+        try:
+            import numpy as np
+            ids = (np.arange(n_global, dtype=np.int64) if n_global <= DUMP_SAMPLE else
+                   np.sort(np.random.default_rng(DUMP_SEED).choice(n_global, DUMP_SAMPLE, replace=False)).astype(np.int64))
+            dev = f"cuda:{local_rank}"
+            lex = torch.zeros(n_global, dtype=torch.float64, device=dev)
+            lex[torch.from_numpy(mesh.global_ids[:mesh.n_owned].astype(np.int64)).to(dev)] = x[:mesh.n_owned]
+            sample = lex[torch.from_numpy(ids).to(dev)]
+            del lex
+            if world > 1:
+                import torch.distributed as dist
+                sample = sample.cpu() if control_on_cpu else sample
+                dist.all_reduce(sample)   # every DoF is owned by exactly one rank, the others add an exact zero
+            if rank == 0:
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                np.save(os.path.join(args.dump_outputs, "solution.npy"), sample.cpu().numpy())
+                np.save(os.path.join(args.dump_outputs, "solution_dofs.npy"), ids.astype(np.float64))
+                np.save(os.path.join(args.dump_outputs, "residual_norms.npy"), np.array([ctl.initial_value(), ctl.last_value()], dtype=np.float64))
+            del sample
+        except Exception as e:   # noqa: BLE001
+            die(f"--dump-outputs {args.dump_outputs}", e)
+
     # Everything below is reporting around the measurement above.  The legs fill `extras`; compose() (defined further down) builds the line
     # from whatever is there.  A watchdog prints the line and ends the process (every rank, exit code 4: the measurement is on stdout, the
     # overrun -- possibly a hung GPU leg -- shows in the run record) if the legs take longer than --post-budget: a diagnostic leg that hangs
@@ -520,7 +558,7 @@ def main():
     # the reference's own protocol (bp5/step-64.cu:443-463,724-730): solves of 200 iterations, wall clock + device sync
     # around each, the BEST repetition is reported.  Minutes-long runs clock ~5 % below short bursts (profiles/r1 j_*).
     sustained = None
-    if args.sustained_iters > 0 and args.sustained_reps > 0:
+    if args.full and args.sustained_iters > 0 and args.sustained_reps > 0:
         best = 0.0
         for _ in range(args.sustained_reps):
             sctl, sdt = timed_solve(args.sustained_iters, profile=False)
@@ -539,7 +577,7 @@ def main():
     # the bare operator kernel in the same run (when the timed solve fused the dot products into it): a short solve with the
     # separate dot-product kernel, so that the operator-only roofline figure of SURVEY 8(d) can be read off the same box
     unfused_ms = None
-    if fused_all:
+    if args.full and fused_all:
         op.mf_data.set_cg_fusion(False)
         uctl, _ = timed_solve(10)
         unfused_ms = uctl.apply_ms_avg
@@ -550,7 +588,7 @@ def main():
     # the phase boundaries of every iteration on the solver's stream; the stamps cost a few us each, so the stamped run is not the timed
     # one).  One driver run then tells how much of an iteration is kernels, exposed exchange, and all-reduce -- per rank extremes.
     exchange_ab = None
-    if world > 1 and not args.no_exchange_ab and args.variant == "merged":
+    if args.full and world > 1 and not args.no_exchange_ab and args.variant == "merged":
         exchange_ab = {}
         k_ab = max(10, min(args.steps, 40))
         extras["exchange_ab"] = {}            # (published leg by leg: the watchdog reports the legs that finished)
@@ -589,7 +627,7 @@ def main():
 
     # BASELINE.md's restatement of config 3 names the 116^3 mesh (100 544 625 DoFs; the headline of rounds 1-3).  The default became 116x116x120 so that eight
     # z-slabs are equally high; the same solve on the 116^3 mesh is reported beside it (N = 1, default mesh only), so that rounds stay comparable
-    if world == 1 and base == HEADLINE_CELLS and not args.cells and p == 4 and args.config in (None, 3) and not args.no_mesh_116:
+    if args.full and world == 1 and base == HEADLINE_CELLS and not args.cells and p == 4 and args.config in (None, 3) and not args.no_mesh_116:
         extras["stage"] = "the same solve on the 116^3 mesh of rounds 1-3"
         m3, _, _ = build(p, (116, 116, 116))
         o3 = pkg.HelmholtzOperator(m3, quad, km, device=local_rank) if args.operator == "helmholtz" else \
@@ -608,30 +646,31 @@ def main():
         torch.cuda.empty_cache()
 
     # achievable-stream figure: device copy y = 1.0 * x over the solver's vectors, read 8 + write 8 B per entry
-    extras["stage"] = "copy-stream measurement"
-    import ctypes as C
-    ya, xa = op.initialize_dof_vector(), op.initialize_dof_vector()
-    L, hnd = pkg.lib(), op.mf_data.handle
-    pv = lambda t: C.c_void_p(t.data_ptr())
-    for _ in range(3):
-        L.bp5_vec_equ(hnd, pv(ya), 1.0, pv(xa), mesh.n_owned)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        L.bp5_vec_equ(hnd, pv(ya), 1.0, pv(xa), mesh.n_owned)
-    e1.record()
-    torch.cuda.synchronize()
-    stream_copy_gbs = 16.0 * mesh.n_owned * 20 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del ya, xa
-    extras["stream_copy_gbs"] = stream_copy_gbs
+    if args.full:
+        extras["stage"] = "copy-stream measurement"
+        import ctypes as C
+        ya, xa = op.initialize_dof_vector(), op.initialize_dof_vector()
+        L, hnd = pkg.lib(), op.mf_data.handle
+        pv = lambda t: C.c_void_p(t.data_ptr())
+        for _ in range(3):
+            L.bp5_vec_equ(hnd, pv(ya), 1.0, pv(xa), mesh.n_owned)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            L.bp5_vec_equ(hnd, pv(ya), 1.0, pv(xa), mesh.n_owned)
+        e1.record()
+        torch.cuda.synchronize()
+        stream_copy_gbs = 16.0 * mesh.n_owned * 20 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        del ya, xa
+        extras["stream_copy_gbs"] = stream_copy_gbs
 
     # BASELINE config 4 as one line: the other degrees at their ~5e7-DoF sizes, one short solve each (N = 1)
     # Both quadratures per degree (the reference's COLLOCATION switch, bp5/step-64.cu:48,243-247): Gauss(p+1) is the
     # reference default and the line's `value`; GLL(p+1) -- true BP5: collocated, one third of the contractions on the same bytes -- is
     # reported beside it per degree ("gll").
     sweep = None
-    if args.config == 4 and world == 1:
+    if args.full and args.config == 4 and world == 1:
         sweep = []
         extras["stage"] = "config-4 degree sweep"
         other_quad = pkg.QUAD_GLL if quad == pkg.QUAD_GAUSS else pkg.QUAD_GAUSS
@@ -678,7 +717,7 @@ def main():
         key = f"p{p}_{args.quadrature}_{base[0]}x{base[1]}x{base[2]}_{args.geometry}_v{ev}" + ("_helmholtz" if args.operator == "helmholtz" else "")
         kname = ctl.apply_kernel or f"apply variant {ev}"
         tr = None
-        if world == 1 and not args.no_traffic_pass and not args.rehearsal:
+        if args.full and world == 1 and not args.no_traffic_pass and not args.rehearsal:
             wl = ["--operator", args.operator, "--degree", str(p), "--quadrature", args.quadrature, "--coefficient", args.coefficient, "--deform", str(args.deform),
                   "--variant", args.variant, "--geometry", args.geometry, "--apply-variant", str(args.apply_variant),
                   "--cells", str(cells[0]), str(cells[1]), str(cells[2]), "--cell-block", str(block[0]), str(block[1]), str(block[2])]
@@ -688,7 +727,7 @@ def main():
             if tr:
                 tr["source"] += ": rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed (not measured in this run)"
         extras["traffic"] = tr
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
             extras["stage"] = "CPU baseline"
             extras["cpu_baseline"] = cpu_baseline(mesh, p, quad, km, args.cpu_budget, max(args.steps, 2))
     watchdog.cancel()

@@ -43,7 +43,7 @@ def _check(line, steps, warmup):
 
 
 def test_bench_json_line_small_workload():
-    r = subprocess.run([sys.executable, BENCH, "--cells", "12", "12", "12", "--steps", "7", "--warmup", "2", "--sustained-iters", "20", "--sustained-reps", "2",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--cells", "12", "12", "12", "--steps", "7", "--warmup", "2", "--sustained-iters", "20", "--sustained-reps", "2",
                         "--cpu-budget", "2"], capture_output=True, text=True,
                        timeout=900, cwd=bp5_pkg.ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -62,7 +62,7 @@ def test_bench_json_line_small_workload():
 
 
 def test_bench_quotes_the_committed_pmc_passes_when_the_live_ones_are_switched_off():
-    r = subprocess.run([sys.executable, BENCH, "--cells", "12", "12", "12", "--steps", "3", "--warmup", "1", "--sustained-iters", "0", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--cells", "12", "12", "12", "--steps", "3", "--warmup", "1", "--sustained-iters", "0", "--no-cpu-baseline",
                         "--no-traffic-pass"], capture_output=True, text=True, timeout=900, cwd=bp5_pkg.ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -100,7 +100,7 @@ def test_bench_watchdog_prints_the_line_when_the_reporting_legs_overrun():
     """the legs behind the timed region (sustained solves, exchange A/B, copy stream, traffic passes, CPU baseline) run under a watchdog: when they take longer than
     --post-budget the line is printed with what is there and the process exits with code 4 -- a hang in a diagnostic leg must not cost a run its measurement, and
     must not pass for a clean run either"""
-    r = subprocess.run([sys.executable, BENCH, "--cells", "24", "24", "24", "--steps", "5", "--warmup", "1", "--sustained-iters", "20000", "--sustained-reps", "100",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--cells", "24", "24", "24", "--steps", "5", "--warmup", "1", "--sustained-iters", "20000", "--sustained-reps", "100",
                         "--post-budget", "2"], capture_output=True, text=True, timeout=900, cwd=bp5_pkg.ROOT)
     assert r.returncode == 4, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -110,3 +110,51 @@ def test_bench_watchdog_prints_the_line_when_the_reporting_legs_overrun():
     assert d["post_processing"]["completed"] is False and d["post_processing"]["stage_reached"] == "sustained solves"
     assert "cpu_baseline" not in d and "sustained" not in d and d["roofline_cg"]["stream_copy_GBs"] is None
     assert "post-processing exceeded" in r.stderr
+
+
+def _run_dump(out_dir, cells, steps, *extra):
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--cells", *[str(c) for c in cells], "--steps", str(steps), "--warmup", "2",
+                        "--dump-outputs", str(out_dir), *extra], capture_output=True, text=True, timeout=600, cwd=bp5_pkg.ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    import numpy as np
+    assert sorted(os.listdir(out_dir)) == ["residual_norms.npy", "solution.npy", "solution_dofs.npy"]
+    arrs = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+    assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    return json.loads(lines[0]), arrs
+
+
+def _same_up_to_rounding(a, b):
+    import numpy as np
+    assert np.array_equal(a["solution_dofs"], b["solution_dofs"])
+    for k in ("solution", "residual_norms"):
+        assert np.linalg.norm(a[k] - b[k]) <= 1e-12 * np.linalg.norm(a[k]), k
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_solve_computed(tmp_path):
+    """A plain run (no --full) times the steps and prints the line, no reporting leg after the timed region; --dump-outputs writes the
+    solution of the timed solve (x0 = 0, exactly --steps iterations) in the lexicographic DoF numbering: the same DoFs and the same values up to
+    rounding from run to run (the solver's reductions are not bitwise reproducible), the oracle's merged CG on the same mesh, and a fixed, seeded
+    sample of the DoFs once the problem is larger than that sample."""
+    import numpy as np
+    import bp5_oracle as O
+    runs = [_run_dump(tmp_path / f"run{k}", (8, 8, 8), 6) for k in range(2)]
+    d, a = runs[0]
+    assert d["steps"] == 6 and d["ms_per_step"] > 0 and d["post_processing"]["completed"] is True
+    assert not {"cpu_baseline", "sustained", "mesh_116_cubed", "exchange_ab", "sweep"} & set(d)
+    assert d["roofline_cg"]["stream_copy_GBs"] is None and d["roofline"]["operator_kernel_unfused"] is None and d["roofline"]["traffic"] is None
+    _same_up_to_rounding(a, runs[1][1])
+    n = 33 ** 3
+    assert np.array_equal(a["solution_dofs"], np.arange(n, dtype=np.float64))
+    sc = d["solve_check"]
+    assert a["residual_norms"].tolist() == [sc["initial_residual"], sc["residual_after_timed_solve"]]
+    pr = O.Problem(4, (8, 8, 8), O.QUAD_GAUSS, h=1.0 / 8, kappa=O.kappa_step64)
+    xr, k, _ = O.cg_merged(pr.vmult, pr.rhs(), 6)
+    assert k == 6 and np.linalg.norm(a["solution"] - xr) / np.linalg.norm(xr) < 1e-11
+    # larger than the sample (137^3 DoFs): the same seeded sample every run, sorted, unique, inside the problem
+    big = [_run_dump(tmp_path / f"big{k}", (34, 34, 34), 3)[1] for k in range(2)]
+    ids = big[0]["solution_dofs"]
+    assert len(ids) == 2 ** 21 and np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < 137 ** 3
+    _same_up_to_rounding(*big)
+    assert np.all(np.isfinite(big[0]["solution"]))

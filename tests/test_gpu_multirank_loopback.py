@@ -179,7 +179,7 @@ def test_bench_with_two_ranks_as_the_driver_launches_it():
     env = dict(os.environ, BP5_LIB=LOOPBACK_LIB, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--cells", "16", "16", "16", "--sustained-iters", "0", "--apply-variant", "56", "--rehearsal"]
+           "--cells", "16", "16", "16", "--sustained-iters", "0", "--apply-variant", "56", "--rehearsal", "--full"]
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]

@@ -6,4 +6,4 @@ set -e
 N=${1:-2}; shift || true
 export BP5_LIB=$PWD/deal-and-ceed-on-gpu_amd/libbp5_loopback.so
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $N \
-  --steps 10 --warmup 3 --sustained-iters 0 --rehearsal "$@"
+  --steps 10 --warmup 3 --sustained-iters 0 --rehearsal --full "$@"
