@@ -6,12 +6,12 @@ All compute goes through the C ABI of include/bp5.h (libbp5.so, hand-written HIP
 There is NO CPU fallback: importing works anywhere, compute calls fail loudly without the
 library or without a GPU."""
 from ._lib import (BP5Error, QUAD_GAUSS, QUAD_GLL, COEF_ONE, COEF_STEP64, CG_PLAIN, CG_MERGED, GEOM_MERGED6, GEOM_AFFINE, OP_POISSON, OP_HELMHOLTZ, build, lib,
-                   lib_path, shape_tables, HEADER_SYMBOLS)
+                   lib_path, shape_tables, tridiagonal_eigenvalues, HEADER_SYMBOLS)
 from .mesh import BrickMesh
 from .matrix_free import (MatrixFree, PoissonOperator, HelmholtzOperator, DiagonalMatrix, IterationNumberControl, SolverControl,
-                          SolverCG, SolverCGFullMerge, Communicator, Vector)
+                          SolverCG, SolverCGFullMerge, Communicator, Vector, PreconditionChebyshev)
 
 __all__ = ["BP5Error", "QUAD_GAUSS", "QUAD_GLL", "COEF_ONE", "COEF_STEP64", "CG_PLAIN", "CG_MERGED", "GEOM_MERGED6", "GEOM_AFFINE", "OP_POISSON", "OP_HELMHOLTZ", "build", "lib",
            "lib_path", "shape_tables", "HEADER_SYMBOLS", "BrickMesh", "MatrixFree", "PoissonOperator", "HelmholtzOperator",
            "DiagonalMatrix", "IterationNumberControl", "SolverControl", "SolverCG", "SolverCGFullMerge",
-           "Communicator", "Vector"]
+           "Communicator", "Vector", "PreconditionChebyshev", "tridiagonal_eigenvalues"]

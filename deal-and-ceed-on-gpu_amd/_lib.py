@@ -90,6 +90,11 @@ class CGResult(C.Structure):
 VMULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)   # bp5_vmult_fn(ctx, dst, src)
 
 
+class ChebyshevParams(C.Structure):
+    _fields_ = [("degree", C.c_int), ("smoothing_range", C.c_double), ("eig_cg_n_iterations", C.c_int), ("max_eigenvalue", C.c_double),
+                ("min_eigenvalue", C.c_double), ("start_ids_host", C.c_void_p)]
+
+
 def lib():
     """Load libbp5.so; fails loudly if it has not been built (no fallback of any kind)."""
     global _LIB
@@ -167,6 +172,13 @@ def lib():
         "bp5_apply_distributed": (i32, [vp, vp, vp, vp, i32]),
         "bp5_cg_solve": (i32, [vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_operator": (i32, [vp, VMULT_FN, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_cg_solve_preconditioned": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_chebyshev_create": (i32, [vp, vp, vp, vp, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),
+        "bp5_chebyshev_eigenvalues": (i32, [vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(i32)]),
+        "bp5_chebyshev_vmult": (i32, [vp, vp, vp]),
+        "bp5_chebyshev_step": (i32, [vp, vp, vp]),
+        "bp5_chebyshev_destroy": (i32, [vp]),
+        "bp5_tridiagonal_eigenvalues": (i32, [i32, vp, vp, vp]),
         "bp5_event_create": (i32, [C.POINTER(vp)]),
         "bp5_event_record": (i32, [vp, vp]),
         "bp5_event_elapsed_ms": (i32, [vp, vp, C.POINTER(f64)]),
@@ -186,6 +198,18 @@ def check(status):
     if status != 0:
         L = lib()
         raise BP5Error(status, f"{L.bp5_strerror(status).decode()}: {L.bp5_last_error().decode()}")
+
+
+def tridiagonal_eigenvalues(diag, offdiag):
+    """All eigenvalues (ascending) of the symmetric tridiagonal matrix -- host-only (Sturm bisection), works without a GPU."""
+    d = np.ascontiguousarray(diag, dtype=np.float64)
+    e = np.ascontiguousarray(offdiag, dtype=np.float64)
+    if e.size != max(d.size - 1, 0):
+        raise BP5Error(1, "offdiag must have len(diag) - 1 entries")
+    e = e if e.size else np.zeros(1)
+    out = np.zeros(d.size)
+    check(lib().bp5_tridiagonal_eigenvalues(int(d.size), d.ctypes.data, e.ctypes.data, out.ctypes.data))
+    return out
 
 
 def shape_tables(degree, quadrature):

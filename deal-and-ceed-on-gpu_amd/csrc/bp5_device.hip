@@ -184,7 +184,7 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   hipStreamSynchronize(mf->stream);
   void *ptrs[] = {mf->d_constrained_bits, mf->d_l2g, mf->d_constrained, mf->d_send_idx, mf->d_coords, mf->d_tab, mf->d_tab_gauss, mf->d_l2g_padded,
                   mf->d_constraint_mask, mf->d_inv_jac, mf->d_JxW, mf->d_qpoints, mf->d_sendbuf, mf->d_recvbuf, mf->d_partials,
-                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal};
+                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z};
   for (void *p : ptrs) if (p) hipFree(p);
   if (mf->h_sc) hipHostFree(mf->h_sc);
   if (mf->h_st) hipHostFree(mf->h_st);
@@ -192,6 +192,8 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   for (hipEvent_t e : mf->phase.ev) hipEventDestroy(e);
   for (hipEvent_t e : mf->ev_solve) if (e) hipEventDestroy(e);
   for (hipEvent_t e : mf->ev_halo) if (e) hipEventDestroy(e);
+  for (hipEvent_t e : mf->ev_done) if (e) hipEventDestroy(e);
+  if (mf->h_done) hipHostFree(mf->h_done);
   if (mf->comm_stream) { hipStreamSynchronize(mf->comm_stream); hipStreamDestroy(mf->comm_stream); }
   for (auto &kv : mf->march_plans) { hipFree(kv.second.team_off); hipFree(kv.second.entries); }
   for (auto &kv : mf->plans) {
@@ -2063,6 +2065,7 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
       KERNEL_CHECK();
       BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
       hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+      if (mf->cg_history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, mf->cg_history, mf->cg_history_cap);
       hipLaunchKernelGGL(cg_direction_kernel, dim3(stream_grid_flat(mf, n, 2)), dim3(VB), 0, s, d, g, diag, n, mf->d_sc, mf->d_st);
       KERNEL_CHECK();
       if (check > 0 && it % check == 0 && it < prm->max_iter) {
@@ -2227,4 +2230,299 @@ extern "C" int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, 
 {
   if (!vmult) return fail(BP5_ERR_INVALID, "null vmult callback");
   return cg_solve_impl(mf, nullptr, vmult, ctx, diag, b, x, prm, res);
+}
+
+// ------------------------------------------------------------------------------------ CG with any preconditioner
+// cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of
+// D g.  Every kernel is gated on the device-side stop flag; the preconditioner itself is not (the host does not know the flag before it
+// looks), it writes only z and its own work vectors, and z is not read once the solve has stopped: the same bits for every check_every.
+extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, bp5_vmult_fn precond, void *precond_ctx,
+                                           const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  if (!mf || (!vmult && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !precond || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
+  if (prm->variant != BP5_CG_PLAIN) return fail(BP5_ERR_INVALID, "a general preconditioner needs BP5_CG_PLAIN (SolverCGFullMerge takes a diagonal only)");
+  if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
+  if (!aligned16(b) || !aligned16(x)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(mf->device));
+  BP5_TRY(ensure_ws(mf));
+  if (!mf->ws_z) {
+    HIP_TRY(hipMalloc((void **)&mf->ws_z, std::max<size_t>(mf->n_local(), 2) * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(mf->ws_z, 0, std::max<size_t>(mf->n_local(), 2) * sizeof(double), mf->stream));
+  }
+  const size_t n = mf->n_owned;
+  const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1), gridf = stream_grid_flat(mf, n, 2);
+  hipStream_t s = mf->stream;
+  double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h, *z = mf->ws_z;
+  ApplyProfile prof{mf, false};
+  auto apply_A = [&](double *src, double *dst) -> int {
+    if (!vmult) return solver_vmult(mf, coef, src, dst, true, prof);
+    const int st = vmult(ctx, dst, src);
+    return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
+  };
+  auto apply_P = [&](double *src, double *dst) -> int {
+    const int st = precond(precond_ctx, dst, src);
+    return st == BP5_OK ? BP5_OK : fail(st, "the preconditioner's vmult callback reported a failure");
+  };
+  mf->fuse = bp5_mf::Fuse{};
+  mf->h_sc[SC_TOL] = prm->abs_tol;
+  HIP_TRY(hipMemcpyAsync(mf->d_sc + SC_TOL, mf->h_sc + SC_TOL, sizeof(double), hipMemcpyHostToDevice, s));
+  mf->h_st[ST_MAXIT] = prm->max_iter;
+  HIP_TRY(hipMemcpyAsync(mf->d_st + ST_MAXIT, mf->h_st + ST_MAXIT, sizeof(int), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s)); // pinned staging words are reused below
+  const hipEvent_t ev0 = mf->ev_solve[0], ev1 = mf->ev_solve[1];
+  HIP_TRY(hipEventRecord(ev0, s));
+  // g = -b, x = 0; z = P g; g.g and g.z in one all-reduce; res0, gh = g.z, stop test; d = -z
+  hipLaunchKernelGGL(pcg_init_kernel, dim3(grid1), dim3(VB), 0, s, b, x, g, n, mf->d_partials);
+  hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
+  KERNEL_CHECK();
+  BP5_TRY(apply_P(g, z));
+  hipLaunchKernelGGL(dot_kernel, dim3(grid2), dim3(VB), 0, s, g, z, n, mf->d_partials);
+  hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GDG, (const int *)nullptr);
+  KERNEL_CHECK();
+  BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
+  hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+  hipLaunchKernelGGL(pcg_direction_kernel<true>, dim3(gridf), dim3(VB), 0, s, d, z, n, mf->d_sc, mf->d_st);
+  KERNEL_CHECK();
+  const int check = prm->check_every;
+  // check_every = 0: the operator and the preconditioner are not gated on the stop flag (a preconditioner is any callback), so the host
+  // looks at the flag itself -- with a lag of DONE_LAG iterations (the copy of iteration k's flag is waited for after iteration k + DONE_LAG
+  // has been enqueued): the queue never drains, and at most DONE_LAG iterations run on a stopped solve, whose kernels leave x, g, d alone
+  constexpr int DONE_LAG = 2;
+  if (check <= 0) {
+    if (!mf->h_done) HIP_TRY(hipHostMalloc((void **)&mf->h_done, (DONE_LAG + 1) * sizeof(int)));
+    for (hipEvent_t &e : mf->ev_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  for (int it = 1; it <= prm->max_iter; ++it) {
+    BP5_TRY(apply_A(d, h));
+    hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_st, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_DH, mf->d_st);
+    KERNEL_CHECK();
+    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1));
+    hipLaunchKernelGGL(pcg_update_kernel, dim3(grid2), dim3(VB), 0, s, x, g, d, h, n, mf->d_sc, mf->d_st, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GG, mf->d_st);
+    KERNEL_CHECK();
+    BP5_TRY(apply_P(g, z)); // (the partial sums of g.g are in SC_GG already: the preconditioner may run reductions of its own)
+    hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid2), dim3(VB), 0, s, g, z, n, mf->d_st, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GDG, mf->d_st);
+    KERNEL_CHECK();
+    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); // g.g, g.z
+    hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res, ++it, stop test, beta = g.z / gh
+    hipLaunchKernelGGL(pcg_direction_kernel<false>, dim3(gridf), dim3(VB), 0, s, d, z, n, mf->d_sc, mf->d_st);
+    KERNEL_CHECK();
+    if (check > 0 && it % check == 0 && it < prm->max_iter) {
+      BP5_TRY(poll_state(mf));
+      if (mf->h_st[ST_DONE]) break;
+    } else if (check <= 0 && it < prm->max_iter) {
+      const int slot = it % (DONE_LAG + 1);
+      HIP_TRY(hipMemcpyAsync(mf->h_done + slot, mf->d_st + ST_DONE, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipEventRecord(mf->ev_done[slot], s));
+      if (it > DONE_LAG) {
+        const int seen = (it - DONE_LAG) % (DONE_LAG + 1);
+        HIP_TRY(hipEventSynchronize(mf->ev_done[seen]));
+        if (mf->h_done[seen]) break;
+      }
+    }
+  }
+  HIP_TRY(hipEventRecord(ev1, s));
+  BP5_TRY(poll_state(mf));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  memset(res, 0, sizeof(*res));
+  res->iterations = mf->h_st[ST_ITER];
+  res->residual = mf->h_sc[SC_RES];
+  res->initial_residual = mf->h_sc[SC_RES0];
+  res->solve_ms = ms;
+  const bool dist_solve = mf->comm && !mf->neighbors.empty();
+  res->exchange_schedule = !dist_solve || vmult ? 0 : overlap_wanted(mf) ? 3 : 1;
+  if (!vmult) strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
+  if (mf->h_st[ST_BREAKDOWN]) return fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
+  return BP5_OK;
+}
+
+// ------------------------------------------------------------------------------------ PreconditionChebyshev
+struct bp5_chebyshev {
+  bp5_mf *mf = nullptr;
+  const double *coef = nullptr;
+  bp5_vmult_fn vmult = nullptr;
+  void *ctx = nullptr;
+  const double *inv_diag = nullptr;
+  int degree = 1;
+  double min_est = 0.0, max_est = 0.0, min_used = 0.0, max_used = 0.0, theta = 1.0, delta = 0.0;
+  int cg_its = 0;
+  std::vector<double> f1, f2; // step k = 1 .. degree-1
+  double *w = nullptr, *t = nullptr; // the other iterate and t = A x_k: owned + ghost each (one allocation)
+};
+
+// t = A x in overwrite mode (zero_dst = 1 and the Dirichlet copy); the distributed apply when there are neighbours
+static int cheb_apply(bp5_chebyshev *c, double *x, double *t)
+{
+  if (c->vmult) {
+    const int st = c->vmult(c->ctx, t, x);
+    return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
+  }
+  bp5_mf *mf = c->mf;
+  if (mf->comm && !mf->neighbors.empty()) return bp5_apply_distributed(mf, c->coef, x, t, 1);
+  return bp5_apply(mf, c->coef, x, t, 1);
+}
+
+// one Chebyshev step kernel: FORM as chebyshev_step_kernel; diag present / absent and the streaming policy (BP5_TUNE_UPDATE_NT) resolved here
+template <int FORM>
+static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, const double *x_old, const double *src, double f1, double f2)
+{
+  bp5_mf *mf = c->mf;
+  const size_t n = mf->n_owned;
+  if (!n) return BP5_OK;
+  const dim3 grid(stream_grid_flat(mf, n, 2)), block(VB);
+  const bool nt = mf->tune[BP5_TUNE_UPDATE_NT] != 0;
+  const double *dg = c->inv_diag, *t = c->t;
+  if (dg) {
+    if (nt) hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, true>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
+    else hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, false>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
+  } else {
+    if (nt) hipLaunchKernelGGL((chebyshev_step_kernel<FORM, false, true>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
+    else hipLaunchKernelGGL((chebyshev_step_kernel<FORM, false, false>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
+  }
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+
+extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag,
+                                    const bp5_chebyshev_params *prm, bp5_chebyshev **out)
+{
+  if (!mf || !prm || !out || (!vmult && !coef && mf->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (prm->degree < 1) return fail(BP5_ERR_INVALID, "Chebyshev degree < 1");
+  const bool given = prm->max_eigenvalue > 0.0 && prm->min_eigenvalue > 0.0;
+  if (given && !(prm->min_eigenvalue < prm->max_eigenvalue)) return fail(BP5_ERR_INVALID, "Chebyshev bounds: need 0 < min_eigenvalue < max_eigenvalue");
+  if (!given && prm->eig_cg_n_iterations < 1) return fail(BP5_ERR_INVALID, "eig_cg_n_iterations < 1 and no bounds given");
+  if (inv_diag && !aligned16(inv_diag)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(mf->device));
+  std::unique_ptr<bp5_chebyshev> c(new bp5_chebyshev);
+  c->mf = mf; c->coef = coef; c->vmult = vmult; c->ctx = ctx; c->inv_diag = inv_diag; c->degree = prm->degree;
+  const size_t nb = (std::max<size_t>(mf->n_local(), 2) * sizeof(double) + 4095) / 4096 * 4096;
+  char *base = nullptr;
+  HIP_TRY(hipMalloc((void **)&base, 2 * nb));
+  c->w = (double *)base;
+  c->t = (double *)(base + nb);
+  struct Free { bp5_chebyshev *c; bool keep = false; ~Free() { if (!keep && c->w) hipFree(c->w); } } guard{c.get()};
+  HIP_TRY(hipMemsetAsync(base, 0, 2 * nb, mf->stream));
+  if (given) {
+    c->min_used = prm->min_eigenvalue;
+    c->max_used = prm->max_eigenvalue;
+  } else {
+    // Jacobi-PCG on A x = v (x_0 = 0) with the alpha / beta history on the device; one copy to the host at the end
+    const int m = prm->eig_cg_n_iterations;
+    std::vector<double> v(std::max<size_t>(mf->n_owned, 1), 0.0);
+    for (uint32_t i = 0; i < mf->n_owned; ++i) {
+      const uint64_t id = prm->start_ids_host ? prm->start_ids_host[i] : i;
+      v[i] = (double)(int)(id % 11u) - 5.0;
+    }
+    double *vb = c->w, *xs = c->t, *hist = nullptr;
+    HIP_TRY(hipMemcpyAsync(vb, v.data(), mf->n_owned * sizeof(double), hipMemcpyHostToDevice, mf->stream));
+    BP5_TRY(bp5_set_constrained(mf, 0.0, vb));
+    double vnorm = 0.0;
+    BP5_TRY(bp5_vec_l2_norm(mf, vb, mf->n_owned, &vnorm));
+    HIP_TRY(hipMalloc((void **)&hist, 2 * (size_t)m * sizeof(double)));
+    struct FreeHist { bp5_mf *mf; double *h; ~FreeHist() { mf->cg_history = nullptr; mf->cg_history_cap = 0; hipFree(h); } } hguard{mf, hist};
+    HIP_TRY(hipMemsetAsync(hist, 0, 2 * (size_t)m * sizeof(double), mf->stream));
+    mf->cg_history = hist;
+    mf->cg_history_cap = m;
+    bp5_cg_params cp{};
+    cp.variant = BP5_CG_PLAIN; cp.max_iter = m; cp.abs_tol = 1e-5 * vnorm; cp.check_every = 0; cp.profile = 0;
+    bp5_cg_result cr{};
+    BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr));
+    mf->cg_history = nullptr;
+    std::vector<double> h(2 * (size_t)m);
+    HIP_TRY(hipMemcpy(h.data(), hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int k = cr.iterations;
+    if (k < 1) return fail(BP5_ERR_INVALID, "Chebyshev estimate: the start vector is zero (no unconstrained DoF)");
+    std::vector<double> T(k), E(std::max(k - 1, 1)), eig(k);
+    for (int j = 0; j < k; ++j) {
+      T[j] = 1.0 / h[2 * j] + (j > 0 ? h[2 * j - 1] / h[2 * j - 2] : 0.0);
+      if (j + 1 < k) E[j] = std::sqrt(h[2 * j + 1]) / h[2 * j];
+    }
+    BP5_TRY(bp5_tridiagonal_eigenvalues(k, T.data(), E.data(), eig.data()));
+    c->cg_its = k;
+    c->min_est = eig.front();
+    c->max_est = eig.back();
+    c->max_used = 1.2 * c->max_est;
+    c->min_used = prm->smoothing_range > 1.0 ? c->max_used / prm->smoothing_range : std::min(0.9 * c->max_used, c->min_est);
+  }
+  if (!(c->max_used > c->min_used) || !(c->min_used > 0.0)) return fail(BP5_ERR_BREAKDOWN, "Chebyshev: degenerate eigenvalue bounds");
+  c->theta = 0.5 * (c->max_used + c->min_used);
+  c->delta = 0.5 * (c->max_used - c->min_used);
+  double rho = c->delta / c->theta;
+  for (int k = 1; k < c->degree; ++k) {
+    const double rho_new = 1.0 / (2.0 * c->theta / c->delta - rho);
+    c->f1.push_back(rho_new * rho);
+    c->f2.push_back(2.0 * rho_new / c->delta);
+    rho = rho_new;
+  }
+  HIP_TRY(hipStreamSynchronize(mf->stream));
+  guard.keep = true;
+  *out = c.release();
+  return BP5_OK;
+}
+
+extern "C" int bp5_chebyshev_eigenvalues(const bp5_chebyshev *c, double *min_est, double *max_est, double *min_used, double *max_used, int *cg_its)
+{
+  if (!c) return fail(BP5_ERR_INVALID, "null argument");
+  if (min_est) *min_est = c->min_est;
+  if (max_est) *max_est = c->max_est;
+  if (min_used) *min_used = c->min_used;
+  if (max_used) *max_used = c->max_used;
+  if (cg_its) *cg_its = c->cg_its;
+  return BP5_OK;
+}
+
+// dst = P src: x_1 = D^-1 src / theta, then degree-1 times t = A x_k and one step kernel.  x_{k+1} lands in x_{k-1}'s buffer: the odd
+// iterates live in one buffer, the even ones in the other, chosen so that x_degree is dst
+extern "C" int bp5_chebyshev_vmult(void *cv, double *dst, double *src)
+{
+  bp5_chebyshev *c = static_cast<bp5_chebyshev *>(cv);
+  if (!c || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  if (!aligned16(dst) || !aligned16(src)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  if (dst == src) return fail(BP5_ERR_INVALID, "Chebyshev vmult: dst and src must differ");
+  double *odd = (c->degree & 1) ? dst : c->w, *even = (c->degree & 1) ? c->w : dst;
+  BP5_TRY(cheb_step_launch<0>(c, odd, nullptr, nullptr, src, 0.0, 1.0 / c->theta));
+  for (int k = 1; k < c->degree; ++k) {
+    double *xk = (k & 1) ? odd : even, *xo = (k & 1) ? even : odd; // x_k, and x_{k-1} (== x_0 = 0 for k = 1), which receives x_{k+1}
+    BP5_TRY(cheb_apply(c, xk, c->t));
+    if (k == 1) BP5_TRY(cheb_step_launch<2>(c, xo, xk, nullptr, src, c->f1[0], c->f2[0]));
+    else BP5_TRY(cheb_step_launch<1>(c, xo, xk, xo, src, c->f1[k - 1], c->f2[k - 1]));
+  }
+  return BP5_OK;
+}
+
+// smoother: x_0 = dst; x_1 = x_0 + D^-1 (src - A x_0) / theta; then the recurrence (degree operator applications).  Even degree: x_0 stays
+// in dst and x_degree lands there; odd degree: x_0 is copied to the work vector first
+extern "C" int bp5_chebyshev_step(bp5_chebyshev *c, double *dst, double *src)
+{
+  if (!c || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  if (!aligned16(dst) || !aligned16(src)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  if (dst == src) return fail(BP5_ERR_INVALID, "Chebyshev step: dst and src must differ");
+  bp5_mf *mf = c->mf;
+  double *a = dst, *b = c->w; // a: x_0, x_2, ...   b: x_1, x_3, ...
+  if (c->degree & 1) {
+    HIP_TRY(hipMemcpyAsync(c->w, dst, mf->n_owned * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
+    a = c->w; b = dst;
+  }
+  BP5_TRY(cheb_apply(c, a, c->t));
+  BP5_TRY(cheb_step_launch<3>(c, b, a, nullptr, src, 0.0, 1.0 / c->theta));
+  for (int k = 1; k < c->degree; ++k) {
+    double *xk = (k & 1) ? b : a, *xo = (k & 1) ? a : b;
+    BP5_TRY(cheb_apply(c, xk, c->t));
+    BP5_TRY(cheb_step_launch<1>(c, xo, xk, xo, src, c->f1[k - 1], c->f2[k - 1]));
+  }
+  return BP5_OK;
+}
+
+extern "C" int bp5_chebyshev_destroy(bp5_chebyshev *c)
+{
+  if (!c) return BP5_OK;
+  hipSetDevice(c->mf->device);
+  hipStreamSynchronize(c->mf->stream);
+  if (c->w) hipFree(c->w);
+  delete c;
+  return BP5_OK;
 }

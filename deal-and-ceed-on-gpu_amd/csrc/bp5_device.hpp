@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 
@@ -112,6 +113,11 @@ struct bp5_mf {
   int *d_st = nullptr;
   double *ws_g = nullptr, *ws_d = nullptr, *ws_h = nullptr, *d_evec = nullptr;
   char *ws_base = nullptr;
+  double *ws_z = nullptr;     // preconditioner output of bp5_cg_solve_preconditioned (allocated on first use)
+  double *cg_history = nullptr; int cg_history_cap = 0;
+  // bp5_cg_solve_preconditioned with check_every = 0: the stop flag of iteration k copied to h_done[k % 3] behind ev_done[k % 3]
+  int *h_done = nullptr; // pinned
+  hipEvent_t ev_done[3] = {nullptr, nullptr, nullptr}; // plain solve: alpha / beta per iteration into this device array (Chebyshev estimate)
   unsigned long long *d_stamps = nullptr;
   double *h_sc = nullptr; // pinned
   int *h_st = nullptr;    // pinned

@@ -3579,6 +3579,131 @@ static __global__ void cgm_init_control_kernel(double *sc, int *st)
   st[ST_DONE] = (sc[SC_RES] <= sc[SC_TOL]) ? 1 : 0;
 }
 
+// ---- CG with a general preconditioner z = P g (bp5_cg_solve_preconditioned).  g, d, h as in the plain solver; z is the
+// preconditioner's output.  Scalars: SC_GG = g.g, SC_GDG = g.z (the slot of g.Dg), the control step is cg_control_kernel's.
+// init: x = 0, g = -b, partial sums of g.g
+static __global__ void __launch_bounds__(VB) pcg_init_kernel(const double *b, double *x, double *g, size_t n, double *partials)
+{
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB;
+  for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
+    const double gi = -b[i];
+    x[i] = 0.0; g[i] = gi;
+    acc[0] += gi * gi;
+  }
+  block_reduce_store<1>(acc, partials);
+}
+// x += alpha d ; g += alpha h ; partial sums of g.g   with alpha = gh / dh
+static __global__ void __launch_bounds__(VB) pcg_update_kernel(double *x, double *g, const double *d, const double *h, size_t n, const double *sc,
+                                                       const int *st, double *partials)
+{
+  if (st[ST_DONE]) return;
+  const double alpha = sc[SC_GH] / sc[SC_DH];
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      double2 xv = *reinterpret_cast<double2 *>(x + i), gv = *reinterpret_cast<double2 *>(g + i);
+      const double2 dv = *reinterpret_cast<const double2 *>(d + i), hv = *reinterpret_cast<const double2 *>(h + i);
+      xv.x += alpha * dv.x; xv.y += alpha * dv.y;
+      gv.x += alpha * hv.x; gv.y += alpha * hv.y;
+      *reinterpret_cast<double2 *>(x + i) = xv;
+      *reinterpret_cast<double2 *>(g + i) = gv;
+      acc[0] += gv.x * gv.x + gv.y * gv.y;
+    } else {
+      const double xi = x[i] + alpha * d[i], gi = g[i] + alpha * h[i];
+      x[i] = xi; g[i] = gi;
+      acc[0] += gi * gi;
+    }
+  }
+  block_reduce_store<1>(acc, partials);
+}
+// partial sums of x.y; a stopped solve leaves the partials alone (finalize_kernel is gated on the same flag)
+static __global__ void __launch_bounds__(VB) pcg_dot_kernel(const double *x, const double *y, size_t n, const int *st, double *partials)
+{
+  if (st[ST_DONE]) return;
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
+      acc[0] += a.x * b.x + a.y * b.y;
+    } else
+      acc[0] += x[i] * y[i];
+  }
+  block_reduce_store<1>(acc, partials);
+}
+// d = beta d - z   (FIRST: d = -z, d not read)
+template <bool FIRST>
+__global__ void __launch_bounds__(VB) pcg_direction_kernel(double *d, const double *z, size_t n, const double *sc, const int *st)
+{
+  if (st[ST_DONE]) return;
+  const double beta = FIRST ? 0.0 : sc[SC_BETA];
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      const double2 zv = *reinterpret_cast<const double2 *>(z + i);
+      double2 dv = FIRST ? double2{0.0, 0.0} : *reinterpret_cast<const double2 *>(d + i);
+      dv.x = FIRST ? -zv.x : beta * dv.x - zv.x;
+      dv.y = FIRST ? -zv.y : beta * dv.y - zv.y;
+      *reinterpret_cast<double2 *>(d + i) = dv;
+    } else
+      d[i] = FIRST ? -z[i] : beta * d[i] - z[i];
+  }
+}
+// Lanczos history of a plain solve (the eigenvalue estimate of PreconditionChebyshev): after the control step of iteration k
+// (1-based), hist[2k-2] = alpha_{k-1}, hist[2k-1] = beta_{k-1} (0 when the solve stopped there: no beta was formed)
+static __global__ void cg_record_kernel(const double *sc, const int *st, double *hist, int cap)
+{
+  const int k = st[ST_ITER];
+  if (k < 1 || k > cap || st[ST_BREAKDOWN]) return;
+  hist[2 * k - 2] = sc[SC_ALPHA];
+  hist[2 * k - 1] = st[ST_DONE] ? 0.0 : sc[SC_BETA];
+}
+
+// ---- PreconditionChebyshev: one launch per Chebyshev step, pointwise over the owned entries, t = A x_k written just before by the operator:
+//   FORM 0  x_1     = f2 D^-1 src                                  (first step of vmult, f2 = 1/theta: reads src, diag)
+//   FORM 1  x_{k+1} = x_k + f1 (x_k - x_{k-1}) + f2 D^-1 (src - t) (reads x, x_old, src, t, diag: 48 B/DoF, 40 without diag)
+//   FORM 2  the same with x_{k-1} = 0                               (second step of vmult: x_old not read)
+//   FORM 3  x_1     = x_0 + f2 D^-1 (src - t)                       (first step of step(): dst improved from its value)
+// x_new goes to x_old's buffer (pointer rotation by the host; FORM 0 / 3: a separate buffer).  NT: t and x_old are read for the last
+// time here -- non-temporal loads under the handle's streaming policy for once-used data (BP5_TUNE_UPDATE_NT, as cgm_update_kernel).
+template <int FORM, bool DIAG, bool NT>
+__global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const double *x, const double *x_old, const double *src, const double *t,
+                                                            const double *diag, size_t n, double f1, double f2)
+{
+  auto load = [](const double *p, bool nt) -> double2 {
+    if (nt) { const bp5_d2u v = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(p)); return double2{v.x, v.y}; }
+    return *reinterpret_cast<const double2 *>(p);
+  };
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      const double2 s = load(src + i, false);
+      const double2 dg = DIAG ? load(diag + i, false) : double2{1.0, 1.0};
+      double2 r;
+      if constexpr (FORM == 0) {
+        r.x = f2 * (dg.x * s.x);
+        r.y = f2 * (dg.y * s.y);
+      } else {
+        const double2 tv = load(t + i, NT), xv = load(x + i, false);
+        const double2 xo = FORM == 1 ? load(x_old + i, NT) : double2{0.0, 0.0};
+        const double2 f1x = FORM == 3 ? double2{0.0, 0.0} : double2{f1 * (xv.x - xo.x), f1 * (xv.y - xo.y)};
+        r.x = xv.x + f1x.x + f2 * (dg.x * (s.x - tv.x));
+        r.y = xv.y + f1x.y + f2 * (dg.y * (s.y - tv.y));
+      }
+      *reinterpret_cast<double2 *>(x_new + i) = r;
+    } else {
+      const double dg = DIAG ? diag[i] : 1.0;
+      if constexpr (FORM == 0) x_new[i] = f2 * (dg * src[i]);
+      else {
+        const double xv = x[i], xo = FORM == 1 ? x_old[i] : 0.0;
+        x_new[i] = xv + (FORM == 3 ? 0.0 : f1 * (xv - xo)) + f2 * (dg * (src[i] - t[i]));
+      }
+    }
+  }
+}
+
 // ---- self-check of the in-launch stream wait-value schedules (bp5_device.hip: halo_streams).  The producer counts itself in exactly like
 // apply_block_kernel's signal_part_done and then stays alive until the consumer -- enqueued on the waiting stream behind
 // hipStreamWaitValue64 -- has run, or 2 ms have passed: *result = 1 says the wait was released WHILE the producing kernel was running

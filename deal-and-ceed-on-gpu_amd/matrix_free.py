@@ -7,6 +7,7 @@ C ABI (include/bp5.h).  Names, argument meaning and error behaviour follow the r
   IterationNumberControl . bp5/step-64.cu:443-445 (last_step)
   SolverCG ............... deal.II SolverCG, call site bp5/step-64.cu:446-453
   SolverCGFullMerge ...... bp5/solver.h:16-30,343-542 (x-update schedule fixed)
+  PreconditionChebyshev .. deal.II PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (Chebyshev-Jacobi, include/bp5.h)
 
 Vectors are torch float64 CUDA tensors of n_owned + n_ghost entries (torch is plumbing for
 device memory / streams / the process group only -- no torch op is on the hot path)."""
@@ -437,6 +438,109 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2}
 
 
+def _callback(obj, mf, failure):
+    """bp5_vmult_fn that runs obj.vmult(dst, src) on torch views of the library's device vectors (owned + ghost length).  It enqueues
+    on the current stream; no exception may cross the C boundary: it is kept in `failure` and status 1 is returned."""
+    torch = _torch()
+
+    def view(p):
+        return torch.as_tensor(_DeviceArray(p, mf.n_local), device=f"cuda:{mf.device}")
+
+    def callback(_ctx, dst, src):
+        try:
+            obj.vmult(view(dst), view(src))
+            return 0
+        except Exception as e:         # noqa: BLE001
+            failure.append(e)
+            return 1
+
+    return _lib.VMULT_FN(callback)
+
+
+class PreconditionChebyshev:
+    """== PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (deal.II): a Chebyshev polynomial of degree `degree` in D^-1 A on the
+    eigenvalue bounds of D^-1 A, estimated at initialize() by a few CG-Lanczos steps (bp5_chebyshev_create, include/bp5.h).  vmult is
+    degree-1 operator applications and degree pointwise step launches, with no dot product: only the operator's halo exchanges.
+
+    A: a PoissonOperator / HelmholtzOperator (its coef, natively) or any object with `mf_data` and `vmult(dst, src)` (through a
+    callback).  AdditionalData.preconditioner: a DiagonalMatrix holding the INVERSE diagonal (compute_diagonal(invert=True)), None = identity."""
+
+    class AdditionalData:
+        def __init__(self, degree=1, smoothing_range=0.0, eig_cg_n_iterations=8, max_eigenvalue=0.0, min_eigenvalue=0.0, preconditioner=None):
+            self.degree, self.smoothing_range, self.eig_cg_n_iterations = int(degree), float(smoothing_range), int(eig_cg_n_iterations)
+            self.max_eigenvalue, self.min_eigenvalue = float(max_eigenvalue), float(min_eigenvalue)
+            self.preconditioner = preconditioner
+
+    def __init__(self):
+        self._h = None
+        self._keep = []
+
+    def initialize(self, A, data=None):
+        self.clear()
+        data = data if data is not None else PreconditionChebyshev.AdditionalData()
+        mf = A.mf_data
+        self.A, self.mf_data, self.data = A, mf, data
+        inv = _vals(data.preconditioner.get_vector()) if data.preconditioner is not None else None
+        ids = getattr(mf.mesh, "global_ids", None)
+        ids = np.ascontiguousarray(ids[:mf.n_owned], dtype=np.uint64) if ids is not None else None
+        prm = _lib.ChebyshevParams(data.degree, data.smoothing_range, data.eig_cg_n_iterations, data.max_eigenvalue, data.min_eigenvalue,
+                                   ids.ctypes.data if ids is not None else None)
+        self._failure = []
+        if isinstance(A, PoissonOperator):
+            coef, cb = _ptr(A.coef), None
+        else:
+            coef, cb = None, _callback(A, mf, self._failure)
+        h = C.c_void_p()
+        status = _lib.lib().bp5_chebyshev_create(mf.handle, coef, C.cast(cb, C.c_void_p) if cb is not None else None, None,
+                                                 _ptr(inv, mf.n_owned) if inv is not None else None, C.byref(prm), C.byref(h))
+        if self._failure:
+            raise self._failure[0]
+        _lib.check(status)
+        self._h = h
+        self._keep = [inv, cb]           # the inverse diagonal and the callback live as long as the handle
+        return self
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, "PreconditionChebyshev.initialize has not been called")
+        return self._h
+
+    def _run(self, fn, dst, src):
+        mf = self.mf_data
+        status = fn(self.handle, _ptr(_vals(dst), mf.n_local), _ptr(_vals(src), mf.n_local))
+        if self._failure:
+            raise self._failure.pop(0)
+        _lib.check(status)
+
+    def vmult(self, dst, src):
+        """dst = P src (dst's prior content ignored); enqueued on the handle's stream."""
+        self._run(_lib.lib().bp5_chebyshev_vmult, dst, src)
+
+    def step(self, dst, src):
+        """Smoother: dst improved from its current value by `degree` Chebyshev steps on A dst = src."""
+        self._run(_lib.lib().bp5_chebyshev_step, dst, src)
+
+    def estimated_eigenvalues(self):
+        """dict(min_est, max_est, min_used, max_used, cg_its): the CG-Lanczos estimate and the bounds the polynomial uses."""
+        v = [C.c_double() for _ in range(4)]
+        k = C.c_int()
+        _lib.check(_lib.lib().bp5_chebyshev_eigenvalues(self.handle, *[C.byref(x) for x in v], C.byref(k)))
+        return dict(min_est=v[0].value, max_est=v[1].value, min_used=v[2].value, max_used=v[3].value, cg_its=k.value)
+
+    def clear(self):
+        if self._h:
+            _lib.lib().bp5_chebyshev_destroy(self._h)
+            self._h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
 class _SolverBase:
     variant = CG_PLAIN
 
@@ -447,34 +551,42 @@ class _SolverBase:
         """== cg.solve(A, x, b, preconditioner), bp5/step-64.cu:450-453,492-495.  x0 = 0.
         A PoissonOperator runs entirely inside bp5_cg_solve; any other object with `mf_data` (vector layout, stream) and
         `vmult(dst, src)` is solved through bp5_cg_solve_operator -- the solvers need nothing of A but vmult
-        (bp5/solver.h:25-30,377,475)."""
+        (bp5/solver.h:25-30,377,475).  The preconditioner: None / DiagonalMatrix (the solvers' diag), a PreconditionChebyshev (native:
+        bp5_cg_solve_preconditioned with bp5_chebyshev_vmult), or any other object with vmult(dst, src) (through a callback; SolverCG only)."""
         mf = A.mf_data
         x, b = _vals(x), _vals(b)
-        diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None
+        general = preconditioner is not None and not hasattr(preconditioner, "get_vector")
+        if general and not hasattr(preconditioner, "vmult"):
+            raise BP5Error(1, "the preconditioner needs get_vector() (diagonal) or vmult(dst, src)")
+        if general and self.variant != CG_PLAIN:
+            raise BP5Error(1, f"{type(self).__name__} takes a diagonal preconditioner only (None or DiagonalMatrix); use SolverCG")
         prm = _lib.CGParams(self.variant, self.control.max_steps, self.control.tolerance, self.check_every,
                             int(self.profile))   # False / True / 2 (phase stamps)
         res = _lib.CGResult()
-        dptr = _ptr(diag, mf.n_owned) if diag is not None else None
-        if isinstance(A, PoissonOperator):
-            status = _lib.lib().bp5_cg_solve(mf.handle, _ptr(A.coef), dptr, _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
+        failure = []
+        native = isinstance(A, PoissonOperator)
+        if general:
+            if isinstance(preconditioner, PreconditionChebyshev):
+                pfn, pctx = C.cast(_lib.lib().bp5_chebyshev_vmult, C.c_void_p), preconditioner.handle
+            else:
+                pcb = _callback(preconditioner, mf, failure)
+                pfn, pctx = C.cast(pcb, C.c_void_p), None
+            acb = None if native else _callback(A, mf, failure)
+            status = _lib.lib().bp5_cg_solve_preconditioned(mf.handle, _ptr(A.coef) if native else None,
+                                                            C.cast(acb, C.c_void_p) if acb is not None else None, None, pfn, pctx,
+                                                            _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
+            if isinstance(preconditioner, PreconditionChebyshev) and preconditioner._failure:
+                failure.append(preconditioner._failure.pop(0))
         else:
-            torch, failure = _torch(), []
-
-            def view(p):
-                return torch.as_tensor(_DeviceArray(p, mf.n_local), device=f"cuda:{mf.device}")
-
-            def callback(_ctx, dst, src):      # enqueues on the current stream; no exception may cross the C boundary
-                try:
-                    A.vmult(view(dst), view(src))
-                    return 0
-                except Exception as e:         # noqa: BLE001
-                    failure.append(e)
-                    return 1
-
-            cb = _lib.VMULT_FN(callback)
-            status = _lib.lib().bp5_cg_solve_operator(mf.handle, cb, None, dptr, _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
-            if failure:
-                raise failure[0]
+            diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None
+            dptr = _ptr(diag, mf.n_owned) if diag is not None else None
+            if native:
+                status = _lib.lib().bp5_cg_solve(mf.handle, _ptr(A.coef), dptr, _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
+            else:
+                cb = _callback(A, mf, failure)
+                status = _lib.lib().bp5_cg_solve_operator(mf.handle, cb, None, dptr, _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
+        if failure:
+            raise failure[0]
         c = self.control
         c._last_step, c._last_value, c._initial_value = res.iterations, res.residual, res.initial_residual
         c.solve_ms, c.apply_ms_avg, c.apply_launches = res.solve_ms, res.apply_ms_avg, res.apply_launches

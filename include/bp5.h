@@ -458,6 +458,57 @@ int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, const doubl
  * energy, so the pass over d and h disappears.  0 switches back to the separate kernels. */
 int bp5_mf_set_cg_fusion(bp5_mf *mf, int on);
 
+/* cg.solve(A, x, b, preconditioner) with ANY preconditioner: z = P g is the caller's callback (bp5_vmult_fn shape: enqueue
+ * dst = P src on the handle's stream, every owned entry of dst defined, ghost ranges usable as scratch).  A is the library's
+ * operator (coef, vmult == NULL) or any operator through its callback (vmult != NULL; coef then ignored).  BP5_CG_PLAIN only
+ * (BP5_CG_MERGED: BP5_ERR_INVALID -- its recurrence has no place for a preconditioner application).  Per iteration: h = A d,
+ * d.h, x += alpha d, g += alpha h, z = P g, g.g and g.z in ONE all-reduce, d = beta d - z.  The preconditioner runs in every
+ * iteration the host enqueues (up to the host's look at the convergence flag); once the device has stopped the solve its output
+ * is ignored, so the result is bitwise the same for every check_every.  Neither the operator nor the preconditioner is gated on the
+ * device's stop flag, so with check_every = 0 the host looks at the flag itself, two iterations behind the work it has enqueued (an
+ * asynchronous copy per iteration; the queue never drains): at most two iterations' applications run after convergence, never max_iter.
+ * precond may be bp5_chebyshev_vmult with its handle. */
+int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, bp5_vmult_fn precond, void *precond_ctx,
+                                const double *b, double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
+
+/* ------------------------------------------------------------------------------------------ */
+/* PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (deal.II): a Chebyshev polynomial in D^-1 A with D^-1 = inv_diag
+ * (NULL: identity), on the spectrum bounds [min_used, max_used] of D^-1 A, theta / delta = their midpoint / half-width:
+ *   vmult (dst = P src, x_0 = 0):   x_1 = D^-1 src / theta;
+ *                                   x_{k+1} = x_k + f1_k (x_k - x_{k-1}) + f2_k D^-1 (src - A x_k),  k = 1 .. degree-1,
+ *                                   rho_0 = delta / theta, rho_k = 1 / (2 theta / delta - rho_{k-1}), f1_k = rho_k rho_{k-1},
+ *                                   f2_k = 2 rho_k / delta;   1 - lambda p(lambda) = T_degree((theta - lambda)/delta) / T_degree(theta/delta)
+ *   step  (dst improved from its current value x_0): x_1 = x_0 + D^-1 (src - A x_0) / theta, then the same recurrence: degree operator
+ *                                   applications.
+ * Each step is ONE launch of a pointwise kernel (48 bytes per DoF: x, x_old, src, t = A x_k, diag read, x_new written into x_old's
+ * buffer; 40 without diag); the scalars are kernel arguments (known on the host at create): vmult and step enqueue on the handle's
+ * stream and never synchronise the host.  No dot product and no all-reduce: only the operator's halo exchanges.
+ * The operator is applied in overwrite mode (zero_dst = 1, Dirichlet copy), with neighbours as bp5_apply_distributed; A is the
+ * library's operator (coef, vmult == NULL) or any operator through its callback. */
+typedef struct {
+  int degree;              /* >= 1; degree 1 == dst = D^-1 src / theta (Jacobi); degree-1 operator applications per vmult       */
+  double smoothing_range;  /* > 1: min_used = max_used / smoothing_range; <= 1: min_used = min(0.9 max_used, min_est)          */
+  int eig_cg_n_iterations; /* CG-Lanczos steps of the estimate (deal.II default 8); the estimate stops early at ||r|| <= 1e-5 ||v|| */
+  double max_eigenvalue, min_eigenvalue; /* both > 0: used as given (min_used, max_used), no estimate                          */
+  const uint64_t *start_ids_host; /* [n_owned] global DoF ids (bp5_mesh_view.global_ids_host) for the estimate's start vector
+                                     v_i = (id mod 11) - 5 (0 on Dirichlet DoFs): the same vector on every rank count; NULL = the
+                                     local index                                                                              */
+} bp5_chebyshev_params;
+typedef struct bp5_chebyshev bp5_chebyshev;
+/* Setup (synchronous): unless both bounds are given, Jacobi-PCG (D^-1 = inv_diag) on A x = v, x_0 = 0, eig_cg_n_iterations steps,
+ * its alpha / beta history copied to the host once at the end; Lanczos tridiagonal T_kk = 1/alpha_k + beta_{k-1}/alpha_{k-1},
+ * T_{k,k+1} = sqrt(beta_k)/alpha_k; min_est / max_est = its extreme eigenvalues; max_used = 1.2 max_est.  Dot products are
+ * all-reduced when a communicator is set.  inv_diag must stay valid for the life of the handle. */
+int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag,
+                         const bp5_chebyshev_params *params, bp5_chebyshev **out);
+int bp5_chebyshev_eigenvalues(const bp5_chebyshev *c, double *min_est, double *max_est, double *min_used, double *max_used, int *cg_its);
+int bp5_chebyshev_vmult(void *c, double *dst, double *src);          /* bp5_vmult_fn shape: dst = P src, dst's prior content ignored */
+int bp5_chebyshev_step(bp5_chebyshev *c, double *dst, double *src);  /* smoother: dst improved from its current value              */
+int bp5_chebyshev_destroy(bp5_chebyshev *c);
+/* all eigenvalues of the symmetric tridiagonal matrix (diag[n], offdiag[n-1]), ascending; Sturm-sequence bisection on the host
+ * (no LAPACK, no GPU) */
+int bp5_tridiagonal_eigenvalues(int n, const double *diag, const double *offdiag, double *eig_ascending_host);
+
 /* event helpers so a host in another language can time on the handle's stream */
 typedef struct bp5_event bp5_event;
 int bp5_event_create(bp5_event **out);

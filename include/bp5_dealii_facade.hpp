@@ -609,6 +609,64 @@ namespace internal {
 template <typename T, typename = void> struct has_coef : std::false_type {};
 template <typename T> struct has_coef<T, decltype((void)std::declval<const T &>().coef())> : std::true_type {};
 } // namespace internal
+// == PreconditionChebyshev<MatrixType, VectorType, DiagonalMatrix> (deal.II; include/bp5.h: bp5_chebyshev_*): a Chebyshev polynomial in
+// D^-1 A, D^-1 = AdditionalData::preconditioner (the INVERSE diagonal, e.g. compute_diagonal(invert); nullptr = identity), on the spectrum
+// bounds of a CG-Lanczos estimate taken at initialize().  MatrixType is the library's own operator (handle() + coef()).
+class ChebyshevHandle { // what SolverCG needs of any PreconditionChebyshev instantiation
+public:
+  bp5_chebyshev *chebyshev_handle() const { return cheb; }
+  bp5_chebyshev_params parameters() const { return prm; }
+
+protected:
+  bp5_chebyshev *cheb = nullptr;
+  bp5_chebyshev_params prm{};
+};
+template <typename MatrixType, typename VectorType = double *, typename PreconditionerType = DiagonalMatrix>
+class PreconditionChebyshev : public ChebyshevHandle {
+public:
+  struct AdditionalData {
+    unsigned int degree = 1;               // degree 1 == Jacobi (D^-1 src / theta); degree-1 operator applications per vmult
+    double smoothing_range = 0.;           // > 1: lower bound = upper / smoothing_range; <= 1: min(0.9 upper, estimated minimum)
+    unsigned int eig_cg_n_iterations = 8;  // CG-Lanczos steps of the estimate
+    double max_eigenvalue = 0., min_eigenvalue = 0.; // both > 0: used as given, no estimate
+    PreconditionerType preconditioner;     // inverse diagonal
+    const uint64_t *start_ids_host = nullptr; // global DoF ids (bp5_mesh_view.global_ids_host): the same start vector on every rank count
+  };
+  PreconditionChebyshev() = default;
+  PreconditionChebyshev(const PreconditionChebyshev &) = delete;
+  PreconditionChebyshev &operator=(const PreconditionChebyshev &) = delete;
+  ~PreconditionChebyshev() { clear(); }
+  void initialize(const MatrixType &A, const AdditionalData &data = AdditionalData())
+  {
+    static_assert(internal::has_coef<MatrixType>::value, "PreconditionChebyshev (facade): the library's own operator (handle() + coef())");
+    clear();
+    prm = bp5_chebyshev_params{(int)data.degree, data.smoothing_range, (int)data.eig_cg_n_iterations, data.max_eigenvalue, data.min_eigenvalue,
+                               data.start_ids_host};
+    mf = A.handle();
+    check(bp5_chebyshev_create(mf, A.coef(), nullptr, nullptr, data.preconditioner.get_vector(), &prm, &cheb));
+  }
+  void clear()
+  {
+    if (cheb) bp5_chebyshev_destroy(cheb);
+    cheb = nullptr;
+  }
+  // dst = P src (dst's prior content ignored); enqueued on the operator's stream
+  void vmult(double *dst, const double *src) const { check(bp5_chebyshev_vmult(cheb, dst, const_cast<double *>(src))); }
+  // smoother: dst improved from its current value
+  void step(double *dst, const double *src) const { check(bp5_chebyshev_step(cheb, dst, const_cast<double *>(src))); }
+  template <typename V> auto vmult(V &dst, const V &src) const -> decltype((void)dst.get_values()) { vmult(dst.get_values(), src.get_values()); }
+  template <typename V> auto step(V &dst, const V &src) const -> decltype((void)dst.get_values()) { step(dst.get_values(), src.get_values()); }
+  struct Eigenvalues { double min_est, max_est, min_used, max_used; int cg_iterations; };
+  Eigenvalues estimated_eigenvalues() const
+  {
+    Eigenvalues e{};
+    check(bp5_chebyshev_eigenvalues(cheb, &e.min_est, &e.max_est, &e.min_used, &e.max_used, &e.cg_iterations));
+    return e;
+  }
+
+private:
+  bp5_mf *mf = nullptr;
+};
 // cg.solve(A, x, b, preconditioner), bp5/solver.h:25-30: the solvers use nothing of A but A.vmult(dst, src).
 //  * an operator that exposes  bp5_mf* handle()  and  const double* coef()  is the library's own Poisson operator: the
 //    whole solve runs inside bp5_cg_solve (fused operator kernels, dot products inside the block kernel where possible);
@@ -650,6 +708,23 @@ public:
       if (s != BP5_OK && !ctx.what.empty()) throw std::runtime_error("operator vmult failed inside the solver: " + ctx.what);
       finish(res, s);
     }
+  }
+  // cg.solve(A, x, b, PreconditionChebyshev): bp5_cg_solve_preconditioned with bp5_chebyshev_vmult (SolverCG only: SolverCGFullMerge's
+  // recurrence takes a diagonal, the library refuses it with BP5_ERR_INVALID).  check_every = 0: the library itself looks at the device's stop
+  // flag two iterations behind the enqueued work, so a converged solve stops applying A and P (include/bp5.h)
+  template <typename MatrixType>
+  void solve(const MatrixType &A, double *x, const double *b, const ChebyshevHandle &preconditioner)
+  {
+    static_assert(internal::has_coef<MatrixType>::value, "raw-pointer solve: the library's own operator");
+    bp5_cg_params prm{VARIANT, (int)control.max_steps, control.tolerance, 0, 0};
+    bp5_cg_result res{};
+    const int s = bp5_cg_solve_preconditioned(A.handle(), A.coef(), nullptr, nullptr, bp5_chebyshev_vmult, preconditioner.chebyshev_handle(), b, x, &prm, &res);
+    finish(res, s);
+  }
+  template <typename MatrixType, typename VectorType>
+  auto solve(const MatrixType &A, VectorType &x, const VectorType &b, const ChebyshevHandle &preconditioner) -> decltype((void)x.get_values())
+  {
+    solve(A, x.get_values(), static_cast<const double *>(b.get_values()), preconditioner);
   }
   bp5_cg_result result{};
 
