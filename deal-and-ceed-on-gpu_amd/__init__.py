@@ -9,9 +9,11 @@ from ._lib import (BP5Error, QUAD_GAUSS, QUAD_GLL, COEF_ONE, COEF_STEP64, CG_PLA
                    lib_path, shape_tables, tridiagonal_eigenvalues, HEADER_SYMBOLS)
 from .mesh import BrickMesh
 from .matrix_free import (MatrixFree, PoissonOperator, HelmholtzOperator, DiagonalMatrix, IterationNumberControl, SolverControl,
-                          SolverCG, SolverCGFullMerge, Communicator, Vector, PreconditionChebyshev)
+                          SolverCG, SolverCGFullMerge, Communicator, Vector, PreconditionChebyshev,
+                          MGTwoLevelTransfer, PreconditionMG, make_mg_hierarchy, mg_coarse_degrees)
 
 __all__ = ["BP5Error", "QUAD_GAUSS", "QUAD_GLL", "COEF_ONE", "COEF_STEP64", "CG_PLAIN", "CG_MERGED", "GEOM_MERGED6", "GEOM_AFFINE", "OP_POISSON", "OP_HELMHOLTZ", "build", "lib",
            "lib_path", "shape_tables", "HEADER_SYMBOLS", "BrickMesh", "MatrixFree", "PoissonOperator", "HelmholtzOperator",
            "DiagonalMatrix", "IterationNumberControl", "SolverControl", "SolverCG", "SolverCGFullMerge",
-           "Communicator", "Vector", "PreconditionChebyshev", "tridiagonal_eigenvalues"]
+           "Communicator", "Vector", "PreconditionChebyshev", "tridiagonal_eigenvalues",
+           "MGTwoLevelTransfer", "PreconditionMG", "make_mg_hierarchy", "mg_coarse_degrees"]

@@ -95,6 +95,16 @@ class ChebyshevParams(C.Structure):
                 ("min_eigenvalue", C.c_double), ("start_ids_host", C.c_void_p)]
 
 
+class MGParams(C.Structure):
+    _fields_ = [("smoother_degree", C.c_int), ("smoothing_range", C.c_double), ("eig_cg_n_iterations", C.c_int), ("coarse_degree", C.c_int),
+                ("coarse_range", C.c_double), ("coarse_eig_cg_n_iterations", C.c_int), ("start_ids_host", C.c_void_p)]
+
+
+class MGLevel(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("degree", C.c_int), ("n_owned", C.c_uint32), ("min_est", C.c_double), ("max_est", C.c_double),
+                ("min_used", C.c_double), ("max_used", C.c_double), ("cg_its", C.c_int), ("chebyshev_degree", C.c_int)]
+
+
 def lib():
     """Load libbp5.so; fails loudly if it has not been built (no fallback of any kind)."""
     global _LIB
@@ -179,6 +189,15 @@ def lib():
         "bp5_chebyshev_step": (i32, [vp, vp, vp]),
         "bp5_chebyshev_destroy": (i32, [vp]),
         "bp5_tridiagonal_eigenvalues": (i32, [i32, vp, vp, vp]),
+        "bp5_mg_transfer_create": (i32, [vp, vp, C.POINTER(vp)]),
+        "bp5_mg_transfer_prolongate_add": (i32, [vp, vp, vp]),
+        "bp5_mg_transfer_restrict_add": (i32, [vp, vp, vp]),
+        "bp5_mg_transfer_destroy": (i32, [vp]),
+        "bp5_mg_params_default": (None, [C.POINTER(MGParams)]),
+        "bp5_mg_create": (i32, [i32, vp, vp, vp, C.POINTER(MGParams), C.POINTER(vp)]),
+        "bp5_mg_vmult": (i32, [vp, vp, vp]),
+        "bp5_mg_level_info": (i32, [vp, i32, C.POINTER(MGLevel)]),
+        "bp5_mg_destroy": (i32, [vp]),
         "bp5_event_create": (i32, [C.POINTER(vp)]),
         "bp5_event_record": (i32, [vp, vp]),
         "bp5_event_elapsed_ms": (i32, [vp, vp, C.POINTER(f64)]),

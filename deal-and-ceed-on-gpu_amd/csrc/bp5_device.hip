@@ -2526,3 +2526,322 @@ extern "C" int bp5_chebyshev_destroy(bp5_chebyshev *c)
   delete c;
   return BP5_OK;
 }
+
+// ------------------------------------------------------------------------------------ p-multigrid transfer (MGTwoLevelTransfer)
+struct bp5_mg_transfer {
+  bp5_mf *fine = nullptr, *coarse = nullptr;
+  int pf = 0, pc = 0;
+  double *d_M = nullptr, *d_w = nullptr, *d_slots = nullptr;   // M [(pf+1)(pc+1)], fine weights [n_local fine], slots [n_cells (pc+1)^3]
+  uint32_t *d_cidx = nullptr, *d_wmask = nullptr;             // coarse indices per cell (MG_NO_DOF: Dirichlet), writer masks per cell
+  uint32_t *d_coff = nullptr, *d_cslot = nullptr;             // per coarse local DoF: its slots, ascending
+};
+
+// the instantiated degree pairs (pf -> max(1, pf / 2))
+template <int NF, int NC>
+static int mg_prolongate_launch(bp5_mg_transfer *t, double *dst, const double *src)
+{
+  using S = MgShape<NF, NC>;
+  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
+  if (grid) hipLaunchKernelGGL((mg_prolongate_kernel<NF, NC>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_cidx, t->fine->d_l2g, t->d_wmask,
+                              nc, src, dst);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+template <int NF, int NC>
+static int mg_restrict_launch(bp5_mg_transfer *t, const double *b, const double *tv)
+{
+  using S = MgShape<NF, NC>;
+  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
+  if (!grid) return BP5_OK;
+  if (tv) hipLaunchKernelGGL((mg_restrict_kernel<NF, NC, true>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->fine->d_l2g, nc, t->d_w, b, tv, t->d_slots);
+  else hipLaunchKernelGGL((mg_restrict_kernel<NF, NC, false>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->fine->d_l2g, nc, t->d_w, b, tv, t->d_slots);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+#define MG_DISPATCH(fn, t, ...)                                                                                    \
+  switch (t->pf) {                                                                                                 \
+  case 2: return fn<3, 2>(t, __VA_ARGS__);                                                                         \
+  case 3: return fn<4, 2>(t, __VA_ARGS__);                                                                         \
+  case 4: return fn<5, 3>(t, __VA_ARGS__);                                                                         \
+  case 5: return fn<6, 3>(t, __VA_ARGS__);                                                                         \
+  case 6: return fn<7, 4>(t, __VA_ARGS__);                                                                         \
+  case 7: return fn<8, 4>(t, __VA_ARGS__);                                                                         \
+  case 8: return fn<9, 5>(t, __VA_ARGS__);                                                                         \
+  default: return fail(BP5_ERR_INVALID, "multigrid transfer: fine degree must be 2..8");                           \
+  }
+static int mg_prolongate_dispatch(bp5_mg_transfer *t, double *dst, const double *src) { MG_DISPATCH(mg_prolongate_launch, t, dst, src); }
+static int mg_restrict_dispatch(bp5_mg_transfer *t, const double *b, const double *tv) { MG_DISPATCH(mg_restrict_launch, t, b, tv); }
+
+static int mg_combine(bp5_mg_transfer *t, double *dst, bool add)
+{
+  bp5_mf *c = t->coarse;
+  const uint32_t n = (uint32_t)c->n_local();
+  if (!n) return BP5_OK;
+  const uint32_t grid = std::min<uint32_t>((n + 255) / 256, 65536u);
+  if (add) hipLaunchKernelGGL(mg_combine_kernel<true>, dim3(grid), dim3(256), 0, c->stream, t->d_coff, t->d_cslot, t->d_slots, c->n_owned, n, dst);
+  else hipLaunchKernelGGL(mg_combine_kernel<false>, dim3(grid), dim3(256), 0, c->stream, t->d_coff, t->d_cslot, t->d_slots, c->n_owned, n, dst);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+static bool mg_distributed(const bp5_mf *mf) { return mf->comm && !mf->neighbors.empty(); }
+
+extern "C" int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_transfer **out)
+{
+  if (!fine || !coarse || !out) return fail(BP5_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (fine->degree < 2 || coarse->degree != std::max(1, fine->degree / 2))
+    return fail(BP5_ERR_INVALID, "multigrid transfer: need fine degree >= 2 and coarse degree max(1, fine degree / 2)");
+  if (fine->d_hang_mask || coarse->d_hang_mask || fine->has_hanging || coarse->has_hanging)
+    return fail(BP5_ERR_INVALID, "multigrid transfer: hanging-node meshes (constraint_mask) are not supported");
+  if (fine->n_cells != coarse->n_cells) return fail(BP5_ERR_INVALID, "multigrid transfer: the handles have different cells");
+  if (fine->comm != coarse->comm) return fail(BP5_ERR_INVALID, "multigrid transfer: the handles have different communicators");
+  if (fine->stream != coarse->stream || fine->device != coarse->device) return fail(BP5_ERR_INVALID, "multigrid transfer: the handles have different streams");
+  const int nf = fine->n, nc = coarse->n, f3 = fine->n3, c3 = coarse->n3;
+  const uint32_t ncell = fine->n_cells;
+  const size_t nlf = fine->n_local(), nlc = coarse->n_local();
+  // same cells: the corner DoFs of the cells correspond one to one
+  {
+    std::vector<uint32_t> f2c(nlf, MG_NO_DOF), c2f(nlc, MG_NO_DOF);
+    for (uint32_t c = 0; c < ncell; ++c)
+      for (int k = 0; k < 2; ++k)
+        for (int j = 0; j < 2; ++j)
+          for (int i = 0; i < 2; ++i) {
+            const uint32_t gf = fine->h_l2g[(size_t)c * f3 + i * (nf - 1) + nf * (j * (nf - 1) + nf * k * (nf - 1))];
+            const uint32_t gc = coarse->h_l2g[(size_t)c * c3 + i * (nc - 1) + nc * (j * (nc - 1) + nc * k * (nc - 1))];
+            if ((f2c[gf] != MG_NO_DOF && f2c[gf] != gc) || (c2f[gc] != MG_NO_DOF && c2f[gc] != gf))
+              return fail(BP5_ERR_INVALID, "multigrid transfer: the handles do not have the same cells (corner DoFs differ)");
+            f2c[gf] = gc;
+            c2f[gc] = gf;
+          }
+  }
+  HIP_TRY(hipSetDevice(fine->device));
+  std::unique_ptr<bp5_mg_transfer> t(new bp5_mg_transfer);
+  struct Free {
+    bp5_mg_transfer *t;
+    bool keep = false;
+    ~Free() { if (!keep) for (void *p : {(void *)t->d_M, (void *)t->d_w, (void *)t->d_slots, (void *)t->d_cidx, (void *)t->d_wmask, (void *)t->d_coff, (void *)t->d_cslot}) if (p) hipFree(p); }
+  } guard{t.get()};
+  t->fine = fine; t->coarse = coarse; t->pf = fine->degree; t->pc = coarse->degree;
+  // M from the product formula on the FE_Q nodes; end rows exact unit vectors
+  std::vector<double> xf(nf), xc(nc), M((size_t)nf * nc);
+  BP5_TRY(bp5_shape_tables(t->pf, BP5_QUAD_GAUSS, xf.data(), nullptr, nullptr, nullptr, nullptr));
+  BP5_TRY(bp5_shape_tables(t->pc, BP5_QUAD_GAUSS, xc.data(), nullptr, nullptr, nullptr, nullptr));
+  for (int a = 0; a < nf; ++a)
+    for (int b = 0; b < nc; ++b) {
+      double v = 1.0;
+      for (int m = 0; m < nc; ++m)
+        if (m != b) v *= (xf[a] - xc[m]) / (xc[b] - xc[m]);
+      M[(size_t)a * nc + b] = v;
+    }
+  for (int b = 0; b < nc; ++b) {
+    M[b] = b == 0 ? 1.0 : 0.0;
+    M[(size_t)(nf - 1) * nc + b] = b == nc - 1 ? 1.0 : 0.0;
+  }
+  BP5_TRY(upload(&t->d_M, M.data(), M.size()));
+  // coarse indices (Dirichlet DoFs: MG_NO_DOF) and the CSR of each coarse DoF's slots, in cell order
+  std::vector<uint32_t> cidx(coarse->h_l2g), coff(nlc + 1, 0u);
+  for (size_t s = 0; s < cidx.size(); ++s) {
+    if (coarse->h_constrained[cidx[s]]) cidx[s] = MG_NO_DOF;
+    else ++coff[cidx[s] + 1];
+  }
+  for (size_t g = 0; g < nlc; ++g) coff[g + 1] += coff[g];
+  std::vector<uint32_t> cslot(coff[nlc]), fill(coff.begin(), coff.end() - 1);
+  for (size_t s = 0; s < cidx.size(); ++s)
+    if (cidx[s] != MG_NO_DOF) cslot[fill[cidx[s]]++] = (uint32_t)s;
+  if ((uint64_t)ncell * c3 >= MG_NO_DOF) return fail(BP5_ERR_INVALID, "multigrid transfer: too many coarse cell entries for 32-bit slots");
+  BP5_TRY(upload(&t->d_cidx, cidx.data(), cidx.size()));
+  BP5_TRY(upload(&t->d_coff, coff.data(), coff.size()));
+  BP5_TRY(upload(&t->d_cslot, cslot.data(), cslot.size()));
+  // writer masks: the first cell (handle order) that holds an owned fine DoF writes it; the cell counts of every fine DoF
+  const int words = (f3 + 31) / 32;
+  std::vector<uint32_t> wmask((size_t)ncell * words, 0u);
+  std::vector<uint8_t> written(fine->n_owned, 0);
+  std::vector<double> count(std::max<size_t>(nlf, 1), 0.0);
+  for (uint32_t c = 0; c < ncell; ++c)
+    for (int r = 0; r < f3; ++r) {
+      const uint32_t g = fine->h_l2g[(size_t)c * f3 + r];
+      count[g] += 1.0;
+      if (g < fine->n_owned && !written[g]) {
+        written[g] = 1;
+        wmask[(size_t)c * words + r / 32] |= 1u << (r & 31);
+      }
+    }
+  for (uint32_t g = 0; g < fine->n_owned; ++g)
+    if (!written[g]) return fail(BP5_ERR_INVALID, "multigrid transfer: an owned fine DoF lies in none of the rank's cells");
+  BP5_TRY(upload(&t->d_wmask, wmask.data(), wmask.size()));
+  BP5_TRY(upload(&t->d_w, count.data(), count.size()));
+  if (mg_distributed(fine)) { // the counts of all ranks: ghost counts to their owners, the totals back to the ghosts
+    BP5_TRY(bp5_halo_scatter_add(fine, t->d_w));
+    BP5_TRY(bp5_halo_gather(fine, t->d_w));
+  }
+  if (nlf) {
+    hipLaunchKernelGGL(reciprocal_kernel, dim3((nlf + 255) / 256), dim3(256), 0, fine->stream, t->d_w, nlf);
+    KERNEL_CHECK();
+  }
+  HIP_TRY(hipMalloc((void **)&t->d_slots, std::max<size_t>((size_t)ncell * c3, 1) * sizeof(double)));
+  HIP_TRY(hipStreamSynchronize(fine->stream));
+  guard.keep = true;
+  *out = t.release();
+  return BP5_OK;
+}
+
+extern "C" int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst, double *src)
+{
+  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  HIP_TRY(hipSetDevice(t->fine->device));
+  if (mg_distributed(t->coarse)) BP5_TRY(bp5_halo_gather(t->coarse, src));
+  return mg_prolongate_dispatch(t, dst, src);
+}
+
+// dst_c (+)= P^T (w (.) (b - tv)), tv == NULL: P^T (w (.) b); with neighbours the fine ghosts of b (and tv) are gathered first and the
+// coarse ghost rows are sent to their owners
+static int mg_restrict(bp5_mg_transfer *t, double *dst, double *b, double *tv, bool add)
+{
+  HIP_TRY(hipSetDevice(t->fine->device));
+  if (mg_distributed(t->fine)) {
+    BP5_TRY(bp5_halo_gather(t->fine, b));
+    if (tv) BP5_TRY(bp5_halo_gather(t->fine, tv));
+  }
+  BP5_TRY(mg_restrict_dispatch(t, b, tv));
+  BP5_TRY(mg_combine(t, dst, add));
+  if (mg_distributed(t->coarse)) BP5_TRY(bp5_halo_scatter_add(t->coarse, dst));
+  return BP5_OK;
+}
+extern "C" int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst, double *src)
+{
+  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  return mg_restrict(t, dst, src, nullptr, true);
+}
+
+extern "C" int bp5_mg_transfer_destroy(bp5_mg_transfer *t)
+{
+  if (!t) return BP5_OK;
+  hipSetDevice(t->fine->device);
+  hipStreamSynchronize(t->fine->stream);
+  for (void *p : {(void *)t->d_M, (void *)t->d_w, (void *)t->d_slots, (void *)t->d_cidx, (void *)t->d_wmask, (void *)t->d_coff, (void *)t->d_cslot})
+    if (p) hipFree(p);
+  delete t;
+  return BP5_OK;
+}
+
+// ------------------------------------------------------------------------------------ PreconditionMG (V-cycle)
+struct bp5_mg {
+  int n_levels = 0;
+  std::vector<bp5_mf *> mf;
+  std::vector<const double *> coef;
+  std::vector<bp5_mg_transfer *> tr;
+  std::vector<bp5_chebyshev *> cheb;          // [l]: the smoother; [n_levels - 1]: the coarse solver
+  std::vector<double *> inv_diag, x, b, t;    // per level; x, b of levels >= 1 (level 0: the caller's dst, src); t of levels < n_levels - 1
+  std::vector<void *> allocs;
+};
+
+extern "C" void bp5_mg_params_default(bp5_mg_params *p)
+{
+  if (!p) return;
+  p->smoother_degree = 4;
+  p->smoothing_range = 20.0;
+  p->eig_cg_n_iterations = 10;
+  p->coarse_degree = 60;
+  p->coarse_range = 1000.0;
+  p->coarse_eig_cg_n_iterations = 30;
+  p->start_ids_host = nullptr;
+}
+
+extern "C" int bp5_mg_destroy(bp5_mg *mg)
+{
+  if (!mg) return BP5_OK;
+  if (!mg->mf.empty()) {
+    hipSetDevice(mg->mf[0]->device);
+    hipStreamSynchronize(mg->mf[0]->stream);
+  }
+  for (bp5_chebyshev *c : mg->cheb) bp5_chebyshev_destroy(c);
+  for (void *p : mg->allocs) hipFree(p);
+  delete mg;
+  return BP5_OK;
+}
+
+extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, bp5_mg_transfer *const *transfers, const bp5_mg_params *prm,
+                             bp5_mg **out)
+{
+  if (n_levels < 1 || !mfs || !coefs || !prm || !out || (n_levels > 1 && !transfers)) return fail(BP5_ERR_INVALID, "null argument or n_levels < 1");
+  *out = nullptr;
+  if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return fail(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
+  for (int l = 0; l < n_levels; ++l) {
+    if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
+    if (mfs[l]->stream != mfs[0]->stream) return fail(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
+  }
+  for (int l = 0; l + 1 < n_levels; ++l)
+    if (!transfers[l] || transfers[l]->fine != mfs[l] || transfers[l]->coarse != mfs[l + 1])
+      return fail(BP5_ERR_INVALID, "multigrid: transfers[l] must connect mfs[l] (fine) and mfs[l + 1] (coarse)");
+  HIP_TRY(hipSetDevice(mfs[0]->device));
+  std::unique_ptr<bp5_mg, int (*)(bp5_mg *)> mg(new bp5_mg, bp5_mg_destroy);
+  mg->n_levels = n_levels;
+  mg->mf.assign(mfs, mfs + n_levels);
+  mg->coef.assign(coefs, coefs + n_levels);
+  mg->tr.assign(transfers, transfers + (n_levels - 1));
+  mg->inv_diag.assign(n_levels, nullptr);
+  mg->x.assign(n_levels, nullptr);
+  mg->b.assign(n_levels, nullptr);
+  mg->t.assign(n_levels, nullptr);
+  auto alloc = [&](double **p, size_t n) -> int {
+    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 2) * sizeof(double)));
+    mg->allocs.push_back(*p);
+    HIP_TRY(hipMemsetAsync(*p, 0, std::max<size_t>(n, 2) * sizeof(double), mfs[0]->stream));
+    return BP5_OK;
+  };
+  for (int l = 0; l < n_levels; ++l) {
+    bp5_mf *m = mfs[l];
+    const size_t nl = m->n_local();
+    BP5_TRY(alloc(&mg->inv_diag[l], nl));
+    if (l > 0) { BP5_TRY(alloc(&mg->x[l], nl)); BP5_TRY(alloc(&mg->b[l], nl)); }
+    if (l + 1 < n_levels) BP5_TRY(alloc(&mg->t[l], nl));
+    BP5_TRY(bp5_compute_diagonal(m, coefs[l], mg->inv_diag[l], 1));
+    const bool coarsest = l + 1 == n_levels;
+    bp5_chebyshev_params cp{};
+    cp.degree = coarsest ? prm->coarse_degree : prm->smoother_degree;
+    cp.smoothing_range = coarsest ? prm->coarse_range : prm->smoothing_range;
+    cp.eig_cg_n_iterations = coarsest ? prm->coarse_eig_cg_n_iterations : prm->eig_cg_n_iterations;
+    cp.start_ids_host = prm->start_ids_host ? prm->start_ids_host[l] : nullptr;
+    bp5_chebyshev *c = nullptr;
+    BP5_TRY(bp5_chebyshev_create(m, coefs[l], nullptr, nullptr, mg->inv_diag[l], &cp, &c));
+    mg->cheb.push_back(c);
+  }
+  HIP_TRY(hipStreamSynchronize(mfs[0]->stream));
+  *out = mg.release();
+  return BP5_OK;
+}
+
+static int mg_level(bp5_mg *mg, int l, double *x, double *b)
+{
+  if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
+  bp5_mf *mf = mg->mf[l];
+  BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                      // pre-smoothing from zero
+  if (mg_distributed(mf)) BP5_TRY(bp5_apply_distributed(mf, mg->coef[l], x, mg->t[l], 1));
+  else BP5_TRY(bp5_apply(mf, mg->coef[l], x, mg->t[l], 1));             // t = A x
+  BP5_TRY(mg_restrict(mg->tr[l], mg->b[l + 1], b, mg->t[l], false));   // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
+  BP5_TRY(mg_level(mg, l + 1, mg->x[l + 1], mg->b[l + 1]));
+  BP5_TRY(bp5_mg_transfer_prolongate_add(mg->tr[l], x, mg->x[l + 1]));  // x += P x_c
+  return bp5_chebyshev_step(mg->cheb[l], x, b);                        // post-smoothing
+}
+
+extern "C" int bp5_mg_vmult(void *mgv, double *dst, double *src)
+{
+  bp5_mg *mg = static_cast<bp5_mg *>(mgv);
+  if (!mg || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  if (dst == src) return fail(BP5_ERR_INVALID, "multigrid vmult: dst and src must differ");
+  HIP_TRY(hipSetDevice(mg->mf[0]->device));
+  return mg_level(mg, 0, dst, src);
+}
+
+extern "C" int bp5_mg_level_info(const bp5_mg *mg, int level, bp5_mg_level *o)
+{
+  if (!mg || !o) return fail(BP5_ERR_INVALID, "null argument");
+  if (level < 0 || level >= mg->n_levels) return fail(BP5_ERR_INVALID, "multigrid: level out of range");
+  memset(o, 0, sizeof(*o));
+  o->n_levels = mg->n_levels;
+  o->degree = mg->mf[level]->degree;
+  o->n_owned = mg->mf[level]->n_owned;
+  const bp5_chebyshev *c = mg->cheb[level];
+  o->chebyshev_degree = c->degree;
+  return bp5_chebyshev_eigenvalues(c, &o->min_est, &o->max_est, &o->min_used, &o->max_used, &o->cg_its);
+}

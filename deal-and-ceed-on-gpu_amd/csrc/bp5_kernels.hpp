@@ -3704,6 +3704,152 @@ __global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const
   }
 }
 
+// ---- p-multigrid transfer between FE_Q(pf) and FE_Q(pc) on the same cells (bp5_mg_transfer_*; deal.II MGTwoLevelTransfer).
+// M[a][b] = phi_b^pc(xi_a^pf), (NF = pf+1) x (NC = pc+1), row-major.  One workgroup takes CPB cells; the tensor product M x M x M is
+// applied direction by direction through LDS (sum factorisation), one output entry per thread and stage.  Cell-local index
+// i + n (j + n k), x fastest, as local_to_global.
+template <int NF, int NC>
+struct MgShape {
+  static constexpr int F3 = NF * NF * NF, C3 = NC * NC * NC;
+  static constexpr int CPB = F3 >= 256 ? 1 : 256 / F3;  // cells per workgroup
+  static constexpr int WORDS = (F3 + 31) / 32;          // writer-mask words per cell
+  static constexpr int LDS = F3 + NC * NF * NF + NC * NC * NF; // doubles per cell (both directions fit)
+};
+constexpr uint32_t MG_NO_DOF = 0xffffffffu; // a coarse Dirichlet DoF in the transfer's coarse index list: its value is 0
+
+// x_f += P e_c: the cell's coarse values (Dirichlet as 0), interpolated to its fine nodes; a fine DoF is written by the one cell whose
+// writer-mask bit is set (the first cell in handle order that holds it; owned DoFs only): plain read-modify-write, no atomics
+template <int NF, int NC>
+__global__ void __launch_bounds__(256) mg_prolongate_kernel(const double *__restrict__ M, const uint32_t *__restrict__ cidx,
+                                                            const uint32_t *__restrict__ fidx, const uint32_t *__restrict__ wmask,
+                                                            uint32_t n_cells, const double *__restrict__ src_c, double *__restrict__ dst_f)
+{
+  using S = MgShape<NF, NC>;
+  constexpr int F3 = S::F3, C3 = S::C3, CPB = S::CPB;
+  __shared__ double sM[NF * NC];
+  __shared__ double buf[CPB][S::LDS];
+  const int t = threadIdx.x;
+  const uint32_t c0 = blockIdx.x * CPB;
+  for (int i = t; i < NF * NC; i += 256) sM[i] = M[i];
+  for (int e = t; e < CPB * C3; e += 256) {
+    const int cl = e / C3, r = e % C3;
+    const uint32_t c = c0 + cl;
+    double v = 0.0;
+    if (c < n_cells) {
+      const uint32_t g = cidx[(size_t)c * C3 + r];
+      v = g == MG_NO_DOF ? 0.0 : src_c[g];
+    }
+    buf[cl][r] = v;
+  }
+  __syncthreads();
+  // x: s1[k][j][a] = sum_b M[a][b] s0[k][j][b]            (k, j < NC)
+  for (int e = t; e < CPB * NC * NC * NF; e += 256) {
+    const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), a = r % NF, kj = r / NF;
+    const double *s0 = buf[cl] + kj * NC;
+    double acc = 0.0;
+#pragma unroll
+    for (int b = 0; b < NC; ++b) acc += sM[a * NC + b] * s0[b];
+    buf[cl][C3 + r] = acc;
+  }
+  __syncthreads();
+  // y: s2[k][b][a] = sum_j M[b][j] s1[k][j][a]             (k < NC)
+  for (int e = t; e < CPB * NC * NF * NF; e += 256) {
+    const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), a = r % NF, b = (r / NF) % NF, k = r / (NF * NF);
+    const double *s1 = buf[cl] + C3;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) acc += sM[b * NC + j] * s1[(k * NC + j) * NF + a];
+    buf[cl][C3 + NC * NC * NF + r] = acc;
+  }
+  __syncthreads();
+  // z and write-out: x_f[l2g] += sum_k M[kk][k] s2[k][b][a] where this cell is the DoF's writer
+  for (int e = t; e < CPB * F3; e += 256) {
+    const int cl = e / F3, r = e % F3, ab = r % (NF * NF), kk = r / (NF * NF);
+    const uint32_t c = c0 + cl;
+    if (c >= n_cells || !((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) continue;
+    const double *s2 = buf[cl] + C3 + NC * NC * NF;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc += sM[kk * NC + k] * s2[k * NF * NF + ab];
+    const uint32_t g = fidx[(size_t)c * F3 + r];
+    dst_f[g] += acc;
+  }
+}
+
+// the cell's share of P^T v:  slots[c][i] = (M^T x M^T x M^T)(w (b - t))|_cell, i < NC^3   (RESIDUAL false: w b, t not read).  w = 1 /
+// (number of cells that hold the DoF, all ranks): the slots of a coarse DoF summed give exactly (P^T v)_c.  No atomics: mg_combine_kernel
+// sums the slots in ascending order
+template <int NF, int NC, bool RESIDUAL>
+__global__ void __launch_bounds__(256) mg_restrict_kernel(const double *__restrict__ M, const uint32_t *__restrict__ fidx, uint32_t n_cells,
+                                                          const double *__restrict__ w, const double *__restrict__ b,
+                                                          const double *__restrict__ tv, double *__restrict__ slots)
+{
+  using S = MgShape<NF, NC>;
+  constexpr int F3 = S::F3, C3 = S::C3, CPB = S::CPB;
+  __shared__ double sM[NF * NC];
+  __shared__ double buf[CPB][S::LDS];
+  const int t = threadIdx.x;
+  const uint32_t c0 = blockIdx.x * CPB;
+  for (int i = t; i < NF * NC; i += 256) sM[i] = M[i];
+  for (int e = t; e < CPB * F3; e += 256) {
+    const int cl = e / F3, r = e % F3;
+    const uint32_t c = c0 + cl;
+    double v = 0.0;
+    if (c < n_cells) {
+      const uint32_t g = fidx[(size_t)c * F3 + r];
+      v = w[g] * (RESIDUAL ? b[g] - tv[g] : b[g]);
+    }
+    buf[cl][r] = v;
+  }
+  __syncthreads();
+  // z: s1[k][j][i] = sum_kk M[kk][k] s0[kk][j][i]          (k < NC)
+  for (int e = t; e < CPB * NC * NF * NF; e += 256) {
+    const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), ji = r % (NF * NF), k = r / (NF * NF);
+    const double *s0 = buf[cl];
+    double acc = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < NF; ++kk) acc += sM[kk * NC + k] * s0[kk * NF * NF + ji];
+    buf[cl][F3 + r] = acc;
+  }
+  __syncthreads();
+  // y: s2[k][j][i] = sum_jj M[jj][j] s1[k][jj][i]          (k, j < NC)
+  for (int e = t; e < CPB * NC * NC * NF; e += 256) {
+    const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), i = r % NF, j = (r / NF) % NC, k = r / (NF * NC);
+    const double *s1 = buf[cl] + F3;
+    double acc = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < NF; ++jj) acc += sM[jj * NC + j] * s1[(k * NF + jj) * NF + i];
+    buf[cl][F3 + NC * NF * NF + r] = acc;
+  }
+  __syncthreads();
+  // x: slot = sum_ii M[ii][i] s2[k][j][ii]
+  for (int e = t; e < CPB * C3; e += 256) {
+    const int cl = e / C3, r = e % C3, i = r % NC, kj = r / NC;
+    const uint32_t c = c0 + cl;
+    if (c >= n_cells) continue;
+    const double *s2 = buf[cl] + F3 + NC * NF * NF;
+    double acc = 0.0;
+#pragma unroll
+    for (int ii = 0; ii < NF; ++ii) acc += sM[ii * NC + i] * s2[kj * NF + ii];
+    slots[(size_t)c * C3 + r] = acc;
+  }
+}
+
+// coarse DoF g: s = sum of its slots in ascending slot (= cell) order (Dirichlet DoFs have none: s = 0); ADD: owned rows dst += s, else
+// and on ghost rows dst = s (the ghost rows then travel to their owners by the scatter-add)
+template <bool ADD>
+__global__ void __launch_bounds__(256) mg_combine_kernel(const uint32_t *__restrict__ off, const uint32_t *__restrict__ slot_of,
+                                                         const double *__restrict__ slots, uint32_t n_owned, uint32_t n, double *__restrict__ dst)
+{
+  const uint32_t stride = gridDim.x * 256;
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n; g += stride) {
+    double s = 0.0;
+    for (uint32_t q = off[g]; q < off[g + 1]; ++q) s += slots[slot_of[q]];
+    if (ADD && g < n_owned) dst[g] += s;
+    else dst[g] = s;
+  }
+}
+
 // ---- self-check of the in-launch stream wait-value schedules (bp5_device.hip: halo_streams).  The producer counts itself in exactly like
 // apply_block_kernel's signal_part_done and then stays alive until the consumer -- enqueued on the waiting stream behind
 // hipStreamWaitValue64 -- has run, or 2 ms have passed: *result = 1 says the wait was released WHILE the producing kernel was running

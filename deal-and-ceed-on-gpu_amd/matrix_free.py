@@ -8,6 +8,8 @@ C ABI (include/bp5.h).  Names, argument meaning and error behaviour follow the r
   SolverCG ............... deal.II SolverCG, call site bp5/step-64.cu:446-453
   SolverCGFullMerge ...... bp5/solver.h:16-30,343-542 (x-update schedule fixed)
   PreconditionChebyshev .. deal.II PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (Chebyshev-Jacobi, include/bp5.h)
+  MGTwoLevelTransfer ..... deal.II MGTwoLevelTransfer (p-transfer between FE_Q(p) and FE_Q(p/2) on the same cells)
+  PreconditionMG ......... deal.II PreconditionMG / Multigrid: V-cycle with Chebyshev smoothers (step-37), p-coarsening
 
 Vectors are torch float64 CUDA tensors of n_owned + n_ghost entries (torch is plumbing for
 device memory / streams / the process group only -- no torch op is on the hot path)."""
@@ -541,6 +543,144 @@ class PreconditionChebyshev:
             pass
 
 
+class MGTwoLevelTransfer:
+    """== MGTwoLevelTransfer (deal.II matrix-free global-coarsening transfer) between two operators of degrees pf >= 2 and
+    pc = max(1, pf // 2) on the same cells (bp5_mg_transfer_*, include/bp5.h).  prolongate_and_add: dst_f += P src_c;
+    restrict_and_add: dst_c += P^T src_f (Dirichlet rows of dst_c unchanged).  Vectors: owned + ghost storage of their operator."""
+
+    def __init__(self, fine_op, coarse_op):
+        self._h = None
+        self.fine, self.coarse = fine_op, coarse_op
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp5_mg_transfer_create(fine_op.mf_data.handle, coarse_op.mf_data.handle, C.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, "MGTwoLevelTransfer has been cleared")
+        return self._h
+
+    def prolongate_and_add(self, dst, src):
+        _lib.check(_lib.lib().bp5_mg_transfer_prolongate_add(self.handle, _ptr(_vals(dst), self.fine.mf_data.n_local),
+                                                             _ptr(_vals(src), self.coarse.mf_data.n_local)))
+
+    def restrict_and_add(self, dst, src):
+        _lib.check(_lib.lib().bp5_mg_transfer_restrict_add(self.handle, _ptr(_vals(dst), self.coarse.mf_data.n_local),
+                                                           _ptr(_vals(src), self.fine.mf_data.n_local)))
+
+    def clear(self):
+        if self._h:
+            _lib.lib().bp5_mg_transfer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
+def mg_coarse_degrees(degree):
+    """The p-multigrid hierarchy p, p // 2, ..., 1 (fine to coarse)."""
+    degrees = [int(degree)]
+    while degrees[-1] > 1:
+        degrees.append(max(1, degrees[-1] // 2))
+    return degrees
+
+
+def make_mg_hierarchy(fine_op):
+    """The operators of the p-multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same cells, block order and
+    numbering scheme, coefficient, quadrature, device, stream and communicator at degrees p // 2, ..., 1.  Returns [fine_op, ...]."""
+    from .mesh import BrickMesh
+    mf, m = fine_op.mf_data, fine_op.mf_data.mesh
+    ops = [fine_op]
+    stream = _torch().cuda.current_stream(mf.device).cuda_stream
+    for p in mg_coarse_degrees(m.degree)[1:]:
+        mesh = BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
+                         dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)
+        ops.append(type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream))
+    return ops
+
+
+class PreconditionMG:
+    """== PreconditionMG<dim, Vector, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a
+    Chebyshev coarse solver (step-37), coarsening in the polynomial degree (bp5_mg_*, include/bp5.h).  operators: PoissonOperators from
+    fine to coarse on the same cells, degrees p, max(1, p // 2), ... (make_mg_hierarchy builds them).  vmult is one symmetric V-cycle,
+    enqueued on the operators' stream without a host synchronisation; SolverCG.solve passes it natively (bp5_mg_vmult)."""
+
+    class AdditionalData:
+        def __init__(self, smoother_degree=4, smoothing_range=20.0, eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0,
+                     coarse_eig_cg_n_iterations=30):
+            self.smoother_degree, self.smoothing_range, self.eig_cg_n_iterations = int(smoother_degree), float(smoothing_range), int(eig_cg_n_iterations)
+            self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
+            self.coarse_eig_cg_n_iterations = int(coarse_eig_cg_n_iterations)
+
+    def __init__(self, operators, data=None):
+        self._h = None
+        self.transfers = []
+        self.initialize(operators, data)
+
+    def initialize(self, operators, data=None):
+        self.clear()
+        data = data if data is not None else PreconditionMG.AdditionalData()
+        ops = list(operators)
+        if not ops or not all(isinstance(o, PoissonOperator) for o in ops):
+            raise BP5Error(1, "PreconditionMG needs a list of PoissonOperators, fine to coarse")
+        self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
+        self.transfers = [MGTwoLevelTransfer(f, c) for f, c in zip(ops[:-1], ops[1:])]
+        ids = []
+        for o in ops:
+            g = getattr(o.mf_data.mesh, "global_ids", None)
+            ids.append(np.ascontiguousarray(g[:o.mf_data.n_owned], dtype=np.uint64) if g is not None else None)
+        id_ptrs = (C.c_void_p * len(ops))(*[a.ctypes.data if a is not None else None for a in ids])
+        prm = _lib.MGParams(data.smoother_degree, data.smoothing_range, data.eig_cg_n_iterations, data.coarse_degree, data.coarse_range,
+                            data.coarse_eig_cg_n_iterations, C.cast(id_ptrs, C.c_void_p))
+        n = len(ops)
+        mfs = (C.c_void_p * n)(*[o.mf_data.handle.value for o in ops])
+        coefs = (C.c_void_p * n)(*[o.coef.data_ptr() if o.coef is not None else None for o in ops])
+        trs = (C.c_void_p * max(n - 1, 1))(*[t.handle.value for t in self.transfers])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp5_mg_create(n, mfs, coefs, trs, C.byref(prm), C.byref(h)))
+        self._h = h
+        return self
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, "PreconditionMG has been cleared")
+        return self._h
+
+    def vmult(self, dst, src):
+        """dst = V src: one V-cycle (dst's prior content ignored); enqueued on the operators' stream."""
+        n = self.mf_data.n_local
+        _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(_vals(dst), n), _ptr(_vals(src), n)))
+
+    def level_info(self):
+        """Per level, fine to coarse: dict(degree, n_owned, n_global_dofs, min_est, max_est, min_used, max_used, cg_its, chebyshev_degree)."""
+        out = []
+        for lev, o in enumerate(self.operators):
+            v = _lib.MGLevel()
+            _lib.check(_lib.lib().bp5_mg_level_info(self.handle, lev, C.byref(v)))
+            out.append(dict(degree=v.degree, n_owned=v.n_owned, n_global_dofs=int(o.mf_data.mesh.n_global_dofs), min_est=v.min_est,
+                            max_est=v.max_est, min_used=v.min_used, max_used=v.max_used, cg_its=v.cg_its, chebyshev_degree=v.chebyshev_degree))
+        return out
+
+    def clear(self):
+        if self._h:
+            _lib.lib().bp5_mg_destroy(self._h)
+            self._h = None
+        for t in self.transfers:
+            t.clear()
+        self.transfers = []
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
 class _SolverBase:
     variant = CG_PLAIN
 
@@ -552,7 +692,7 @@ class _SolverBase:
         A PoissonOperator runs entirely inside bp5_cg_solve; any other object with `mf_data` (vector layout, stream) and
         `vmult(dst, src)` is solved through bp5_cg_solve_operator -- the solvers need nothing of A but vmult
         (bp5/solver.h:25-30,377,475).  The preconditioner: None / DiagonalMatrix (the solvers' diag), a PreconditionChebyshev (native:
-        bp5_cg_solve_preconditioned with bp5_chebyshev_vmult), or any other object with vmult(dst, src) (through a callback; SolverCG only)."""
+        bp5_cg_solve_preconditioned with bp5_chebyshev_vmult), a PreconditionMG (native: bp5_mg_vmult), or any other object with vmult(dst, src) (through a callback; SolverCG only)."""
         mf = A.mf_data
         x, b = _vals(x), _vals(b)
         general = preconditioner is not None and not hasattr(preconditioner, "get_vector")
@@ -568,6 +708,8 @@ class _SolverBase:
         if general:
             if isinstance(preconditioner, PreconditionChebyshev):
                 pfn, pctx = C.cast(_lib.lib().bp5_chebyshev_vmult, C.c_void_p), preconditioner.handle
+            elif isinstance(preconditioner, PreconditionMG):
+                pfn, pctx = C.cast(_lib.lib().bp5_mg_vmult, C.c_void_p), preconditioner.handle
             else:
                 pcb = _callback(preconditioner, mf, failure)
                 pfn, pctx = C.cast(pcb, C.c_void_p), None

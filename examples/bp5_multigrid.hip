@@ -1,0 +1,109 @@
+// Multigrid-preconditioned CG written like the solve of deal.II's step-37 (Poisson with step-64's kappa), against the deal.II-shaped
+// facade (include/bp5_dealii_facade.hpp): the operators of the levels p, p / 2, ..., 1 on the same cells, PreconditionMG (V-cycle,
+// Chebyshev smoothers, Chebyshev coarse solver), SolverCG.  Prints the iteration count, the levels and the solution's norm.
+//
+//   bp5_multigrid <p> <nx> <ny> <nz> <deform> <rel_tol> [coefficient]
+//     coefficient: 0 = kappa 1, 1 = step-64's kappa (default)
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include "bp5_dealii_facade.hpp"
+
+using namespace bp5::dealii_facade;
+
+// the library's own Poisson operator on a brick mesh: handle() + coef() make the facade's solvers and PreconditionMG run it natively
+class LaplaceOperator {
+public:
+  LaplaceOperator(const bp5_mesh_view &mv, int coefficient)
+  {
+    bp5_mf_desc d{};
+    d.dim = 3; d.degree = mv.degree; d.quadrature = BP5_QUAD_GAUSS; d.coefficient = coefficient;
+    d.n_cells = mv.n_cells; d.n_interior_cells = mv.n_interior_cells; d.n_owned = mv.n_owned; d.n_ghost = mv.n_ghost;
+    d.local_to_global_host = mv.local_to_global_host; d.node_coords_host = mv.node_coords_host;
+    d.constrained_host = mv.constrained_host; d.n_constrained = mv.n_constrained;
+    d.n_cell_blocks = mv.n_cell_blocks; d.cell_block_offsets_host = mv.cell_block_offsets_host;
+    mf_data.reinit(d);
+    n_owned = mv.n_owned;
+    size_t nc;
+    check(bp5_mf_coef_size(mf_data.handle(), &nc));
+    check(bp5_vec_alloc(nc, &coef_));
+    check(bp5_mf_compute_merged_metric(mf_data.handle(), coef_));
+  }
+  ~LaplaceOperator() { bp5_vec_free(coef_); }
+  void vmult(double *dst, const double *src) const { check(bp5_apply(mf_data.handle(), coef_, src, dst, 1)); }
+  void initialize_dof_vector(double **v) const { mf_data.initialize_dof_vector(v); }
+  // == MatrixFreeOperators::Base::compute_diagonal + inverse (step-37: the Jacobi part of the Chebyshev smoother)
+  void compute_diagonal(double *diag, bool invert) const { check(bp5_compute_diagonal(mf_data.handle(), coef_, diag, invert ? 1 : 0)); }
+  bp5_mf *handle() const { return mf_data.handle(); }
+  const double *coef() const { return coef_; }
+  size_t n_owned = 0;
+
+private:
+  CUDAWrappers::MatrixFree<3, double> mf_data;
+  double *coef_ = nullptr;
+};
+
+int main(int argc, char **argv)
+{
+  if (argc < 7) {
+    fprintf(stderr, "usage: %s p nx ny nz deform rel_tol [coefficient]\n", argv[0]);
+    return 2;
+  }
+  try {
+    const int coefficient = argc > 7 ? atoi(argv[7]) : BP5_COEF_STEP64;
+    std::vector<bp5_mesh *> meshes;
+    std::vector<bp5_mesh_view> views;
+    for (int p = atoi(argv[1]);; p = p / 2 > 1 ? p / 2 : 1) { // the hierarchy p, p / 2, ..., 1 on the same cells
+      bp5_mesh_desc md{};
+      md.degree = p;
+      for (int d = 0; d < 3; ++d) md.cells[d] = (uint32_t)atoi(argv[2 + d]);
+      md.h = 1.0; md.deform_amp = atof(argv[5]); md.n_ranks = 1;
+      bp5_mesh *mesh;
+      check(bp5_mesh_create_brick(&md, &mesh));
+      bp5_mesh_view mv;
+      check(bp5_mesh_view_get(mesh, &mv));
+      meshes.push_back(mesh);
+      views.push_back(mv);
+      if (p == 1) break;
+    }
+    {
+      std::vector<std::unique_ptr<LaplaceOperator>> ops;
+      std::vector<const LaplaceOperator *> levels;
+      PreconditionMG::AdditionalData data;
+      for (const bp5_mesh_view &mv : views) {
+        ops.emplace_back(new LaplaceOperator(mv, coefficient));
+        levels.push_back(ops.back().get());
+        data.start_ids_host.push_back(mv.global_ids_host);
+      }
+      const LaplaceOperator &A = *ops[0];
+      double *b, *x;
+      A.initialize_dof_vector(&b); A.initialize_dof_vector(&x);
+      check(bp5_assemble_rhs(A.handle(), b));
+      PreconditionMG P;
+      P.initialize(levels, data);
+      double bnorm;
+      check(bp5_vec_l2_norm(A.handle(), b, A.n_owned, &bnorm));
+      SolverControl control(1000, atof(argv[6]) * bnorm);
+      SolverCG cg(control);
+      cg.solve(A, x, b, P);
+      double xnorm;
+      check(bp5_vec_l2_norm(A.handle(), x, A.n_owned, &xnorm));
+      printf("dofs %llu\niterations %u\nresidual %.6e\n", (unsigned long long)views[0].n_global_dofs, control.last_step(), control.last_value());
+      for (int l = 0; l < (int)levels.size(); ++l) {
+        const bp5_mg_level o = P.level_info(l);
+        printf("level%d %d %u %.12e %.12e\n", l, o.degree, o.n_owned, o.min_used, o.max_used);
+      }
+      printf("solution_norm %.15e\nsolve_ms %.3f\n", xnorm, cg.result.solve_ms);
+      P.clear();
+      bp5_vec_free(b); bp5_vec_free(x);
+    }
+    for (bp5_mesh *m : meshes) bp5_mesh_destroy(m);
+  } catch (const std::exception &e) {
+    fprintf(stderr, "error: %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}

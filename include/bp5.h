@@ -509,6 +509,64 @@ int bp5_chebyshev_destroy(bp5_chebyshev *c);
  * (no LAPACK, no GPU) */
 int bp5_tridiagonal_eigenvalues(int n, const double *diag, const double *offdiag, double *eig_ascending_host);
 
+/* ------------------------------------------------------------------------------------------ */
+/* p-multigrid: deal.II MGTwoLevelTransfer (matrix-free global-coarsening transfer), Multigrid and PreconditionMG with Chebyshev
+ * smoothers (step-37), coarsening in the polynomial degree on the same cells.
+ *
+ * Transfer between a fine handle of degree pf >= 2 and a coarse handle of degree pc = max(1, pf / 2) on the SAME cells in the same
+ * order (two bp5_mesh_create_brick meshes that differ only in degree; checked through the cells' corner DoFs), the same communicator
+ * and stream.  M[a][b] = phi_b^pc(xi_a^pf) (FE_Q nodes of bp5_shape_tables; its end rows exact unit vectors); P = M x M x M cell by cell,
+ * with the coarse Dirichlet DoFs taken as 0:
+ *   prolongate_add  dst_f += P src_c: each cell interpolates its coarse values to its fine nodes; every owned fine DoF is written by ONE
+ *                   cell (the first in handle order that holds it): no atomics, no race.  With neighbours the coarse ghosts are gathered
+ *                   first (src_c's ghost range is written); dst_f's ghost range is not touched.
+ *   restrict_add    dst_c += P^T src_f, Dirichlet rows of dst_c unchanged: each cell forms M^T x M^T x M^T of w (.) src_f, w = 1 / (number
+ *                   of cells that hold the DoF, counted over all ranks at create), into a slot array; one combine pass sums the slots of
+ *                   each coarse DoF in cell order (bitwise reproducible).  With neighbours: src_f's ghosts gathered first, dst_c's ghost
+ *                   range sent to its owners and added (then zeroed).
+ * Conforming meshes only (a handle with hanging-node masks: BP5_ERR_INVALID).  Vectors: owned + ghost storage of their handle.
+ * Create is synchronous; the applications enqueue on the handles' stream. */
+typedef struct bp5_mg_transfer bp5_mg_transfer;
+int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_transfer **out);
+int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst_fine, double *src_coarse);
+int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst_coarse, double *src_fine);
+int bp5_mg_transfer_destroy(bp5_mg_transfer *t);
+
+/* PreconditionMG: one symmetric V-cycle per vmult.  Levels fine (0) to coarse (n_levels - 1), mfs[l] / coefs[l] the level's handle and
+ * merged metric, transfers[l] between level l and l + 1 (n_levels - 1 of them).  At create every level gets its inverse diagonal
+ * (bp5_compute_diagonal) and a Chebyshev-Jacobi polynomial (bp5_chebyshev_create: smoother_degree on [max_used / smoothing_range,
+ * max_used]; the coarsest level: coarse_degree on [max_used / coarse_range, max_used], a fixed polynomial, so the cycle is a fixed
+ * symmetric linear operator as CG needs).  vmult (dst = V src, dst's prior content ignored), level l from x_l = 0:
+ *   l = coarsest:  x_l = coarse polynomial (src_l)
+ *   else           x_l = smoother vmult (src_l)                       pre-smoothing from zero
+ *                  src_{l+1} = P^T (w (.) (src_l - A_l x_l)), Dirichlet rows 0   (fused: the fine residual is never stored)
+ *                  x_{l+1} = V_{l+1}(src_{l+1}); x_l += P x_{l+1}; x_l = smoother step (x_l, src_l)   post-smoothing
+ * Everything is enqueued on the fine handle's stream (all handles share it): no host synchronisation and no all-reduce; the halo
+ * exchanges of the levels run one after the other on the one communicator. */
+typedef struct {
+  int smoother_degree;         /* default 4                                                                                  */
+  double smoothing_range;      /* default 20                                                                                 */
+  int eig_cg_n_iterations;     /* CG-Lanczos steps of each smoother's estimate (default 10)                                  */
+  int coarse_degree;           /* Chebyshev degree of the coarse solver (default 60)                                         */
+  double coarse_range;         /* its max_used / min_used (default 1000)                                                     */
+  int coarse_eig_cg_n_iterations; /* CG-Lanczos steps of the coarse estimate (default 30)                                   */
+  const uint64_t *const *start_ids_host; /* [n_levels] per level the global DoF ids of the owned DoFs (bp5_chebyshev_params); NULL:
+                                            the local index                                                                  */
+} bp5_mg_params;
+typedef struct {
+  int n_levels, degree;
+  uint32_t n_owned;            /* owned DoFs of this rank on the level                                                      */
+  double min_est, max_est, min_used, max_used; /* the level's Chebyshev estimate and the bounds its polynomial uses            */
+  int cg_its, chebyshev_degree;
+} bp5_mg_level;
+typedef struct bp5_mg bp5_mg;
+void bp5_mg_params_default(bp5_mg_params *params);
+int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, bp5_mg_transfer *const *transfers, const bp5_mg_params *params,
+                  bp5_mg **out);
+int bp5_mg_vmult(void *mg, double *dst, double *src); /* bp5_vmult_fn shape: plugs into bp5_cg_solve_preconditioned */
+int bp5_mg_level_info(const bp5_mg *mg, int level, bp5_mg_level *out);
+int bp5_mg_destroy(bp5_mg *mg);
+
 /* event helpers so a host in another language can time on the handle's stream */
 typedef struct bp5_event bp5_event;
 int bp5_event_create(bp5_event **out);

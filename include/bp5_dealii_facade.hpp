@@ -26,6 +26,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -667,6 +668,97 @@ public:
 private:
   bp5_mf *mf = nullptr;
 };
+// == MGTransferMatrixFree / MGTwoLevelTransfer (deal.II global-coarsening transfer; include/bp5.h: bp5_mg_transfer_*): the p-transfer
+// between two of the library's operators of degrees p >= 2 and max(1, p / 2) on the same cells
+class MGTwoLevelTransfer {
+public:
+  MGTwoLevelTransfer() = default;
+  MGTwoLevelTransfer(const MGTwoLevelTransfer &) = delete;
+  MGTwoLevelTransfer &operator=(const MGTwoLevelTransfer &) = delete;
+  ~MGTwoLevelTransfer() { clear(); }
+  template <typename MatrixType>
+  void reinit(const MatrixType &fine, const MatrixType &coarse)
+  {
+    clear();
+    check(bp5_mg_transfer_create(fine.handle(), coarse.handle(), &t));
+  }
+  void prolongate_and_add(double *dst_fine, const double *src_coarse) const { check(bp5_mg_transfer_prolongate_add(t, dst_fine, const_cast<double *>(src_coarse))); }
+  void restrict_and_add(double *dst_coarse, const double *src_fine) const { check(bp5_mg_transfer_restrict_add(t, dst_coarse, const_cast<double *>(src_fine))); }
+  void clear()
+  {
+    if (t) bp5_mg_transfer_destroy(t);
+    t = nullptr;
+  }
+  bp5_mg_transfer *handle() const { return t; }
+
+private:
+  bp5_mg_transfer *t = nullptr;
+};
+// == PreconditionMG<dim, VectorType, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a Chebyshev
+// coarse solver (step-37), coarsening in the polynomial degree (include/bp5.h: bp5_mg_*).  levels: the library's own operators, fine to
+// coarse, degrees p, max(1, p / 2), ..., on the same cells
+class PreconditionMG {
+public:
+  struct AdditionalData {
+    unsigned int smoother_degree = 4;
+    double smoothing_range = 20.;
+    unsigned int eig_cg_n_iterations = 10;
+    unsigned int coarse_degree = 60;
+    double coarse_range = 1000.;
+    unsigned int coarse_eig_cg_n_iterations = 30;
+    std::vector<const uint64_t *> start_ids_host; // per level: bp5_mesh_view.global_ids_host (empty: the local index)
+  };
+  PreconditionMG() = default;
+  PreconditionMG(const PreconditionMG &) = delete;
+  PreconditionMG &operator=(const PreconditionMG &) = delete;
+  ~PreconditionMG() { clear(); }
+  template <typename MatrixType>
+  void initialize(const std::vector<const MatrixType *> &levels) { initialize(levels, AdditionalData()); }
+  template <typename MatrixType>
+  void initialize(const std::vector<const MatrixType *> &levels, const AdditionalData &data)
+  {
+    static_assert(internal::has_coef<MatrixType>::value, "PreconditionMG (facade): the library's own operators (handle() + coef())");
+    clear();
+    const int n = (int)levels.size();
+    std::vector<bp5_mf *> mfs;
+    std::vector<const double *> coefs;
+    for (const MatrixType *A : levels) { mfs.push_back(A->handle()); coefs.push_back(A->coef()); }
+    transfers.resize(n > 0 ? n - 1 : 0);
+    std::vector<bp5_mg_transfer *> th;
+    for (int l = 0; l + 1 < n; ++l) {
+      transfers[l].reset(new MGTwoLevelTransfer);
+      transfers[l]->reinit(*levels[l], *levels[l + 1]);
+      th.push_back(transfers[l]->handle());
+    }
+    bp5_mg_params prm;
+    bp5_mg_params_default(&prm);
+    prm.smoother_degree = (int)data.smoother_degree; prm.smoothing_range = data.smoothing_range;
+    prm.eig_cg_n_iterations = (int)data.eig_cg_n_iterations; prm.coarse_degree = (int)data.coarse_degree;
+    prm.coarse_range = data.coarse_range; prm.coarse_eig_cg_n_iterations = (int)data.coarse_eig_cg_n_iterations;
+    if ((int)data.start_ids_host.size() == n) prm.start_ids_host = data.start_ids_host.data();
+    check(bp5_mg_create(n, mfs.data(), coefs.data(), th.data(), &prm, &mg));
+  }
+  void clear()
+  {
+    if (mg) bp5_mg_destroy(mg);
+    mg = nullptr;
+    transfers.clear();
+  }
+  // dst = one V-cycle applied to src (dst's prior content ignored); enqueued on the operators' stream
+  void vmult(double *dst, const double *src) const { check(bp5_mg_vmult(mg, dst, const_cast<double *>(src))); }
+  template <typename V> auto vmult(V &dst, const V &src) const -> decltype((void)dst.get_values()) { vmult(dst.get_values(), src.get_values()); }
+  bp5_mg_level level_info(int level) const
+  {
+    bp5_mg_level o{};
+    check(bp5_mg_level_info(mg, level, &o));
+    return o;
+  }
+  bp5_mg *mg_handle() const { return mg; }
+
+private:
+  bp5_mg *mg = nullptr;
+  std::vector<std::unique_ptr<MGTwoLevelTransfer>> transfers;
+};
 // cg.solve(A, x, b, preconditioner), bp5/solver.h:25-30: the solvers use nothing of A but A.vmult(dst, src).
 //  * an operator that exposes  bp5_mf* handle()  and  const double* coef()  is the library's own Poisson operator: the
 //    whole solve runs inside bp5_cg_solve (fused operator kernels, dot products inside the block kernel where possible);
@@ -725,6 +817,16 @@ public:
   auto solve(const MatrixType &A, VectorType &x, const VectorType &b, const ChebyshevHandle &preconditioner) -> decltype((void)x.get_values())
   {
     solve(A, x.get_values(), static_cast<const double *>(b.get_values()), preconditioner);
+  }
+  // cg.solve(A, x, b, PreconditionMG): bp5_cg_solve_preconditioned with bp5_mg_vmult (SolverCG only)
+  template <typename MatrixType>
+  void solve(const MatrixType &A, double *x, const double *b, const PreconditionMG &preconditioner)
+  {
+    static_assert(internal::has_coef<MatrixType>::value, "raw-pointer solve: the library's own operator");
+    bp5_cg_params prm{VARIANT, (int)control.max_steps, control.tolerance, 0, 0};
+    bp5_cg_result res{};
+    const int s = bp5_cg_solve_preconditioned(A.handle(), A.coef(), nullptr, nullptr, bp5_mg_vmult, preconditioner.mg_handle(), b, x, &prm, &res);
+    finish(res, s);
   }
   bp5_cg_result result{};
 
