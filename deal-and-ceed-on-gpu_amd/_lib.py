@@ -126,6 +126,7 @@ def lib():
         "bp5_mesh_create_brick": (i32, [C.POINTER(MeshDesc), C.POINTER(vp)]),
         "bp5_mesh_view_get": (i32, [vp, C.POINTER(MeshView)]),
         "bp5_mesh_destroy": (None, [vp]),
+        "bp5_mesh_parent_cells": (i32, [vp, vp, vp, vp]),
         "bp5_device_count": (i32, [C.POINTER(i32)]),
         "bp5_vec_alloc": (i32, [sz, C.POINTER(vp)]),
         "bp5_vec_free": (i32, [vp]),
@@ -190,6 +191,7 @@ def lib():
         "bp5_chebyshev_destroy": (i32, [vp]),
         "bp5_tridiagonal_eigenvalues": (i32, [i32, vp, vp, vp]),
         "bp5_mg_transfer_create": (i32, [vp, vp, C.POINTER(vp)]),
+        "bp5_mg_transfer_create_geometric": (i32, [vp, vp, vp, vp, C.POINTER(vp)]),
         "bp5_mg_transfer_prolongate_add": (i32, [vp, vp, vp]),
         "bp5_mg_transfer_restrict_add": (i32, [vp, vp, vp]),
         "bp5_mg_transfer_destroy": (i32, [vp]),

@@ -2531,9 +2531,12 @@ extern "C" int bp5_chebyshev_destroy(bp5_chebyshev *c)
 struct bp5_mg_transfer {
   bp5_mf *fine = nullptr, *coarse = nullptr;
   int pf = 0, pc = 0;
-  double *d_M = nullptr, *d_w = nullptr, *d_slots = nullptr;   // M [(pf+1)(pc+1)], fine weights [n_local fine], slots [n_cells (pc+1)^3]
-  uint32_t *d_cidx = nullptr, *d_wmask = nullptr;             // coarse indices per cell (MG_NO_DOF: Dirichlet), writer masks per cell
+  bool geometric = false;                                      // h-transfer (pf == pc): parent cells, M_0 and M_1
+  double *d_M = nullptr, *d_w = nullptr, *d_slots = nullptr;   // M [(pf+1)(pc+1)] (geometric: [2][(p+1)^2]), fine weights [n_local fine], slots [fine n_cells (pc+1)^3]
+  uint32_t *d_cidx = nullptr, *d_wmask = nullptr;             // coarse indices per cell (MG_NO_DOF: Dirichlet; geometric: per COARSE cell), writer masks per fine cell
   uint32_t *d_coff = nullptr, *d_cslot = nullptr;             // per coarse local DoF: its slots, ascending
+  uint32_t *d_pcode = nullptr;                                 // geometric: per fine cell parent << 3 | child
+  std::vector<void *> device_arrays() const { return {d_M, d_w, d_slots, d_cidx, d_wmask, d_coff, d_cslot, d_pcode}; }
 };
 
 // the instantiated degree pairs (pf -> max(1, pf / 2))
@@ -2569,8 +2572,48 @@ static int mg_restrict_launch(bp5_mg_transfer *t, const double *b, const double 
   case 8: return fn<9, 5>(t, __VA_ARGS__);                                                                         \
   default: return fail(BP5_ERR_INVALID, "multigrid transfer: fine degree must be 2..8");                           \
   }
-static int mg_prolongate_dispatch(bp5_mg_transfer *t, double *dst, const double *src) { MG_DISPATCH(mg_prolongate_launch, t, dst, src); }
-static int mg_restrict_dispatch(bp5_mg_transfer *t, const double *b, const double *tv) { MG_DISPATCH(mg_restrict_launch, t, b, tv); }
+// geometric transfers, p = 1..4
+template <int N>
+static int mg_geo_prolongate_launch(bp5_mg_transfer *t, double *dst, const double *src)
+{
+  using S = MgShape<N, N>;
+  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
+  if (grid) hipLaunchKernelGGL((mg_geo_prolongate_kernel<N>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_cidx, t->d_pcode, t->fine->d_l2g,
+                              t->d_wmask, nc, src, dst);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+template <int N>
+static int mg_geo_restrict_launch(bp5_mg_transfer *t, const double *b, const double *tv)
+{
+  using S = MgShape<N, N>;
+  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
+  if (!grid) return BP5_OK;
+  if (tv) hipLaunchKernelGGL((mg_geo_restrict_kernel<N, true>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_pcode, t->fine->d_l2g, nc, t->d_w, b, tv,
+                             t->d_slots);
+  else hipLaunchKernelGGL((mg_geo_restrict_kernel<N, false>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_pcode, t->fine->d_l2g, nc, t->d_w, b, tv,
+                          t->d_slots);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+#define MG_GEO_DISPATCH(fn, t, ...)                                                                                \
+  switch (t->pf) {                                                                                                 \
+  case 1: return fn<2>(t, __VA_ARGS__);                                                                            \
+  case 2: return fn<3>(t, __VA_ARGS__);                                                                            \
+  case 3: return fn<4>(t, __VA_ARGS__);                                                                            \
+  case 4: return fn<5>(t, __VA_ARGS__);                                                                            \
+  default: return fail(BP5_ERR_INVALID, "geometric multigrid transfer: degree must be 1..4");                      \
+  }
+static int mg_prolongate_dispatch(bp5_mg_transfer *t, double *dst, const double *src)
+{
+  if (t->geometric) MG_GEO_DISPATCH(mg_geo_prolongate_launch, t, dst, src);
+  MG_DISPATCH(mg_prolongate_launch, t, dst, src);
+}
+static int mg_restrict_dispatch(bp5_mg_transfer *t, const double *b, const double *tv)
+{
+  if (t->geometric) MG_GEO_DISPATCH(mg_geo_restrict_launch, t, b, tv);
+  MG_DISPATCH(mg_restrict_launch, t, b, tv);
+}
 
 static int mg_combine(bp5_mg_transfer *t, double *dst, bool add)
 {
@@ -2584,6 +2627,67 @@ static int mg_combine(bp5_mg_transfer *t, double *dst, bool add)
   return BP5_OK;
 }
 static bool mg_distributed(const bp5_mf *mf) { return mf->comm && !mf->neighbors.empty(); }
+
+// the CSR of each coarse local DoF's slots, ascending (= cell order): slot_dof[s] the coarse DoF slot s adds to (MG_NO_DOF: none)
+static int mg_upload_slot_csr(bp5_mg_transfer *t, const std::vector<uint32_t> &slot_dof)
+{
+  const size_t nlc = t->coarse->n_local();
+  std::vector<uint32_t> coff(nlc + 1, 0u);
+  for (uint32_t g : slot_dof)
+    if (g != MG_NO_DOF) ++coff[g + 1];
+  for (size_t g = 0; g < nlc; ++g) coff[g + 1] += coff[g];
+  std::vector<uint32_t> cslot(coff[nlc]), fill(coff.begin(), coff.end() - 1);
+  for (size_t s = 0; s < slot_dof.size(); ++s)
+    if (slot_dof[s] != MG_NO_DOF) cslot[fill[slot_dof[s]]++] = (uint32_t)s;
+  BP5_TRY(upload(&t->d_coff, coff.data(), coff.size()));
+  BP5_TRY(upload(&t->d_cslot, cslot.data(), cslot.size()));
+  return BP5_OK;
+}
+
+// fine side of either transfer: writer masks (the first cell in handle order that holds an owned fine DoF writes it), the weights w = 1 /
+// (cells that hold the DoF, all ranks), the slot array; synchronises the stream
+static int mg_setup_fine_side(bp5_mg_transfer *t)
+{
+  bp5_mf *fine = t->fine;
+  const int f3 = fine->n3, c3 = t->coarse->n3;
+  const uint32_t ncell = fine->n_cells;
+  const size_t nlf = fine->n_local();
+  const int words = (f3 + 31) / 32;
+  std::vector<uint32_t> wmask((size_t)ncell * words, 0u);
+  std::vector<uint8_t> written(fine->n_owned, 0);
+  std::vector<double> count(std::max<size_t>(nlf, 1), 0.0);
+  for (uint32_t c = 0; c < ncell; ++c)
+    for (int r = 0; r < f3; ++r) {
+      const uint32_t g = fine->h_l2g[(size_t)c * f3 + r];
+      count[g] += 1.0;
+      if (g < fine->n_owned && !written[g]) {
+        written[g] = 1;
+        wmask[(size_t)c * words + r / 32] |= 1u << (r & 31);
+      }
+    }
+  for (uint32_t g = 0; g < fine->n_owned; ++g)
+    if (!written[g]) return fail(BP5_ERR_INVALID, "multigrid transfer: an owned fine DoF lies in none of the rank's cells");
+  BP5_TRY(upload(&t->d_wmask, wmask.data(), wmask.size()));
+  BP5_TRY(upload(&t->d_w, count.data(), count.size()));
+  if (mg_distributed(fine)) { // the counts of all ranks: ghost counts to their owners, the totals back to the ghosts
+    BP5_TRY(bp5_halo_scatter_add(fine, t->d_w));
+    BP5_TRY(bp5_halo_gather(fine, t->d_w));
+  }
+  if (nlf) {
+    hipLaunchKernelGGL(reciprocal_kernel, dim3((nlf + 255) / 256), dim3(256), 0, fine->stream, t->d_w, nlf);
+    KERNEL_CHECK();
+  }
+  HIP_TRY(hipMalloc((void **)&t->d_slots, std::max<size_t>((size_t)ncell * c3, 1) * sizeof(double)));
+  HIP_TRY(hipStreamSynchronize(fine->stream));
+  return BP5_OK;
+}
+
+// frees the device arrays of a transfer that was not handed out
+struct MgTransferGuard {
+  bp5_mg_transfer *t;
+  bool keep = false;
+  ~MgTransferGuard() { if (!keep) for (void *p : t->device_arrays()) if (p) hipFree(p); }
+};
 
 extern "C" int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_transfer **out)
 {
@@ -2616,11 +2720,7 @@ extern "C" int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_trans
   }
   HIP_TRY(hipSetDevice(fine->device));
   std::unique_ptr<bp5_mg_transfer> t(new bp5_mg_transfer);
-  struct Free {
-    bp5_mg_transfer *t;
-    bool keep = false;
-    ~Free() { if (!keep) for (void *p : {(void *)t->d_M, (void *)t->d_w, (void *)t->d_slots, (void *)t->d_cidx, (void *)t->d_wmask, (void *)t->d_coff, (void *)t->d_cslot}) if (p) hipFree(p); }
-  } guard{t.get()};
+  MgTransferGuard guard{t.get()};
   t->fine = fine; t->coarse = coarse; t->pf = fine->degree; t->pc = coarse->degree;
   // M from the product formula on the FE_Q nodes; end rows exact unit vectors
   std::vector<double> xf(nf), xc(nc), M((size_t)nf * nc);
@@ -2639,47 +2739,95 @@ extern "C" int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_trans
   }
   BP5_TRY(upload(&t->d_M, M.data(), M.size()));
   // coarse indices (Dirichlet DoFs: MG_NO_DOF) and the CSR of each coarse DoF's slots, in cell order
-  std::vector<uint32_t> cidx(coarse->h_l2g), coff(nlc + 1, 0u);
-  for (size_t s = 0; s < cidx.size(); ++s) {
-    if (coarse->h_constrained[cidx[s]]) cidx[s] = MG_NO_DOF;
-    else ++coff[cidx[s] + 1];
-  }
-  for (size_t g = 0; g < nlc; ++g) coff[g + 1] += coff[g];
-  std::vector<uint32_t> cslot(coff[nlc]), fill(coff.begin(), coff.end() - 1);
+  std::vector<uint32_t> cidx(coarse->h_l2g);
   for (size_t s = 0; s < cidx.size(); ++s)
-    if (cidx[s] != MG_NO_DOF) cslot[fill[cidx[s]]++] = (uint32_t)s;
+    if (coarse->h_constrained[cidx[s]]) cidx[s] = MG_NO_DOF;
   if ((uint64_t)ncell * c3 >= MG_NO_DOF) return fail(BP5_ERR_INVALID, "multigrid transfer: too many coarse cell entries for 32-bit slots");
   BP5_TRY(upload(&t->d_cidx, cidx.data(), cidx.size()));
-  BP5_TRY(upload(&t->d_coff, coff.data(), coff.size()));
-  BP5_TRY(upload(&t->d_cslot, cslot.data(), cslot.size()));
-  // writer masks: the first cell (handle order) that holds an owned fine DoF writes it; the cell counts of every fine DoF
-  const int words = (f3 + 31) / 32;
-  std::vector<uint32_t> wmask((size_t)ncell * words, 0u);
-  std::vector<uint8_t> written(fine->n_owned, 0);
-  std::vector<double> count(std::max<size_t>(nlf, 1), 0.0);
-  for (uint32_t c = 0; c < ncell; ++c)
-    for (int r = 0; r < f3; ++r) {
-      const uint32_t g = fine->h_l2g[(size_t)c * f3 + r];
-      count[g] += 1.0;
-      if (g < fine->n_owned && !written[g]) {
-        written[g] = 1;
-        wmask[(size_t)c * words + r / 32] |= 1u << (r & 31);
+  BP5_TRY(mg_upload_slot_csr(t.get(), cidx));
+  BP5_TRY(mg_setup_fine_side(t.get()));
+  guard.keep = true;
+  *out = t.release();
+  return BP5_OK;
+}
+
+extern "C" int bp5_mg_transfer_create_geometric(bp5_mf *fine, bp5_mf *coarse, const uint32_t *parent, const uint8_t *child, bp5_mg_transfer **out)
+{
+  if (!fine || !coarse || !out || (fine->n_cells && (!parent || !child))) return fail(BP5_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (fine->degree != coarse->degree || fine->degree < 1 || fine->degree > 4)
+    return fail(BP5_ERR_INVALID, "geometric multigrid transfer: need equal degrees in 1..4");
+  if (fine->d_hang_mask || coarse->d_hang_mask || fine->has_hanging || coarse->has_hanging)
+    return fail(BP5_ERR_INVALID, "geometric multigrid transfer: hanging-node meshes (constraint_mask) are not supported");
+  if (fine->comm != coarse->comm) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: the handles have different communicators");
+  if (fine->stream != coarse->stream || fine->device != coarse->device)
+    return fail(BP5_ERR_INVALID, "geometric multigrid transfer: the handles have different streams");
+  const int n = fine->n, p = fine->degree, n3 = fine->n3;
+  const uint32_t nf = fine->n_cells, nc = coarse->n_cells;
+  if ((uint64_t)nf != 8ull * nc) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: the fine handle must have 8 cells per coarse cell");
+  if (nc >= (1u << 29)) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: too many coarse cells for 29-bit parent indices");
+  if ((uint64_t)nf * n3 >= MG_NO_DOF) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: too many fine cell entries for 32-bit slots");
+  // every coarse cell: 8 children with distinct child codes
+  std::vector<uint8_t> seen(nc, 0);
+  for (uint32_t k = 0; k < nf; ++k) {
+    if (parent[k] >= nc) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: a parent index is not a local coarse cell");
+    if (child[k] > 7) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: a child code is not in 0..7");
+    if (seen[parent[k]] & (1u << child[k])) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: a coarse cell has two children with one child code");
+    seen[parent[k]] |= (uint8_t)(1u << child[k]);
+  }
+  for (uint32_t c = 0; c < nc; ++c)
+    if (seen[c] != 0xff) return fail(BP5_ERR_INVALID, "geometric multigrid transfer: a coarse cell does not have 8 children");
+  // the map against the geometry: the corner a child shares with its parent has the parent's coordinates (to 1e-12 of the parent's size)
+  {
+    std::vector<double> xf(fine->n_local() * 3), xc(coarse->n_local() * 3);
+    HIP_TRY(hipSetDevice(fine->device));
+    HIP_TRY(hipStreamSynchronize(fine->stream));
+    if (!xf.empty()) HIP_TRY(hipMemcpy(xf.data(), fine->d_coords, xf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (!xc.empty()) HIP_TRY(hipMemcpy(xc.data(), coarse->d_coords, xc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    auto corner = [&](int ch) { return (ch & 1) * p + n * (((ch >> 1) & 1) * p + n * ((ch >> 2) & 1) * p); };
+    for (uint32_t k = 0; k < nf; ++k) {
+      const uint32_t *lc = &coarse->h_l2g[(size_t)parent[k] * n3];
+      const double *a = &xc[3 * (size_t)lc[0]], *z = &xc[3 * (size_t)lc[n3 - 1]];
+      const double size = std::sqrt((z[0] - a[0]) * (z[0] - a[0]) + (z[1] - a[1]) * (z[1] - a[1]) + (z[2] - a[2]) * (z[2] - a[2]));
+      const double *Xf = &xf[3 * (size_t)fine->h_l2g[(size_t)k * n3 + corner(child[k])]], *Xc = &xc[3 * (size_t)lc[corner(child[k])]];
+      for (int e = 0; e < 3; ++e)
+        if (!(std::fabs(Xf[e] - Xc[e]) <= 1e-12 * size))
+          return fail(BP5_ERR_INVALID, "geometric multigrid transfer: a fine cell's corner does not lie on its parent's corner (wrong parent map)");
+    }
+  }
+  std::unique_ptr<bp5_mg_transfer> t(new bp5_mg_transfer);
+  MgTransferGuard guard{t.get()};
+  t->fine = fine; t->coarse = coarse; t->pf = t->pc = p; t->geometric = true;
+  // M_s[a][b] = phi_b(xi_a / 2 + s / 2) from the product formula; rows on a coarse node exact unit rows
+  std::vector<double> x(n), M(2 * (size_t)n * n);
+  BP5_TRY(bp5_shape_tables(p, BP5_QUAD_GAUSS, x.data(), nullptr, nullptr, nullptr, nullptr));
+  for (int sh = 0; sh < 2; ++sh)
+    for (int a = 0; a < n; ++a) {
+      const double xa = 0.5 * x[a] + 0.5 * sh;
+      double *row = &M[((size_t)sh * n + a) * n];
+      int hit = -1;
+      for (int b = 0; b < n; ++b)
+        if (std::fabs(xa - x[b]) < 1e-12) hit = b;
+      for (int b = 0; b < n; ++b) {
+        double v = 1.0;
+        for (int m = 0; m < n; ++m)
+          if (m != b) v *= (xa - x[m]) / (x[b] - x[m]);
+        row[b] = hit < 0 ? v : (b == hit ? 1.0 : 0.0);
       }
     }
-  for (uint32_t g = 0; g < fine->n_owned; ++g)
-    if (!written[g]) return fail(BP5_ERR_INVALID, "multigrid transfer: an owned fine DoF lies in none of the rank's cells");
-  BP5_TRY(upload(&t->d_wmask, wmask.data(), wmask.size()));
-  BP5_TRY(upload(&t->d_w, count.data(), count.size()));
-  if (mg_distributed(fine)) { // the counts of all ranks: ghost counts to their owners, the totals back to the ghosts
-    BP5_TRY(bp5_halo_scatter_add(fine, t->d_w));
-    BP5_TRY(bp5_halo_gather(fine, t->d_w));
+  BP5_TRY(upload(&t->d_M, M.data(), M.size()));
+  // per coarse cell its Dirichlet-masked coarse indices; per fine cell parent << 3 | child; the slots of fine cell k add to its parent's DoFs
+  std::vector<uint32_t> pidx(coarse->h_l2g), pcode(nf), slot_dof((size_t)nf * n3);
+  for (uint32_t &g : pidx)
+    if (coarse->h_constrained[g]) g = MG_NO_DOF;
+  for (uint32_t k = 0; k < nf; ++k) {
+    pcode[k] = parent[k] << 3 | child[k];
+    std::copy(pidx.begin() + (size_t)parent[k] * n3, pidx.begin() + (size_t)(parent[k] + 1) * n3, slot_dof.begin() + (size_t)k * n3);
   }
-  if (nlf) {
-    hipLaunchKernelGGL(reciprocal_kernel, dim3((nlf + 255) / 256), dim3(256), 0, fine->stream, t->d_w, nlf);
-    KERNEL_CHECK();
-  }
-  HIP_TRY(hipMalloc((void **)&t->d_slots, std::max<size_t>((size_t)ncell * c3, 1) * sizeof(double)));
-  HIP_TRY(hipStreamSynchronize(fine->stream));
+  BP5_TRY(upload(&t->d_cidx, pidx.data(), pidx.size()));
+  BP5_TRY(upload(&t->d_pcode, pcode.data(), pcode.size()));
+  BP5_TRY(mg_upload_slot_csr(t.get(), slot_dof));
+  BP5_TRY(mg_setup_fine_side(t.get()));
   guard.keep = true;
   *out = t.release();
   return BP5_OK;
@@ -2718,7 +2866,7 @@ extern "C" int bp5_mg_transfer_destroy(bp5_mg_transfer *t)
   if (!t) return BP5_OK;
   hipSetDevice(t->fine->device);
   hipStreamSynchronize(t->fine->stream);
-  for (void *p : {(void *)t->d_M, (void *)t->d_w, (void *)t->d_slots, (void *)t->d_cidx, (void *)t->d_wmask, (void *)t->d_coff, (void *)t->d_cslot})
+  for (void *p : t->device_arrays())
     if (p) hipFree(p);
   delete t;
   return BP5_OK;

@@ -425,6 +425,7 @@ struct bp5_mesh {
   uint64_t n_global = 0;
   uint32_t ND[3] = {0, 0, 0};
   std::vector<uint32_t> l2g, constrained, send_offsets, send_indices, recv_offsets, block_off;
+  std::vector<uint32_t> cell_xyz; // [n_cells][3] the global cell coordinates of every local cell, in handle order
   std::vector<double> coords;
   std::vector<uint64_t> gids;
   std::vector<int> neighbors;
@@ -554,6 +555,7 @@ extern "C" int bp5_mesh_create_brick(const bp5_mesh_desc *d, bp5_mesh **out)
   // cells form compact groups for the block-assembled operator kernel
   const size_t nl = (size_t)n * n * n;
   m->l2g.resize(n_cells * nl);
+  m->cell_xyz.resize(n_cells * 3);
   const uint64_t zi0 = z0 + (r > 0 ? 1 : 0); // interior layers [zi0, z1)
   m->n_interior = (uint32_t)((z1 - zi0) * n0 * n1);
   const bool blocked = d->cell_block[0] && d->cell_block[1] && d->cell_block[2];
@@ -574,6 +576,7 @@ extern "C" int bp5_mesh_create_brick(const bp5_mesh_desc *d, bp5_mesh **out)
                 for (uint64_t x = X; x < std::min(X + bx, n0); ++x) {
                   if (class_major && (int)(((x - X) & 1) | (((y - Y) & 1) << 1) | (((z - Z) & 1) << 2)) != cls) continue;
                   uint32_t *dst = &m->l2g[c * nl];
+                  m->cell_xyz[3 * c] = (uint32_t)x; m->cell_xyz[3 * c + 1] = (uint32_t)y; m->cell_xyz[3 * c + 2] = (uint32_t)z;
                   for (int k = 0; k < n; ++k)
                     for (int j = 0; j < n; ++j)
                       for (int i = 0; i < n; ++i) dst[i + n * (j + n * k)] = local_of(p * x + i, p * y + j, p * z + k);
@@ -689,6 +692,44 @@ extern "C" int bp5_mesh_view_get(const bp5_mesh *m, bp5_mesh_view *v)
 }
 
 extern "C" void bp5_mesh_destroy(bp5_mesh *m) { delete m; }
+
+// 2:1 pair: the coarse z-slab of every rank r holds the parents of its fine z-slab, floor(n2 r / R) == 2 floor((n2 / 2) r / R)
+static bool slab_split_nests(uint64_t n2, int R)
+{
+  for (int r = 0; r <= R; ++r)
+    if (n2 * r / R != 2 * ((n2 / 2) * r / R)) return false;
+  return true;
+}
+
+extern "C" int bp5_mesh_parent_cells(const bp5_mesh *fine, const bp5_mesh *coarse, uint32_t *parent, uint8_t *child)
+{
+  if (!fine || !coarse || (fine->n_cells && (!parent || !child))) return fail(BP5_ERR_INVALID, "null argument");
+  const bp5_mesh_desc &f = fine->desc, &c = coarse->desc;
+  if (f.degree != c.degree) return fail(BP5_ERR_INVALID, "mesh parent cells: the meshes have different degrees");
+  for (int e = 0; e < 3; ++e)
+    if (f.cells[e] != 2 * c.cells[e]) return fail(BP5_ERR_INVALID, "mesh parent cells: the fine mesh must have twice the coarse cells in every direction");
+  if (std::fabs(2.0 * f.h - c.h) > 1e-14 * c.h) return fail(BP5_ERR_INVALID, "mesh parent cells: the coarse cell size must be twice the fine one");
+  if (f.deform_amp != c.deform_amp) return fail(BP5_ERR_INVALID, "mesh parent cells: the meshes have different deformations");
+  if (f.rank != c.rank || f.n_ranks != c.n_ranks) return fail(BP5_ERR_INVALID, "mesh parent cells: the meshes have different ranks");
+  if (!slab_split_nests(f.cells[2], f.n_ranks))
+    return fail(BP5_ERR_INVALID, "mesh parent cells: the z-slab split of the coarse mesh does not hold the parents of every rank's fine cells "
+                                 "(floor(n2 r / R) != 2 floor((n2 / 2) r / R) for some rank r)");
+  // coarse cell -> local index through its lexicographic position inside the rank's slab
+  const uint64_t cx = c.cells[0], cy = c.cells[1], cz0 = (uint64_t)c.cells[2] * c.rank / c.n_ranks;
+  std::vector<uint32_t> local(coarse->n_cells, 0xffffffffu);
+  for (uint32_t k = 0; k < coarse->n_cells; ++k) {
+    const uint32_t *X = &coarse->cell_xyz[3 * (size_t)k];
+    local[X[0] + cx * (X[1] + cy * (X[2] - cz0))] = k;
+  }
+  for (uint32_t k = 0; k < fine->n_cells; ++k) {
+    const uint32_t *X = &fine->cell_xyz[3 * (size_t)k];
+    const uint64_t z = X[2] / 2;
+    if (z < cz0 || z - cz0 >= coarse->n_cells / (cx * cy)) return fail(BP5_ERR_INVALID, "mesh parent cells: a parent lies outside the rank's coarse cells");
+    parent[k] = local[X[0] / 2 + cx * (X[1] / 2 + cy * (z - cz0))];
+    child[k] = (uint8_t)((X[0] & 1) | ((X[1] & 1) << 1) | ((X[2] & 1) << 2));
+  }
+  return BP5_OK;
+}
 
 // ---------------------------------------------------------------------------------- tridiagonal eigenvalues
 // Sturm-sequence bisection (Barth, Martin, Wilkinson 1967): the number of negative pivots of the LDL^T factorisation of T - x I is the number of

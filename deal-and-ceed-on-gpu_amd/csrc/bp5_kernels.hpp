@@ -3850,6 +3850,131 @@ __global__ void __launch_bounds__(256) mg_combine_kernel(const uint32_t *__restr
   }
 }
 
+// ---- geometric (h) transfer at one degree between a coarse parent and its 8 children (bp5_mg_transfer_create_geometric; deal.II
+// MGTwoLevelTransfer::reinit_geometric_transfer).  M[s][a][b] = phi_b(xi_a / 2 + s / 2), s = 0, 1, N x N each (N = p + 1).  pcode[c] =
+// parent << 3 | child of fine cell c (child = cx | cy << 1 | cz << 2); pidx: the Dirichlet-masked coarse index list of every coarse cell
+// (MG_NO_DOF: value 0).  The same sum factorisation, writer masks and slots as the p-transfer (MgShape<N, N>); every cell applies
+// M[cx] x M[cy] x M[cz]
+template <int N>
+__global__ void __launch_bounds__(256) mg_geo_prolongate_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pidx,
+                                                                const uint32_t *__restrict__ pcode, const uint32_t *__restrict__ fidx,
+                                                                const uint32_t *__restrict__ wmask, uint32_t n_cells,
+                                                                const double *__restrict__ src_c, double *__restrict__ dst_f)
+{
+  using S = MgShape<N, N>;
+  constexpr int N3 = S::F3, CPB = S::CPB;
+  __shared__ double sM[2 * N * N];
+  __shared__ double buf[CPB][S::LDS];
+  __shared__ uint32_t sch[CPB];
+  const int t = threadIdx.x;
+  const uint32_t c0 = blockIdx.x * CPB;
+  for (int i = t; i < 2 * N * N; i += 256) sM[i] = M[i];
+  for (int cl = t; cl < CPB; cl += 256) sch[cl] = c0 + cl < n_cells ? pcode[c0 + cl] & 7u : 0u;
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3;
+    const uint32_t c = c0 + cl;
+    double v = 0.0;
+    if (c < n_cells) {
+      const uint32_t g = pidx[(size_t)(pcode[c] >> 3) * N3 + r];
+      v = g == MG_NO_DOF ? 0.0 : src_c[g];
+    }
+    buf[cl][r] = v;
+  }
+  __syncthreads();
+  // x: s1[k][j][a] = sum_b Mx[a][b] s0[k][j][b]
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, a = r % N, kj = r / N;
+    const double *Mx = sM + (sch[cl] & 1u) * N * N, *s0 = buf[cl] + kj * N;
+    double acc = 0.0;
+#pragma unroll
+    for (int b = 0; b < N; ++b) acc += Mx[a * N + b] * s0[b];
+    buf[cl][N3 + r] = acc;
+  }
+  __syncthreads();
+  // y: s2[k][b][a] = sum_j My[b][j] s1[k][j][a]
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, a = r % N, b = (r / N) % N, k = r / (N * N);
+    const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc += My[b * N + j] * s1[(k * N + j) * N + a];
+    buf[cl][2 * N3 + r] = acc;
+  }
+  __syncthreads();
+  // z and write-out where this cell is the DoF's writer
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, ab = r % (N * N), kk = r / (N * N);
+    const uint32_t c = c0 + cl;
+    if (c >= n_cells || !((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) continue;
+    const double *Mz = sM + ((sch[cl] >> 2) & 1u) * N * N, *s2 = buf[cl] + 2 * N3;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc += Mz[kk * N + k] * s2[k * N * N + ab];
+    dst_f[fidx[(size_t)c * N3 + r]] += acc;
+  }
+}
+
+// the fine cell's share of P^T v in its slots: slots[c][i] = (Mx^T x My^T x Mz^T)(w (b - t))|_cell, i < N^3 (RESIDUAL false: w b);
+// mg_combine_kernel sums them per coarse DoF in cell order
+template <int N, bool RESIDUAL>
+__global__ void __launch_bounds__(256) mg_geo_restrict_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pcode,
+                                                              const uint32_t *__restrict__ fidx, uint32_t n_cells, const double *__restrict__ w,
+                                                              const double *__restrict__ b, const double *__restrict__ tv,
+                                                              double *__restrict__ slots)
+{
+  using S = MgShape<N, N>;
+  constexpr int N3 = S::F3, CPB = S::CPB;
+  __shared__ double sM[2 * N * N];
+  __shared__ double buf[CPB][S::LDS];
+  __shared__ uint32_t sch[CPB];
+  const int t = threadIdx.x;
+  const uint32_t c0 = blockIdx.x * CPB;
+  for (int i = t; i < 2 * N * N; i += 256) sM[i] = M[i];
+  for (int cl = t; cl < CPB; cl += 256) sch[cl] = c0 + cl < n_cells ? pcode[c0 + cl] & 7u : 0u;
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3;
+    const uint32_t c = c0 + cl;
+    double v = 0.0;
+    if (c < n_cells) {
+      const uint32_t g = fidx[(size_t)c * N3 + r];
+      v = w[g] * (RESIDUAL ? b[g] - tv[g] : b[g]);
+    }
+    buf[cl][r] = v;
+  }
+  __syncthreads();
+  // z: s1[k][j][i] = sum_kk Mz[kk][k] s0[kk][j][i]
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, ji = r % (N * N), k = r / (N * N);
+    const double *Mz = sM + ((sch[cl] >> 2) & 1u) * N * N, *s0 = buf[cl];
+    double acc = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < N; ++kk) acc += Mz[kk * N + k] * s0[kk * N * N + ji];
+    buf[cl][N3 + r] = acc;
+  }
+  __syncthreads();
+  // y: s2[k][j][i] = sum_jj My[jj][j] s1[k][jj][i]
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, i = r % N, j = (r / N) % N, k = r / (N * N);
+    const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
+    double acc = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < N; ++jj) acc += My[jj * N + j] * s1[(k * N + jj) * N + i];
+    buf[cl][2 * N3 + r] = acc;
+  }
+  __syncthreads();
+  // x: slot = sum_ii Mx[ii][i] s2[k][j][ii]
+  for (int e = t; e < CPB * N3; e += 256) {
+    const int cl = e / N3, r = e % N3, i = r % N, kj = r / N;
+    const uint32_t c = c0 + cl;
+    if (c >= n_cells) continue;
+    const double *Mx = sM + (sch[cl] & 1u) * N * N, *s2 = buf[cl] + 2 * N3;
+    double acc = 0.0;
+#pragma unroll
+    for (int ii = 0; ii < N; ++ii) acc += Mx[ii * N + i] * s2[kj * N + ii];
+    slots[(size_t)c * N3 + r] = acc;
+  }
+}
+
 // ---- self-check of the in-launch stream wait-value schedules (bp5_device.hip: halo_streams).  The producer counts itself in exactly like
 // apply_block_kernel's signal_part_done and then stays alive until the consumer -- enqueued on the waiting stream behind
 // hipStreamWaitValue64 -- has run, or 2 ms have passed: *result = 1 says the wait was released WHILE the producing kernel was running

@@ -8,8 +8,10 @@ C ABI (include/bp5.h).  Names, argument meaning and error behaviour follow the r
   SolverCG ............... deal.II SolverCG, call site bp5/step-64.cu:446-453
   SolverCGFullMerge ...... bp5/solver.h:16-30,343-542 (x-update schedule fixed)
   PreconditionChebyshev .. deal.II PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (Chebyshev-Jacobi, include/bp5.h)
-  MGTwoLevelTransfer ..... deal.II MGTwoLevelTransfer (p-transfer between FE_Q(p) and FE_Q(p/2) on the same cells)
-  PreconditionMG ......... deal.II PreconditionMG / Multigrid: V-cycle with Chebyshev smoothers (step-37), p-coarsening
+  MGTwoLevelTransfer ..... deal.II MGTwoLevelTransfer (p-transfer between FE_Q(p) and FE_Q(p/2) on the same cells; geometric
+                           transfer between 2:1 meshes of one degree, reinit_geometric_transfer)
+  PreconditionMG ......... deal.II PreconditionMG / Multigrid: V-cycle with Chebyshev smoothers (step-37), p-coarsening, then optional
+                           h-coarsening at degree 1 (step-75's global coarsening)
 
 Vectors are torch float64 CUDA tensors of n_owned + n_ghost entries (torch is plumbing for
 device memory / streams / the process group only -- no torch op is on the hot path)."""
@@ -545,14 +547,21 @@ class PreconditionChebyshev:
 
 class MGTwoLevelTransfer:
     """== MGTwoLevelTransfer (deal.II matrix-free global-coarsening transfer) between two operators of degrees pf >= 2 and
-    pc = max(1, pf // 2) on the same cells (bp5_mg_transfer_*, include/bp5.h).  prolongate_and_add: dst_f += P src_c;
-    restrict_and_add: dst_c += P^T src_f (Dirichlet rows of dst_c unchanged).  Vectors: owned + ghost storage of their operator."""
+    pc = max(1, pf // 2) on the same cells (bp5_mg_transfer_*, include/bp5.h); geometric=True: == reinit_geometric_transfer between two
+    operators of one degree in 1..4 on a 2:1 pair of BrickMeshes (BrickMesh.coarsen), the parent map from BrickMesh.parent_cells
+    (bp5_mg_transfer_create_geometric).  prolongate_and_add: dst_f += P src_c; restrict_and_add: dst_c += P^T src_f (Dirichlet rows of
+    dst_c unchanged).  Vectors: owned + ghost storage of their operator."""
 
-    def __init__(self, fine_op, coarse_op):
+    def __init__(self, fine_op, coarse_op, geometric=False):
         self._h = None
-        self.fine, self.coarse = fine_op, coarse_op
+        self.fine, self.coarse, self.geometric = fine_op, coarse_op, bool(geometric)
         h = C.c_void_p()
-        _lib.check(_lib.lib().bp5_mg_transfer_create(fine_op.mf_data.handle, coarse_op.mf_data.handle, C.byref(h)))
+        if self.geometric:
+            parent, child = fine_op.mf_data.mesh.parent_cells(coarse_op.mf_data.mesh)
+            _lib.check(_lib.lib().bp5_mg_transfer_create_geometric(fine_op.mf_data.handle, coarse_op.mf_data.handle, parent.ctypes.data,
+                                                                   child.ctypes.data, C.byref(h)))
+        else:
+            _lib.check(_lib.lib().bp5_mg_transfer_create(fine_op.mf_data.handle, coarse_op.mf_data.handle, C.byref(h)))
         self._h = h
 
     @property
@@ -589,24 +598,41 @@ def mg_coarse_degrees(degree):
     return degrees
 
 
-def make_mg_hierarchy(fine_op):
-    """The operators of the p-multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same cells, block order and
-    numbering scheme, coefficient, quadrature, device, stream and communicator at degrees p // 2, ..., 1.  Returns [fine_op, ...]."""
+def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
+    """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same cells, block order and
+    numbering scheme, coefficient, quadrature, device, stream and communicator at degrees p // 2, ..., 1; then, at degree 1, up to
+    h_levels geometric levels (an int, or "max": as many as the mesh allows), each on BrickMesh.coarsen(min_cells) of the one above
+    (half the cells per direction, twice h, the same domain), stopping where coarsen returns None.  h_levels = 0 (default): the p-levels
+    only.  Returns [fine_op, ...]."""
     from .mesh import BrickMesh
+    if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
+        raise BP5Error(1, f"make_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
     mf, m = fine_op.mf_data, fine_op.mf_data.mesh
     ops = [fine_op]
     stream = _torch().cuda.current_stream(mf.device).cuda_stream
+
+    def level(mesh):
+        return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream)
+
     for p in mg_coarse_degrees(m.degree)[1:]:
-        mesh = BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
-                         dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)
-        ops.append(type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream))
+        ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
+                                   dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)))
+    n_h = 0
+    while h_levels == "max" or n_h < h_levels:
+        coarse = ops[-1].mf_data.mesh.coarsen(min_cells)
+        if coarse is None:
+            break
+        ops.append(level(coarse))
+        n_h += 1
     return ops
 
 
 class PreconditionMG:
     """== PreconditionMG<dim, Vector, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a
-    Chebyshev coarse solver (step-37), coarsening in the polynomial degree (bp5_mg_*, include/bp5.h).  operators: PoissonOperators from
-    fine to coarse on the same cells, degrees p, max(1, p // 2), ... (make_mg_hierarchy builds them).  vmult is one symmetric V-cycle,
+    Chebyshev coarse solver (step-37), coarsening in the polynomial degree and then in the mesh (bp5_mg_*, include/bp5.h).  operators:
+    PoissonOperators from fine to coarse, degrees p, max(1, p // 2), ..., 1 on the same cells, then optionally degree-1 levels on
+    2:1 coarser BrickMeshes (make_mg_hierarchy builds them).  A pair of different degrees gets the p-transfer, a pair of equal degrees
+    the geometric one.  vmult is one symmetric V-cycle,
     enqueued on the operators' stream without a host synchronisation; SolverCG.solve passes it natively (bp5_mg_vmult)."""
 
     class AdditionalData:
@@ -628,7 +654,7 @@ class PreconditionMG:
         if not ops or not all(isinstance(o, PoissonOperator) for o in ops):
             raise BP5Error(1, "PreconditionMG needs a list of PoissonOperators, fine to coarse")
         self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
-        self.transfers = [MGTwoLevelTransfer(f, c) for f, c in zip(ops[:-1], ops[1:])]
+        self.transfers = [MGTwoLevelTransfer(f, c, geometric=f.mf_data.mesh.degree == c.mf_data.mesh.degree) for f, c in zip(ops[:-1], ops[1:])]
         ids = []
         for o in ops:
             g = getattr(o.mf_data.mesh, "global_ids", None)
@@ -657,12 +683,14 @@ class PreconditionMG:
         _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(_vals(dst), n), _ptr(_vals(src), n)))
 
     def level_info(self):
-        """Per level, fine to coarse: dict(degree, n_owned, n_global_dofs, min_est, max_est, min_used, max_used, cg_its, chebyshev_degree)."""
+        """Per level, fine to coarse: dict(degree, cells, n_owned, n_global_dofs, min_est, max_est, min_used, max_used, cg_its,
+        chebyshev_degree); cells: the level mesh's global cells per direction (None if its mesh does not say)."""
         out = []
         for lev, o in enumerate(self.operators):
             v = _lib.MGLevel()
             _lib.check(_lib.lib().bp5_mg_level_info(self.handle, lev, C.byref(v)))
-            out.append(dict(degree=v.degree, n_owned=v.n_owned, n_global_dofs=int(o.mf_data.mesh.n_global_dofs), min_est=v.min_est,
+            cells = getattr(o.mf_data.mesh, "cells", None)
+            out.append(dict(degree=v.degree, cells=tuple(int(c) for c in cells) if cells is not None else None, n_owned=v.n_owned, n_global_dofs=int(o.mf_data.mesh.n_global_dofs), min_est=v.min_est,
                             max_est=v.max_est, min_used=v.min_used, max_used=v.max_used, cg_its=v.cg_its, chebyshev_degree=v.chebyshev_degree))
         return out
 

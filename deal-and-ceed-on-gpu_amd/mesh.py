@@ -45,6 +45,28 @@ class BrickMesh:
         self.cell_block_order = cell_block_order
         self.cell_block_offsets = arr(v.cell_block_offsets_host, v.n_cell_blocks + 1, np.uint32) if v.n_cell_blocks else None
 
+    def coarsen(self, min_cells=4):
+        """The 2:1 coarser mesh (geometric multigrid): half the cells per direction, twice h, the same degree, domain, deformation,
+        rank split, cell blocks and numbering scheme.  None where coarsening stops: an odd cell count, fewer than min_cells cells in a
+        direction, or a z-slab split of the coarse mesh that does not hold the parents of every rank's fine cells
+        (floor(n2 r / R) != 2 floor((n2 / 2) r / R) for some r: there is no repartitioning)."""
+        n2, R = self.cells[2], self.n_ranks
+        if any(c % 2 or c // 2 < min_cells for c in self.cells):
+            return None
+        if any(n2 * r // R != 2 * ((n2 // 2) * r // R) for r in range(R + 1)):
+            return None
+        return BrickMesh(self.degree, tuple(c // 2 for c in self.cells), h=2 * self.h, deform_amp=self.deform_amp, rank=self.rank,
+                         n_ranks=self.n_ranks, cell_block=self.cell_block, dof_numbering=self.dof_numbering,
+                         cell_block_order=self.cell_block_order)
+
+    def parent_cells(self, coarse):
+        """(parent, child) of bp5_mesh_parent_cells: per local cell of this mesh, in handle order, the local index of its parent in the
+        2:1 coarser mesh `coarse` (uint32) and its position there, cx | cy << 1 | cz << 2 (uint8)"""
+        parent = np.zeros(self.n_cells, dtype=np.uint32)
+        child = np.zeros(self.n_cells, dtype=np.uint8)
+        _lib.check(_lib.lib().bp5_mesh_parent_cells(self._h, coarse._h, parent.ctypes.data, child.ctypes.data))
+        return parent, child
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             _lib.lib().bp5_mesh_destroy(self._h)

@@ -1,9 +1,11 @@
 // Multigrid-preconditioned CG written like the solve of deal.II's step-37 (Poisson with step-64's kappa), against the deal.II-shaped
-// facade (include/bp5_dealii_facade.hpp): the operators of the levels p, p / 2, ..., 1 on the same cells, PreconditionMG (V-cycle,
-// Chebyshev smoothers, Chebyshev coarse solver), SolverCG.  Prints the iteration count, the levels and the solution's norm.
+// facade (include/bp5_dealii_facade.hpp): the operators of the levels p, p / 2, ..., 1 on the same cells, then up to h_levels degree-1
+// levels on 2:1 coarser meshes (step-75's global coarsening), PreconditionMG (V-cycle, Chebyshev smoothers, Chebyshev coarse solver),
+// SolverCG.  Prints the iteration count, the levels and the solution's norm.
 //
-//   bp5_multigrid <p> <nx> <ny> <nz> <deform> <rel_tol> [coefficient]
+//   bp5_multigrid <p> <nx> <ny> <nz> <deform> <rel_tol> [coefficient] [h_levels]
 //     coefficient: 0 = kappa 1, 1 = step-64's kappa (default)
+//     h_levels: h-levels below degree 1 (default 0); coarsening stops at an odd cell count or below 4 cells in a direction
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,11 +51,12 @@ private:
 int main(int argc, char **argv)
 {
   if (argc < 7) {
-    fprintf(stderr, "usage: %s p nx ny nz deform rel_tol [coefficient]\n", argv[0]);
+    fprintf(stderr, "usage: %s p nx ny nz deform rel_tol [coefficient] [h_levels]\n", argv[0]);
     return 2;
   }
   try {
     const int coefficient = argc > 7 ? atoi(argv[7]) : BP5_COEF_STEP64;
+    const int h_levels = argc > 8 ? atoi(argv[8]) : 0;
     std::vector<bp5_mesh *> meshes;
     std::vector<bp5_mesh_view> views;
     for (int p = atoi(argv[1]);; p = p / 2 > 1 ? p / 2 : 1) { // the hierarchy p, p / 2, ..., 1 on the same cells
@@ -69,6 +72,30 @@ int main(int argc, char **argv)
       views.push_back(mv);
       if (p == 1) break;
     }
+    // h-levels at degree 1 (BrickMesh.coarsen's rule on one rank), with the parent maps of their transfers
+    std::vector<std::vector<uint32_t>> parents(views.size() - 1);
+    std::vector<std::vector<uint8_t>> children(views.size() - 1);
+    for (int k = 0; k < h_levels; ++k) {
+      bp5_mesh_desc md{};
+      md.degree = 1;
+      md.h = double(2 << k); md.deform_amp = atof(argv[5]); md.n_ranks = 1;
+      bool ok = true;
+      for (int d = 0; d < 3; ++d) {
+        const uint32_t n = views.back().global_dofs_per_dir[d] - 1; // cells of the level above (degree 1)
+        ok = ok && n % 2 == 0 && n / 2 >= 4;
+        md.cells[d] = n / 2;
+      }
+      if (!ok) break;
+      bp5_mesh *mesh;
+      check(bp5_mesh_create_brick(&md, &mesh));
+      bp5_mesh_view mv;
+      check(bp5_mesh_view_get(mesh, &mv));
+      parents.emplace_back(views.back().n_cells);
+      children.emplace_back(views.back().n_cells);
+      check(bp5_mesh_parent_cells(meshes.back(), mesh, parents.back().data(), children.back().data()));
+      meshes.push_back(mesh);
+      views.push_back(mv);
+    }
     {
       std::vector<std::unique_ptr<LaplaceOperator>> ops;
       std::vector<const LaplaceOperator *> levels;
@@ -77,6 +104,10 @@ int main(int argc, char **argv)
         ops.emplace_back(new LaplaceOperator(mv, coefficient));
         levels.push_back(ops.back().get());
         data.start_ids_host.push_back(mv.global_ids_host);
+      }
+      for (size_t l = 0; l < parents.size(); ++l) {
+        data.parent_cells.push_back(parents[l].empty() ? nullptr : parents[l].data());
+        data.child.push_back(children[l].empty() ? nullptr : children[l].data());
       }
       const LaplaceOperator &A = *ops[0];
       double *b, *x;

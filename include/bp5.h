@@ -119,6 +119,16 @@ int bp5_mesh_create_brick(const bp5_mesh_desc *desc, bp5_mesh **out);
 int bp5_mesh_view_get(const bp5_mesh *mesh, bp5_mesh_view *out);
 void bp5_mesh_destroy(bp5_mesh *mesh);
 
+/* Parent map of a 2:1 pair of brick meshes (the geometric multigrid transfer, bp5_mg_transfer_create_geometric): for every locally
+ * owned cell k of `fine`, in handle order, parent_cell_host[k] = the local index of the coarse cell that contains it and
+ * child_host[k] = its position in that parent, cx | cy << 1 | cz << 2 (cx = 1: the upper half in x).  Correct for every cell order the
+ * generator emits (lexicographic, bricks, class-major, the ghost-touching layer last on ranks > 0).  The pair must have the same
+ * degree, deform_amp, rank and n_ranks, fine cells = 2 x coarse cells in every direction and fine h = coarse h / 2, and the coarse
+ * z-slab split must hold the parents of every rank's fine cells: floor(n2 r / R) == 2 floor((n2 / 2) r / R) for all r (n2 = fine
+ * layers, R = n_ranks; e.g. 120 layers on 8 ranks fail: there is no repartitioning).  Otherwise BP5_ERR_INVALID with the reason in
+ * bp5_last_error.  Host only (no GPU).  parent_cell_host, child_host: [fine n_cells]. */
+int bp5_mesh_parent_cells(const bp5_mesh *fine, const bp5_mesh *coarse, uint32_t *parent_cell_host, uint8_t *child_host);
+
 /* ------------------------------------------------------------------------------------------ */
 /* device + vectors                                                                            */
 int bp5_device_count(int *count);
@@ -532,8 +542,25 @@ int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst_fine, double 
 int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst_coarse, double *src_fine);
 int bp5_mg_transfer_destroy(bp5_mg_transfer *t);
 
+/* Geometric (h) transfer at one degree p in 1..4 (deal.II MGTwoLevelTransfer::reinit_geometric_transfer, step-75's h-levels): the
+ * coarse handle's cells are the parents of the fine handle's, 8 children each (bp5_mesh_parent_cells gives the map: parent_cell_host[k],
+ * child_host[k] = cx | cy << 1 | cz << 2 of fine cell k).  M_s[a][b] = phi_b^p(xi_a / 2 + s / 2), s = 0, 1, on the FE_Q nodes of
+ * bp5_shape_tables; rows where a fine node coincides with a coarse node are exact unit rows.  Fine cell k interpolates its parent's
+ * coarse values with M_cx x M_cy x M_cz.  Everything else is the p-transfer's scheme above: prolongate_add writes each owned fine DoF
+ * from one cell (writer mask); restrict_add forms w (.) src_f (w = 1 / cells holding the DoF, all ranks) per fine cell into slots that
+ * one combine pass sums in cell order (no atomics, bitwise reproducible); coarse Dirichlet DoFs are read as 0 and get no slots; the same
+ * halo gather and scatter-add with neighbours.  The handle works with bp5_mg_transfer_prolongate_add / _restrict_add / _destroy and
+ * in bp5_mg_create chains (mixed with p-transfers).  Device data: one Dirichlet-masked coarse index list per coarse cell and one
+ * 32-bit word per fine cell (parent << 3 | child).  Checked at create (BP5_ERR_INVALID): equal degrees in 1..4; same communicator,
+ * stream and device; no hanging-node masks; every coarse cell has exactly 8 children with distinct child codes and every parent index
+ * is a local coarse cell; the fine corner each child shares with its parent has the parent's corner coordinates to 1e-12 of the
+ * parent's size (catches a wrong map).  Create is synchronous. */
+int bp5_mg_transfer_create_geometric(bp5_mf *fine, bp5_mf *coarse, const uint32_t *parent_cell_host, const uint8_t *child_host,
+                                     bp5_mg_transfer **out);
+
 /* PreconditionMG: one symmetric V-cycle per vmult.  Levels fine (0) to coarse (n_levels - 1), mfs[l] / coefs[l] the level's handle and
- * merged metric, transfers[l] between level l and l + 1 (n_levels - 1 of them).  At create every level gets its inverse diagonal
+ * merged metric, transfers[l] between level l and l + 1 (n_levels - 1 of them; p-transfers and geometric transfers in any mix, e.g.
+ * step-75's p = 4, 2, 1 on the fine cells, then p = 1 on cells / 2, cells / 4).  At create every level gets its inverse diagonal
  * (bp5_compute_diagonal) and a Chebyshev-Jacobi polynomial (bp5_chebyshev_create: smoother_degree on [max_used / smoothing_range,
  * max_used]; the coarsest level: coarse_degree on [max_used / coarse_range, max_used], a fixed polynomial, so the cycle is a fixed
  * symmetric linear operator as CG needs).  vmult (dst = V src, dst's prior content ignored), level l from x_l = 0:

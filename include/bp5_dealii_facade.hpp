@@ -682,6 +682,14 @@ public:
     clear();
     check(bp5_mg_transfer_create(fine.handle(), coarse.handle(), &t));
   }
+  // == reinit_geometric_transfer: fine and coarse of one degree (1..4) on a 2:1 pair of meshes; parent_cell / child per fine cell from
+  // bp5_mesh_parent_cells (include/bp5.h: bp5_mg_transfer_create_geometric)
+  template <typename MatrixType>
+  void reinit_geometric_transfer(const MatrixType &fine, const MatrixType &coarse, const uint32_t *parent_cell, const uint8_t *child)
+  {
+    clear();
+    check(bp5_mg_transfer_create_geometric(fine.handle(), coarse.handle(), parent_cell, child, &t));
+  }
   void prolongate_and_add(double *dst_fine, const double *src_coarse) const { check(bp5_mg_transfer_prolongate_add(t, dst_fine, const_cast<double *>(src_coarse))); }
   void restrict_and_add(double *dst_coarse, const double *src_fine) const { check(bp5_mg_transfer_restrict_add(t, dst_coarse, const_cast<double *>(src_fine))); }
   void clear()
@@ -695,8 +703,10 @@ private:
   bp5_mg_transfer *t = nullptr;
 };
 // == PreconditionMG<dim, VectorType, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a Chebyshev
-// coarse solver (step-37), coarsening in the polynomial degree (include/bp5.h: bp5_mg_*).  levels: the library's own operators, fine to
-// coarse, degrees p, max(1, p / 2), ..., on the same cells
+// coarse solver (step-37), coarsening in the polynomial degree and then in the mesh (include/bp5.h: bp5_mg_*).  levels: the library's own
+// operators, fine to coarse, degrees p, max(1, p / 2), ..., 1 on the same cells, then optionally degree-1 operators on 2:1 coarser meshes.
+// The levels carry no mesh: the pair (l, l + 1) gets the geometric transfer when AdditionalData::parent_cells[l] is given (with child[l],
+// from bp5_mesh_parent_cells), the p-transfer otherwise
 class PreconditionMG {
 public:
   struct AdditionalData {
@@ -707,6 +717,8 @@ public:
     double coarse_range = 1000.;
     unsigned int coarse_eig_cg_n_iterations = 30;
     std::vector<const uint64_t *> start_ids_host; // per level: bp5_mesh_view.global_ids_host (empty: the local index)
+    std::vector<const uint32_t *> parent_cells;   // per level pair l: the parent map of an h-pair (bp5_mesh_parent_cells), nullptr for a p-pair
+    std::vector<const uint8_t *> child;           // ... and the child codes
   };
   PreconditionMG() = default;
   PreconditionMG(const PreconditionMG &) = delete;
@@ -727,7 +739,11 @@ public:
     std::vector<bp5_mg_transfer *> th;
     for (int l = 0; l + 1 < n; ++l) {
       transfers[l].reset(new MGTwoLevelTransfer);
-      transfers[l]->reinit(*levels[l], *levels[l + 1]);
+      if (l < (int)data.parent_cells.size() && data.parent_cells[l]) {
+        if (l >= (int)data.child.size() || !data.child[l]) throw std::runtime_error("PreconditionMG: parent_cells[l] given without child[l]");
+        transfers[l]->reinit_geometric_transfer(*levels[l], *levels[l + 1], data.parent_cells[l], data.child[l]);
+      } else
+        transfers[l]->reinit(*levels[l], *levels[l + 1]);
       th.push_back(transfers[l]->handle());
     }
     bp5_mg_params prm;

@@ -9,9 +9,16 @@
           included; bytes per fine DoF in the row)
   solve   iterations and time to solution (tolerance 1e-8 ||b||) of MG-PCG for coarse Chebyshev degrees 30 and 60 (default)
 
+With --h-levels N | max (the hybrid hierarchy: the p-levels, then up to N geometric levels at degree 1 on 2:1 coarser meshes,
+make_mg_hierarchy(h_levels=...)) the same legs run on that hierarchy, and
+  setup   also reports each level's cells
+  cycle   also times the first geometric transfer and reads mg_geo_prolongate_kernel / mg_geo_restrict_kernel from the kernel statistics
+  solve   runs coarse degrees 10, 20, 30 and 60 on the hybrid hierarchy, and the p-only default (coarse degree 60) beside them
+--degree sets the fine degree (default 4), e.g. --degree 1 --cells 256 256 256 --h-levels max against --h-levels 0 (one level).
+
 Driver (default): runs every leg in a fresh child process under `timeout -k 10 <limit>` and stops at the first leg that fails; one JSON
 line per leg on stdout, all of them in <out>/bench_multigrid.json.
-  python tools/bench_multigrid.py [--cells 116 116 120] [--out bench_out]
+  python tools/bench_multigrid.py [--cells 116 116 120] [--degree 4] [--h-levels N|max] [--out bench_out]
 """
 import argparse
 import json
@@ -26,10 +33,10 @@ sys.path.insert(0, ROOT)
 LEGS = {"setup": 240, "cycle": 300, "solve": 420}
 
 
-def _hierarchy(pkg, cells):
-    mesh = pkg.BrickMesh(4, cells, h=1.0 / cells[0], cell_block=(4, 4, 4), dof_numbering=1, cell_block_order=1)
+def _hierarchy(pkg, cells, degree=4, h_levels=None):
+    mesh = pkg.BrickMesh(degree, cells, h=1.0 / cells[0], cell_block=(4, 4, 4), dof_numbering=1, cell_block_order=1)
     op = pkg.PoissonOperator(mesh, pkg.QUAD_GAUSS, pkg.COEF_STEP64)
-    ops = pkg.make_mg_hierarchy(op)
+    ops = pkg.make_mg_hierarchy(op) if h_levels is None else pkg.make_mg_hierarchy(op, h_levels=h_levels)
     for o in ops:
         o.mf_data.set_apply_variant(56)
     return ops
@@ -55,17 +62,28 @@ def transfer_bytes(nf, nc, n_cells, n_fine, n_coarse):
             "mg_combine_kernel": n_cells * 12 * c3 + 12 * n_coarse}
 
 
-def leg(name, cells):
+def geo_transfer_bytes(n, n_cells, n_fine, n_coarse):
+    """the same for a geometric transfer at degree n - 1 (per fine cell: parent word, index stream, writer mask, slots; the parents' index
+    lists counted once per coarse cell)"""
+    n3, words = n ** 3, (n ** 3 + 31) // 32
+    return {"mg_geo_prolongate_kernel": 16 * n_fine + n_cells * (4 + 4 * n3 + 4 * words) + (n_cells // 8) * 4 * n3 + 8 * n_coarse,
+            "mg_geo_restrict_kernel": 24 * n_fine + n_cells * (4 + 4 * n3 + 8 * n3),
+            "mg_combine_kernel": n_cells * 12 * n3 + 12 * n_coarse}
+
+
+def leg(name, cells, degree=4, h_levels=None):
     import torch
     import bp5_pkg
     pkg = bp5_pkg.load()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ops = _hierarchy(pkg, cells)
+    ops = _hierarchy(pkg, cells, degree, h_levels)
     fine = ops[0]
     n = fine.mf_data.n_owned
     out = {"leg": name, "cells": list(cells), "n_dofs": int(fine.mf_data.mesh.n_global_dofs), "degrees": [o.mf_data.mesh.degree for o in ops],
            "level_dofs": [int(o.mf_data.mesh.n_global_dofs) for o in ops]}
+    if h_levels is not None:
+        out.update(h_levels=h_levels, level_cells=[list(o.mf_data.mesh.cells) for o in ops])
     if name == "setup":
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -87,26 +105,43 @@ def leg(name, cells):
             out[f"apply_ms_p{ops[l].mf_data.mesh.degree}"] = _timed(torch, lambda: ops[l].vmult(dst, src), reps)
         out["v_cycle_ms"] = cyc[0]
         out["level_ms"] = [cyc[l] - (cyc[l + 1] if l + 1 < len(cyc) else 0.0) for l in range(len(cyc))]
-        tr = mgs[0].transfers[0]
-        xf, xc = fine.initialize_dof_vector(), ops[1].initialize_dof_vector()
-        out["prolongate_ms"] = _timed(torch, lambda: tr.prolongate_and_add(xf, xc), reps)
-        out["restrict_ms"] = _timed(torch, lambda: tr.restrict_and_add(xc, b), reps)
-        out["transfer_bytes"] = transfer_bytes(5, 3, fine.mf_data.mesh.n_cells, n, ops[1].mf_data.n_owned)
+        if len(ops) > 1 and not mgs[0].transfers[0].geometric:
+            tr = mgs[0].transfers[0]
+            nf_, nc_ = ops[0].mf_data.mesh.degree + 1, ops[1].mf_data.mesh.degree + 1
+            xf, xc = fine.initialize_dof_vector(), ops[1].initialize_dof_vector()
+            out["prolongate_ms"] = _timed(torch, lambda: tr.prolongate_and_add(xf, xc), reps)
+            out["restrict_ms"] = _timed(torch, lambda: tr.restrict_and_add(xc, b), reps)
+            out["transfer_bytes"] = transfer_bytes(nf_, nc_, fine.mf_data.mesh.n_cells, n, ops[1].mf_data.n_owned)
+            out["transfer_pair"] = [nf_, nc_]
+        geo = [l for l, t in enumerate(mgs[0].transfers) if t.geometric]
+        if geo:   # the finest geometric transfer
+            l = geo[0]
+            tr, fo, co = mgs[0].transfers[l], ops[l], ops[l + 1]
+            xf, xc, bf = fo.initialize_dof_vector(), co.initialize_dof_vector(), fo.initialize_dof_vector()
+            bf[:fo.mf_data.n_owned] = 1.0
+            out["geo_level"] = l
+            out["geo_prolongate_ms"] = _timed(torch, lambda: tr.prolongate_and_add(xf, xc), reps)
+            out["geo_restrict_ms"] = _timed(torch, lambda: tr.restrict_and_add(xc, bf), reps)
+            out["geo_transfer_bytes"] = geo_transfer_bytes(fo.mf_data.mesh.degree + 1, fo.mf_data.mesh.n_cells, fo.mf_data.n_owned, co.mf_data.n_owned)
+            out["geo_n_fine_dofs"] = int(fo.mf_data.mesh.n_global_dofs)
     elif name == "solve":
         b = fine.assemble_rhs()
         tol = 1e-8 * float(torch.linalg.norm(b[:n]))
         rows = {}
-        for cdeg in (30, 60):
+        runs = [("mg_pcg_coarse%d", c, ops) for c in ((30, 60) if h_levels is None else (10, 20, 30, 60))]
+        if h_levels is not None:   # the p-only default beside the hybrid rows
+            runs.append(("p_only_mg_pcg_coarse%d", 60, ops[:len(pkg.mg_coarse_degrees(degree))]))
+        for key, cdeg, lops in runs:
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            mg = pkg.PreconditionMG(ops, pkg.PreconditionMG.AdditionalData(coarse_degree=cdeg))
+            mg = pkg.PreconditionMG(lops, pkg.PreconditionMG.AdditionalData(coarse_degree=cdeg))
             torch.cuda.synchronize()
             setup_ms = (time.perf_counter() - t1) * 1e3
             for rep in range(2):
                 ctl = pkg.SolverControl(500, tol)
                 x = fine.initialize_dof_vector()
                 pkg.SolverCG(ctl).solve(fine, x, b, mg)
-            rows[f"mg_pcg_coarse{cdeg}"] = dict(iterations=ctl.last_step(), solve_ms=ctl.solve_ms, setup_ms=setup_ms, residual=ctl.last_value(),
+            rows[key % cdeg] = dict(n_levels=len(lops), iterations=ctl.last_step(), solve_ms=ctl.solve_ms, setup_ms=setup_ms, residual=ctl.last_value(),
                                                 converged=ctl.last_value() <= tol, ms_per_iteration=ctl.solve_ms / max(ctl.last_step(), 1),
                                                 solution_l2=fine.l2_norm_solution(x))
             mg.clear()
@@ -115,15 +150,21 @@ def leg(name, cells):
 
 
 def kernel_rows(stats_csv, legrow):
-    """the fine transfer's kernels (mg_*<5, 3...>, combine on the p = 2 level) of a rocprofv3 kernel_stats.csv: calls, average time, TB/s"""
+    """the fine transfer's kernels (mg_*<5, 3...>, combine on the p = 2 level) of a rocprofv3 kernel_stats.csv: calls, average time, TB/s;
+    with h-levels also the geometric kernels (mg_geo_*: every level's launches averaged)"""
     import csv
-    nbytes = legrow["transfer_bytes"]
+    nbytes = legrow.get("transfer_bytes", {})
     n_f = legrow["n_dofs"]
     rows = {}
     for r in csv.DictReader(open(stats_csv)):
         name, avg = r["Name"], float(r["AverageNs"]) * 1e-9
+        for k, nb in legrow.get("geo_transfer_bytes", {}).items():
+            if k.startswith("mg_geo_") and k in name:
+                key = name[name.index(k):].split("(")[0].replace(" ", "")
+                rows[key] = dict(calls=int(r["Calls"]), avg_us=avg * 1e6, bytes_per_fine_dof_finest=nb / legrow["geo_n_fine_dofs"],
+                                 note="every geometric level's launches averaged (no bandwidth: the levels differ in size); geo_*_ms time the finest")
         for k, nb in nbytes.items():
-            fine_one = ("<5, 3" in name) if k != "mg_combine_kernel" else True
+            fine_one = (f"<{legrow['transfer_pair'][0]}, {legrow['transfer_pair'][1]}" in name) if k != "mg_combine_kernel" else True
             if k in name and fine_one:
                 key = k + ("<5,3,true>" if k == "mg_restrict_kernel" and "true" in name else "<5,3,false>" if k == "mg_restrict_kernel" else
                            "<5,3>" if k == "mg_prolongate_kernel" else ("<true>" if "true" in name else "<false>"))
@@ -136,16 +177,21 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--leg", choices=sorted(LEGS), help="run one leg in this process (the driver's child)")
     ap.add_argument("--cells", type=int, nargs=3, default=[116, 116, 120])
+    ap.add_argument("--degree", type=int, default=4)
+    ap.add_argument("--h-levels", default=None, help="N or max: the hybrid hierarchy (default: the p-levels only, today's legs)")
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out"))
     args = ap.parse_args()
+    h_levels = None if args.h_levels is None else (args.h_levels if args.h_levels == "max" else int(args.h_levels))
     if args.leg:
-        print(json.dumps(leg(args.leg, tuple(args.cells))), flush=True)
+        print(json.dumps(leg(args.leg, tuple(args.cells), args.degree, h_levels)), flush=True)
         return 0
     os.makedirs(args.out, exist_ok=True)
     results = []
     prof_dir = os.path.join(os.path.abspath(args.out), "bench_multigrid_prof")
     for name, limit in LEGS.items():
-        leg_cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--cells"] + [str(c) for c in args.cells]
+        leg_cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--degree", str(args.degree), "--cells"] + [str(c) for c in args.cells]
+        if h_levels is not None:
+            leg_cmd += ["--h-levels", str(h_levels)]
         profiled = name == "cycle" and shutil.which("rocprofv3") is not None
         if profiled:   # kernel statistics only: no counter collection, no other tracing
             leg_cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof_dir, "-o", "cycle", "--"] + leg_cmd
@@ -160,7 +206,8 @@ def main():
             row["kernel_stats"] = kernel_rows(stats[0], row) if stats else "no kernel_stats.csv written"
         print(json.dumps(row), flush=True)
         results.append(row)
-        with open(os.path.join(args.out, "bench_multigrid.json"), "w") as f:
+        tag = "" if h_levels is None else f"_p{args.degree}_h{h_levels}"
+        with open(os.path.join(args.out, f"bench_multigrid{tag}.json"), "w") as f:
             json.dump(results, f, indent=1)
     return 0
 
