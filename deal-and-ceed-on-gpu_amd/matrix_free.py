@@ -599,8 +599,9 @@ def mg_coarse_degrees(degree):
 
 
 def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
-    """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same cells, block order and
-    numbering scheme, coefficient, quadrature, device, stream and communicator at degrees p // 2, ..., 1; then, at degree 1, up to
+    """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same operator class, cells, block order
+    and numbering scheme, coefficient, quadrature, geometry mode, device, stream and communicator at degrees p // 2, ..., 1; then, at
+    degree 1, up to
     h_levels geometric levels (an int, or "max": as many as the mesh allows), each on BrickMesh.coarsen(min_cells) of the one above
     (half the cells per direction, twice h, the same domain), stopping where coarsen returns None.  h_levels = 0 (default): the p-levels
     only.  Returns [fine_op, ...]."""
@@ -611,8 +612,10 @@ def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
     ops = [fine_op]
     stream = _torch().cuda.current_stream(mf.device).cuda_stream
 
+    geometry = dict(geometry=fine_op.geometry) if fine_op.geometry else {}     # (HelmholtzOperator: six-plane geometry only)
+
     def level(mesh):
-        return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream)
+        return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream, **geometry)
 
     for p in mg_coarse_degrees(m.degree)[1:]:
         ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,

@@ -1,12 +1,11 @@
 """numpy reference of the geometric (h) multigrid transfer and the hybrid p-then-h V-cycle (include/bp5.h:
 bp5_mg_transfer_create_geometric, bp5_mg_*), on the oracle's lexicographic BrickMesh.  The 1-D factor of a direction holds M_s[a][b] =
 phi_b(xi_a / 2 + s / 2) in rows p (2c + s) + a, columns p c + b; the global prolongation is the Kronecker product of the three factors,
-applied by multigrid_ref.Transfer's einsum sweeps.  The V-cycle is multigrid_ref.VCycle's recursion over multigrid_ref.Level /
+applied by multigrid_ref.Transfer's sweeps.  The V-cycle is multigrid_ref.VCycle's recursion over multigrid_ref.Level /
 Transfer, with the h-levels on O.Problem(..., h = 2^k h)."""
 import numpy as np
 
 import bp5_oracle as O
-import chebyshev_ref as R
 import multigrid_ref as G
 
 
@@ -76,16 +75,10 @@ def hierarchy(p, cells, h_levels="max", min_cells=4, n_ranks=1):
 
 
 class Level(G.Level):
-    """multigrid_ref.Level on a mesh of cell size h"""
+    """multigrid_ref.Level on a mesh of cell size h (Poisson or Helmholtz operator)"""
 
-    def __init__(self, p, cells, h, quadrature, deform_amp, kappa, degree, smoothing_range, eig_its):
-        self.pr = O.Problem(p, cells, quadrature, h=h, deform_amp=deform_amp, kappa=kappa)
-        m = self.pr.mesh
-        self.inv = 1.0 / O.operator_diagonal(m, self.pr.coef, self.pr.N, self.pr.D)
-        v = R.start_vector(np.arange(m.n_dofs), m.constrained)
-        self.min_est, self.max_est, self.cg_its = R.lanczos_estimate(self.pr.vmult, self.inv, v, eig_its)
-        self.min_used, self.max_used = R.bounds(self.min_est, self.max_est, smoothing_range)
-        self.degree = degree
+    def __init__(self, p, cells, h, quadrature, deform_amp, kappa, degree, smoothing_range, eig_its, operator="poisson"):
+        super().__init__(p, cells, quadrature, deform_amp, kappa, degree, smoothing_range, eig_its, h=h, operator=operator)
 
 
 class HybridVCycle(G.VCycle):
@@ -94,12 +87,13 @@ class HybridVCycle(G.VCycle):
 
     def __init__(self, p, cells, quadrature=O.QUAD_GAUSS, deform_amp=0.0, kappa=O.kappa_none, h_levels="max", min_cells=4,
                  smoother_degree=4, smoothing_range=20.0, eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0,
-                 coarse_eig_cg_n_iterations=30):
+                 coarse_eig_cg_n_iterations=30, operator="poisson"):
         self.spec = hierarchy(p, cells, h_levels, min_cells)
         self.levels = []
         for lev, (q, c, h) in enumerate(self.spec):
             last = lev + 1 == len(self.spec)
             self.levels.append(Level(q, c, h, quadrature, deform_amp, kappa, coarse_degree if last else smoother_degree,
-                                     coarse_range if last else smoothing_range, coarse_eig_cg_n_iterations if last else eig_cg_n_iterations))
+                                     coarse_range if last else smoothing_range, coarse_eig_cg_n_iterations if last else eig_cg_n_iterations,
+                                     operator=operator))
         self.transfers = [G.Transfer(fc, pf, pc) if pf != pc else GeometricTransfer(cc, pc)
                           for (pf, fc, _), (pc, cc, _) in zip(self.spec[:-1], self.spec[1:])]

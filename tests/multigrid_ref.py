@@ -1,6 +1,6 @@
 """numpy reference of the p-multigrid transfer and V-cycle (include/bp5.h: bp5_mg_transfer_*, bp5_mg_*), on the oracle's lexicographic
 BrickMesh.  There the global prolongation P is the Kronecker product of three banded 1-D matrices (M repeated cell by cell along each
-direction), applied by three einsum sweeps and never assembled.  The V-cycle reuses chebyshev_ref.py.  Shared by the CPU and GPU tests of
+direction), applied by three sweeps (one matrix product per direction) and never assembled.  The V-cycle reuses chebyshev_ref.py.  Shared by the CPU and GPU tests of
 the multigrid preconditioner and by the loopback worker."""
 import numpy as np
 
@@ -58,26 +58,86 @@ class Transfer:
         bc[0], bc[-1], bc[:, 0], bc[:, -1], bc[:, :, 0], bc[:, :, -1] = True, True, True, True, True, True
         self.boundary_c = bc.ravel()
 
+    @staticmethod
+    def _sweeps(u, Px, Py, Pz):
+        """(Pz x Py x Px) u on u[z][y][x], one direction at a time (x, y, z): three matrix products, no intermediate larger than the
+        result, so the 1.4e8-DoF meshes of the full-size tests fit too"""
+        u = u @ Px.T
+        u = np.matmul(Py, u)
+        return np.tensordot(Pz, u, axes=(1, 0))
+
     def prolongate(self, ec):
         u = np.where(self.boundary_c, 0.0, ec).reshape(self.shape_c)
         Px, Py, Pz = self.P1
-        return np.einsum("xa,yb,zc,cba->zyx", Px, Py, Pz, u, optimize=True).ravel()
+        return self._sweeps(u, Px, Py, Pz).ravel()
 
     def restrict(self, rf):
         u = rf.reshape(self.shape_f)
         Px, Py, Pz = self.P1
-        r = np.einsum("xa,yb,zc,zyx->cba", Px, Py, Pz, u, optimize=True).ravel()
+        r = self._sweeps(u, Px.T, Py.T, Pz.T).ravel()
         r[self.boundary_c] = 0.0
         return r
 
 
-class Level:
-    """one level: the oracle problem, its inverse diagonal and the Chebyshev bounds of bp5_mg_create"""
+class HelmholtzProblem:
+    """O.Problem's interface for step-64's Helmholtz operator (HelmholtzOperator, BP5_OP_HELMHOLTZ): (grad v, grad u) + (v, a u), the
+    gradient term with coefficient 1 and a = coefficient(x) in the mass term.  vmult is O.apply_helmholtz_cells with the geometry
+    evaluated once: the merged metric for the gradient term, a JxW at the quadrature points for the mass term."""
 
-    def __init__(self, p, cells, quadrature, deform_amp, kappa, degree, smoothing_range, eig_its):
-        self.pr = O.Problem(p, cells, quadrature, deform_amp=deform_amp, kappa=kappa)
+    def __init__(self, p, cells, quadrature=O.QUAD_GAUSS, h=1.0, deform_amp=0.0, coefficient=O.kappa_step64):
+        self.pr = O.Problem(p, cells, quadrature, h=h, deform_amp=deform_amp, kappa=O.kappa_none)
+        self.mesh, self.N, self.D, self.w, self.coef = self.pr.mesh, self.pr.N, self.pr.D, self.pr.w, self.pr.coef
+        _, JxW, xq = O.jacobians(self.mesh, self.N, self.D, self.w)
+        n = self.mesh.n
+        self.mass = (coefficient(xq) * JxW).reshape(self.mesh.n_cells, n, n, n)
+
+    def apply_cells(self, src):
+        m, N, n = self.mesh, self.N, self.mesh.n
+        dst = O.apply_cells(m, self.coef, N, self.D, src)
+        idx = m.l2g.astype(np.int64)
+        uq = np.einsum("ck,bj,ai,...kji->...cba", N, N, N, src[idx].reshape(m.n_cells, n, n, n), optimize=True)
+        y = np.einsum("ck,bj,ai,...cba->...kji", N, N, N, self.mass * uq, optimize=True)
+        np.add.at(dst, idx.ravel(), y.reshape(-1))
+        return dst
+
+    def vmult(self, src):
+        dst = self.apply_cells(src)
+        c = self.mesh.constrained.astype(np.int64)
+        dst[c] = src[c]
+        return dst
+
+    def diagonal(self):
+        """O.operator_diagonal plus the mass term's diagonal (N * N in every direction on the a JxW plane), 1 on Dirichlet DoFs"""
+        m, NN = self.mesh, self.N * self.N
+        y = np.einsum("ck,bj,ai,...cba->...kji", NN, NN, NN, self.mass, optimize=True)
+        d = O.operator_diagonal(m, self.coef, self.N, self.D)
+        np.add.at(d, m.l2g.astype(np.int64).ravel(), y.reshape(-1))
+        d[m.constrained.astype(np.int64)] = 1.0
+        return d
+
+    def rhs(self):
+        return self.pr.rhs()
+
+
+def problem(operator, p, cells, quadrature=O.QUAD_GAUSS, h=1.0, deform_amp=0.0, kappa=O.kappa_none):
+    """(problem, diagonal): "poisson": O.Problem with kappa in the gradient term (PoissonOperator); "helmholtz": HelmholtzProblem with
+    kappa as the mass coefficient a (HelmholtzOperator: COEF_STEP64 -> O.kappa_step64, COEF_ONE -> O.kappa_none)"""
+    if operator == "poisson":
+        pr = O.Problem(p, cells, quadrature, h=h, deform_amp=deform_amp, kappa=kappa)
+        return pr, O.operator_diagonal(pr.mesh, pr.coef, pr.N, pr.D)
+    if operator == "helmholtz":
+        pr = HelmholtzProblem(p, cells, quadrature, h=h, deform_amp=deform_amp, coefficient=kappa)
+        return pr, pr.diagonal()
+    raise ValueError(f"unknown operator {operator!r}")
+
+
+class Level:
+    """one level: the oracle problem (Poisson or Helmholtz operator), its inverse diagonal and the Chebyshev bounds of bp5_mg_create"""
+
+    def __init__(self, p, cells, quadrature, deform_amp, kappa, degree, smoothing_range, eig_its, h=1.0, operator="poisson"):
+        self.pr, diag = problem(operator, p, cells, quadrature, h=h, deform_amp=deform_amp, kappa=kappa)
         m = self.pr.mesh
-        self.inv = 1.0 / O.operator_diagonal(m, self.pr.coef, self.pr.N, self.pr.D)
+        self.inv = 1.0 / diag
         v = R.start_vector(np.arange(m.n_dofs), m.constrained)
         self.min_est, self.max_est, self.cg_its = R.lanczos_estimate(self.pr.vmult, self.inv, v, eig_its)
         self.min_used, self.max_used = R.bounds(self.min_est, self.max_est, smoothing_range)
@@ -97,13 +157,14 @@ class VCycle:
     """PreconditionMG of bp5_mg_create with its default parameters (or the given ones)"""
 
     def __init__(self, p, cells, quadrature=O.QUAD_GAUSS, deform_amp=0.0, kappa=O.kappa_none, smoother_degree=4, smoothing_range=20.0,
-                 eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0, coarse_eig_cg_n_iterations=30):
+                 eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0, coarse_eig_cg_n_iterations=30, operator="poisson"):
         ds = degrees(p)
         self.levels = []
         for lev, q in enumerate(ds):
             last = lev + 1 == len(ds)
             self.levels.append(Level(q, cells, quadrature, deform_amp, kappa, coarse_degree if last else smoother_degree,
-                                     coarse_range if last else smoothing_range, coarse_eig_cg_n_iterations if last else eig_cg_n_iterations))
+                                     coarse_range if last else smoothing_range, coarse_eig_cg_n_iterations if last else eig_cg_n_iterations,
+                                     operator=operator))
         self.transfers = [Transfer(cells, f, c) for f, c in zip(ds[:-1], ds[1:])]
 
     def level(self, lev, b):

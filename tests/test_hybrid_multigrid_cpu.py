@@ -217,3 +217,32 @@ def test_hybrid_v_cycle_is_symmetric():
     c = V.levels[0].pr.mesh.constrained.astype(np.int64)
     u[c] = v[c] = 0.0
     assert abs(u @ V.vmult(v) - v @ V.vmult(u)) < 1e-12 * abs(u @ V.vmult(u))
+
+
+def test_geometric_sweeps_equal_the_assembled_kronecker_product():
+    T = H.GeometricTransfer((2, 1, 3), 2)
+    Px, Py, Pz = T.P1
+    P = np.kron(Pz, np.kron(Py, Px))
+    rng = np.random.default_rng(10)
+    ec, rf = rng.uniform(-1, 1, P.shape[1]), rng.uniform(-1, 1, P.shape[0])
+    z = np.where(T.boundary_c, 0.0, 1.0)
+    assert np.abs(T.prolongate(ec) - P @ (z * ec)).max() < 1e-14
+    assert np.abs(T.restrict(rf) - z * (P.T @ rf)).max() < 1e-13
+
+
+def test_hybrid_helmholtz_levels_carry_the_mass_term_of_their_mesh():
+    """operator="helmholtz": every level, p and h, is step-64's Helmholtz operator on its own mesh (cell size 2^k h: the mass term scales
+    as h^3, the gradient term as h), and the hybrid MG-PCG converges in a few iterations"""
+    import multigrid_ref as G
+    V = H.HybridVCycle(2, (8, 8, 8), deform_amp=AMP, kappa=O.kappa_step64, coarse_degree=10, operator="helmholtz")
+    assert [(q, c) for q, c, _ in V.spec] == [(2, (8, 8, 8)), (1, (8, 8, 8)), (1, (4, 4, 4))]
+    for (q, c, h), L in zip(V.spec, V.levels):
+        ref = G.HelmholtzProblem(q, c, h=h, deform_amp=AMP)
+        s = O.deterministic_src(ref.mesh.n_dofs, ref.mesh.constrained, seed=5)
+        assert np.linalg.norm(L.A(s) - ref.vmult(s)) < 1e-13 * np.linalg.norm(ref.vmult(s))
+        assert np.array_equal(L.inv, 1.0 / ref.diagonal())
+    A = V.levels[0]
+    b = A.pr.rhs()
+    tol = 1e-8 * np.linalg.norm(b)
+    x, k, res = R.pcg(A.A, V.vmult, b, 100, tol=tol)
+    assert res <= tol and k <= 12, k

@@ -107,3 +107,54 @@ def test_v_cycle_is_symmetric():
     c = V.levels[0].pr.mesh.constrained.astype(np.int64)
     u[c] = v[c] = 0.0
     assert abs(u @ V.vmult(v) - v @ V.vmult(u)) < 1e-12 * abs(u @ V.vmult(u))
+
+
+@pytest.mark.parametrize("pf,cells", [(4, (3, 2, 1)), (2, (1, 3, 2))])
+def test_direction_sweeps_equal_the_assembled_kronecker_product(pf, cells):
+    """Transfer applies P = Pz x Py x Px one direction at a time (the full-size GPU tests rely on it at 1.4e8 DoFs): against np.kron"""
+    T = G.Transfer(cells, pf)
+    Px, Py, Pz = T.P1
+    P = np.kron(Pz, np.kron(Py, Px))
+    rng = np.random.default_rng(9)
+    ec, rf = rng.uniform(-1, 1, P.shape[1]), rng.uniform(-1, 1, P.shape[0])
+    z = np.where(T.boundary_c, 0.0, 1.0)
+    assert np.abs(T.prolongate(ec) - P @ (z * ec)).max() < 1e-14
+    assert np.abs(T.restrict(rf) - z * (P.T @ rf)).max() < 1e-13
+
+
+@pytest.mark.parametrize("p,quad,amp", [(2, 0, 0.05), (3, 1, 0.0), (4, 0, 0.04)])
+def test_helmholtz_problem_is_the_oracle_helmholtz_operator(p, quad, amp):
+    """HelmholtzProblem (the Helmholtz levels of the multigrid reference): vmult is O.apply_helmholtz_cells with the Dirichlet rows of
+    PoissonOperator.vmult, and its diagonal is (A e_g)_g"""
+    cells = (2, 2, 1)
+    pr = G.HelmholtzProblem(p, cells, quad, h=0.5, deform_amp=amp)
+    m = pr.mesh
+    s = O.deterministic_src(m.n_dofs, seed=3)
+    ref = O.apply_helmholtz_cells(m, pr.N, pr.D, pr.w, s)
+    c = m.constrained.astype(np.int64)
+    ref[c] = s[c]
+    assert np.linalg.norm(pr.vmult(s) - ref) < 1e-13 * np.linalg.norm(ref)
+    d_ref = np.array([pr.vmult(np.eye(1, m.n_dofs, g).ravel())[g] for g in range(m.n_dofs)])
+    assert np.abs(pr.diagonal() - d_ref).max() < 1e-13 * np.abs(d_ref).max()
+    # the mass term is there: the Poisson diagonal is smaller on every free row
+    free = np.ones(m.n_dofs, bool)
+    free[c] = False
+    po, d_po = G.problem("poisson", p, cells, quad, h=0.5, deform_amp=amp)
+    assert (d_ref[free] > d_po[free]).all()
+
+
+def test_helmholtz_v_cycle_is_symmetric_and_converges():
+    V = G.VCycle(4, (3, 3, 3), deform_amp=0.05, kappa=O.kappa_step64, operator="helmholtz")
+    assert all(isinstance(L.pr, G.HelmholtzProblem) for L in V.levels)
+    A = V.levels[0]
+    n = A.pr.mesh.n_dofs
+    rng = np.random.default_rng(4)
+    u, v = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n)
+    c = A.pr.mesh.constrained.astype(np.int64)
+    u[c] = v[c] = 0.0
+    assert abs(u @ V.vmult(v) - v @ V.vmult(u)) < 1e-12 * abs(u @ V.vmult(u))
+    b = A.pr.rhs()
+    tol = 1e-8 * np.linalg.norm(b)
+    x, k, res = R.pcg(A.A, V.vmult, b, 100, tol=tol)
+    assert res <= tol and 3 <= k <= 9, k
+    assert np.linalg.norm(b - A.A(x)) <= 1.01 * tol
