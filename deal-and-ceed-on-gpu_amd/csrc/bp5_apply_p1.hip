@@ -1,3 +1,3 @@
 // fused-operator kernels of degree 1: instantiates the variant dispatch of bp5_device.hpp for this degree
 #include "bp5_device.hpp"
-template int apply_degree_impl<1>(bp5_mf *, const double *, const double *, double *, uint32_t, uint32_t, bool);
+template int apply_degree_impl<1>(bp5_mf *, ApplyCall &, const double *, const double *, double *);

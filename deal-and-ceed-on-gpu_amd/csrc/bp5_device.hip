@@ -328,7 +328,7 @@ extern "C" int bp5_mf_block_plan_carry(bp5_mf *mf, uint32_t *n_faces, uint32_t *
   *n_faces = 0;
   for (uint32_t len : dp->h_carry_len) *n_faces += len != 0;
   *n_shared = dp->n_shared;
-  *n_shared_last_launch = dp->cr_active ? dp->cr_active->n_shared : dp->n_shared;
+  *n_shared_last_launch = dp->cr_last_launch ? dp->cr_last_launch->n_shared : dp->n_shared;
   return BP5_OK;
 }
 extern "C" int bp5_mf_get_apply_variant(bp5_mf *mf, int *effective)
@@ -898,34 +898,39 @@ int get_plan(bp5_mf *mf, int cpt, TeamPlan &tp, bp5_mf::DevPlan **dpo)
 
 // fixed grid of the fused solver's combine pass: k workgroups per CU (BP5_TUNE_COMBINE_WG_PER_CU, default 16: profiles/r4 h_*; each
 // workgroup walks its tiles two at a time), never more than tiles or free dot-product columns
-static uint32_t combine_grid(bp5_mf *mf, uint32_t tiles)
+int device_cus(bp5_mf *mf)
 {
-  const uint32_t cols = (uint32_t)PARTIAL_STRIDE - mf->fuse.n_cols - 1024u;
+  if (!mf->n_cus) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, mf->device) == hipSuccess) mf->n_cus = prop.multiProcessorCount;
+  }
+  return mf->n_cus;
+}
+static uint32_t combine_grid(bp5_mf *mf, uint32_t tiles, uint32_t cols_used)
+{
+  const uint32_t cols = (uint32_t)PARTIAL_STRIDE - cols_used - 1024u;
   uint32_t grid = std::min<uint32_t>(tiles, cols);
   const int k = mf->tune[BP5_TUNE_COMBINE_WG_PER_CU];
-  if (k > 0) {
-    if (!mf->n_cus) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, mf->device) == hipSuccess) mf->n_cus = prop.multiProcessorCount;
-    }
-    grid = std::min<uint32_t>(grid, (uint32_t)k * (uint32_t)std::max(mf->n_cus, 1));
-  }
+  if (k > 0) grid = std::min<uint32_t>(grid, (uint32_t)k * (uint32_t)std::max(device_cus(mf), 1));
   return std::max<uint32_t>(grid, 1u);
 }
-int launch_combine(bp5_mf *mf, bp5_mf::DevPlan *dp, double *dst, bool set, int window)
+int launch_combine(bp5_mf *mf, ApplyCall &call, bp5_mf::DevPlan *dp, double *dst, bool set, int window, bool on_comm_stream)
 {
   if (!dp->n_shared) return BP5_OK;
+  const hipStream_t stream = on_comm_stream ? mf->comm_stream : mf->stream;
+  FuseState *const fuse = call.fuse;
+  const bool runs = dp->cr_tile && !call.csr_combine; // the run-length form of the pass (else: the per-DoF CSR kernel)
   // the tables of the block launch this pass follows: the plan's own, or (face carry) its partition's without the carried faces
   bp5_mf::DevPlan::CombineTables own;
   own.start = dp->cr_start; own.dof0 = dp->cr_dof0; own.soff = dp->cr_soff; own.slots = dp->cr_slots; own.tile = dp->cr_tile;
   own.n_shared = dp->n_shared; own.n_shared_owned = dp->n_shared_owned;
-  const bp5_mf::DevPlan::CombineTables &ct = (dp->cr_active && dp->cr_tile && !mf->combine_csr) ? *dp->cr_active : own;
+  const bp5_mf::DevPlan::CombineTables &ct = (call.combine_tables && runs) ? *call.combine_tables : own;
   if (!ct.n_shared) return BP5_OK;
-  if (mf->fuse.on && !(set && dp->cr_tile && !mf->combine_csr)) return fail(BP5_ERR_INVALID, "fused dot products need the run-length combine pass in overwrite mode");
-  if (window != COMBINE_ALL && !(dp->cr_tile && !mf->combine_csr)) return fail(BP5_ERR_INVALID, "combine windows need the run-length combine pass");
-  if (mf->prof_mark && window != COMBINE_GHOST) { HIP_TRY(hipEventRecord(mf->prof_mark, mf->stream)); mf->prof_mark = nullptr; }
+  if (fuse && !(set && runs)) return fail(BP5_ERR_INVALID, "fused dot products need the run-length combine pass in overwrite mode");
+  if (window != COMBINE_ALL && !runs) return fail(BP5_ERR_INVALID, "combine windows need the run-length combine pass");
+  if (call.mark_event && !call.mark_recorded && window != COMBINE_GHOST) { HIP_TRY(hipEventRecord(call.mark_event, stream)); call.mark_recorded = true; }
   const dim3 cg((dp->n_shared + 255) / 256); // CSR kernel
-  if (dp->cr_tile && !mf->combine_csr) {
+  if (runs) {
     CombineRuns cr{};
     cr.start = ct.start; cr.dof0 = ct.dof0; cr.soff = ct.soff; cr.slots = ct.slots; cr.tile_run = ct.tile;
     cr.n_shared = ct.n_shared;
@@ -937,49 +942,49 @@ int launch_combine(bp5_mf *mf, bp5_mf::DevPlan *dp, double *dst, bool set, int w
     cr.dof_hi = window == COMBINE_OWNED ? mf->n_owned : 0xffffffffu;
     if (window == COMBINE_GHOST_THEN_OWNED) {
       // owned rows exactly as COMBINE_OWNED (tiles, columns), preceded in the SAME launch by one workgroup per ghost tile that signals
-      if (!(mf->fuse.on && set && mf->d_signal)) return fail(BP5_ERR_INVALID, "ghost-rows-first combine launch: fused overwrite launches with a signal word only");
+      if (!(fuse && set && mf->d_signal)) return fail(BP5_ERR_INVALID, "ghost-rows-first combine launch: fused overwrite launches with a signal word only");
       cr.tile0 = 0u;
       cr.dof_lo = 0u; cr.dof_hi = mf->n_owned;
       cr.ghost_tile0 = ct.n_shared_owned / COMBINE_TILE;
       cr.ghost_blocks = all_tiles - cr.ghost_tile0;
       cr.signal = mf->d_signal;
       const uint32_t owned_tiles = (ct.n_shared_owned + COMBINE_TILE - 1) / COMBINE_TILE;
-      cr.cg_p = mf->fuse.p; cr.cg_r = mf->fuse.r; cr.dot_partials = mf->d_partials; cr.dot_col0 = mf->fuse.n_cols;
+      cr.cg_p = fuse->p; cr.cg_r = fuse->r; cr.dot_partials = mf->d_partials; cr.dot_col0 = fuse->n_cols;
       cr.n_owned = mf->n_owned; cr.n_tiles = owned_tiles; cr.cg_state = mf->d_st;
-      if (mf->fuse.n_cols + 1024u + 8u > (uint32_t)PARTIAL_STRIDE) return fail(BP5_ERR_UNSUPPORTED, "no partial-sum columns left for the combine pass");
-      const uint32_t grid = combine_grid(mf, owned_tiles);
-      if (ct.n_shared >= (8u << 20)) hipLaunchKernelGGL((combine_runs_kernel<false, true, true>), dim3(grid + cr.ghost_blocks), dim3(256), 0, mf->stream, cr, dp->partial, dst);
-      else hipLaunchKernelGGL((combine_runs_kernel<false, true, false>), dim3(grid + cr.ghost_blocks), dim3(256), 0, mf->stream, cr, dp->partial, dst);
+      if (fuse->n_cols + 1024u + 8u > (uint32_t)PARTIAL_STRIDE) return fail(BP5_ERR_UNSUPPORTED, "no partial-sum columns left for the combine pass");
+      const uint32_t grid = combine_grid(mf, owned_tiles, fuse->n_cols);
+      if (ct.n_shared >= (8u << 20)) hipLaunchKernelGGL((combine_runs_kernel<false, true, true>), dim3(grid + cr.ghost_blocks), dim3(256), 0, stream, cr, dp->partial, dst);
+      else hipLaunchKernelGGL((combine_runs_kernel<false, true, false>), dim3(grid + cr.ghost_blocks), dim3(256), 0, stream, cr, dp->partial, dst);
       KERNEL_CHECK();
-      mf->fuse.n_cols += grid;
+      fuse->n_cols += grid;
       mf->signal_target += cr.ghost_blocks; // every ghost workgroup counts itself in once
       return BP5_OK;
     }
     if (tile1 <= cr.tile0) return BP5_OK; // no row in the window
     const dim3 cgt(tile1 - cr.tile0);
-    if (mf->fuse.on && window != COMBINE_GHOST) { // fused CG dot products over the brick-surface DoFs; columns behind the block kernel's workgroups
+    if (fuse && window != COMBINE_GHOST) { // fused CG dot products over the brick-surface DoFs; columns behind the block kernel's workgroups
       // (ghost rows never enter the dot products: their window takes the plain kernel below)
-      cr.cg_p = mf->fuse.p; cr.cg_r = mf->fuse.r; cr.dot_partials = mf->d_partials; cr.dot_col0 = mf->fuse.n_cols;
+      cr.cg_p = fuse->p; cr.cg_r = fuse->r; cr.dot_partials = mf->d_partials; cr.dot_col0 = fuse->n_cols;
       cr.n_owned = mf->n_owned; cr.n_tiles = cgt.x; cr.cg_state = mf->d_st;
-      if (mf->fuse.n_cols + 1024u + 8u > (uint32_t)PARTIAL_STRIDE) return fail(BP5_ERR_UNSUPPORTED, "no partial-sum columns left for the combine pass");
-      const uint32_t grid = combine_grid(mf, cgt.x); // (1024 columns stay free for the exchange)
+      if (fuse->n_cols + 1024u + 8u > (uint32_t)PARTIAL_STRIDE) return fail(BP5_ERR_UNSUPPORTED, "no partial-sum columns left for the combine pass");
+      const uint32_t grid = combine_grid(mf, cgt.x, fuse->n_cols); // (1024 columns stay free for the exchange)
       // pairs of consecutive ordinals pay on long passes; short ones (config 2, the strong-scaling ranks) are latency-bound
-      if (ct.n_shared >= (8u << 20)) hipLaunchKernelGGL((combine_runs_kernel<false, true, true>), dim3(grid), dim3(256), 0, mf->stream, cr, dp->partial, dst);
-      else hipLaunchKernelGGL((combine_runs_kernel<false, true, false>), dim3(grid), dim3(256), 0, mf->stream, cr, dp->partial, dst);
+      if (ct.n_shared >= (8u << 20)) hipLaunchKernelGGL((combine_runs_kernel<false, true, true>), dim3(grid), dim3(256), 0, stream, cr, dp->partial, dst);
+      else hipLaunchKernelGGL((combine_runs_kernel<false, true, false>), dim3(grid), dim3(256), 0, stream, cr, dp->partial, dst);
       KERNEL_CHECK();
-      mf->fuse.n_cols += grid;
+      fuse->n_cols += grid;
       return BP5_OK;
     }
     const bool pairs = ct.n_shared >= (8u << 20) && window != COMBINE_GHOST;
-    if (set && pairs) hipLaunchKernelGGL((combine_runs_kernel<false, false, true>), cgt, dim3(256), 0, mf->stream, cr, dp->partial, dst);
-    else if (set) hipLaunchKernelGGL((combine_runs_kernel<false, false, false>), cgt, dim3(256), 0, mf->stream, cr, dp->partial, dst);
-    else if (pairs) hipLaunchKernelGGL((combine_runs_kernel<true, false, true>), cgt, dim3(256), 0, mf->stream, cr, dp->partial, dst);
-    else hipLaunchKernelGGL((combine_runs_kernel<true, false, false>), cgt, dim3(256), 0, mf->stream, cr, dp->partial, dst);
+    if (set && pairs) hipLaunchKernelGGL((combine_runs_kernel<false, false, true>), cgt, dim3(256), 0, stream, cr, dp->partial, dst);
+    else if (set) hipLaunchKernelGGL((combine_runs_kernel<false, false, false>), cgt, dim3(256), 0, stream, cr, dp->partial, dst);
+    else if (pairs) hipLaunchKernelGGL((combine_runs_kernel<true, false, true>), cgt, dim3(256), 0, stream, cr, dp->partial, dst);
+    else hipLaunchKernelGGL((combine_runs_kernel<true, false, false>), cgt, dim3(256), 0, stream, cr, dp->partial, dst);
     KERNEL_CHECK();
     return BP5_OK;
   }
-  if (set) hipLaunchKernelGGL(combine_kernel<false>, cg, dim3(256), 0, mf->stream, dp->sh_dof, dp->sh_off, dp->sh_slot, dp->partial, dst, dp->n_shared);
-  else hipLaunchKernelGGL(combine_kernel<true>, cg, dim3(256), 0, mf->stream, dp->sh_dof, dp->sh_off, dp->sh_slot, dp->partial, dst, dp->n_shared);
+  if (set) hipLaunchKernelGGL(combine_kernel<false>, cg, dim3(256), 0, stream, dp->sh_dof, dp->sh_off, dp->sh_slot, dp->partial, dst, dp->n_shared);
+  else hipLaunchKernelGGL(combine_kernel<true>, cg, dim3(256), 0, stream, dp->sh_dof, dp->sh_off, dp->sh_slot, dp->partial, dst, dp->n_shared);
   KERNEL_CHECK();
   return BP5_OK;
 }
@@ -995,6 +1000,27 @@ bool block_aligned(const bp5_mf *mf, uint32_t c0, uint32_t c1, uint32_t *b0, uin
   *b1 = (uint32_t)(i1 - o.begin());
   return true;
 }
+// The block kernel for the cells [c0, c1) = the blocks [b0, b1) of the caller's blocking?  Decided once per handle (auto_block): the LDS of the
+// default shape fits `wg_per_cu` workgroups per CU, the plan has packed indices where the build at hand needs them, and there are bricks
+// enough for the persistent workgroups to balance.  Round 1 measured 3.6 bricks per workgroup (54^3 cells) 4 % behind the pencil kernel
+// as a bare operator; with the CG dot products fused into the write-out the block kernel is ahead there too (profiles/r2: 0.439 vs
+// 0.446 ms per iteration), so the bar dropped to 3 bricks per workgroup -- and, measured down the reference's mesh family at p = 4
+// (profiles/r2 "small meshes"), the fused iteration wins from 2 bricks per CU on (1.1e6 DoFs: +15 %; 5.4e5 DoFs: par; below: the pencil
+// kernel; p = 3: +34 %, p = 6: +14 %, p = 7: +8 %, p = 1: +4 % at 2-7 bricks per CU).
+// Sub-ranges: worth it only while the range still feeds the persistent grid (else the pencil kernel)
+static bool block_kernel_pays(bp5_mf *mf, uint32_t c0, uint32_t c1, uint32_t b0, uint32_t b1, int wg_per_cu, bool need_packed)
+{
+  if (mf->auto_block < 0) {
+    bp5_mf::DevPlan *dp = nullptr;
+    mf->auto_block = 0;
+    if (get_plan_raw(mf, -block_cpt(mf), &dp, 64) == BP5_OK && (dp->packed || !need_packed)) {
+      const size_t lds = block_default_lds_bytes(mf->degree, dp->max_list); // (the launcher's own formula)
+      mf->auto_block = lds * wg_per_cu <= 160 * 1024 && dp->n_groups >= 2u * (uint32_t)std::max(device_cus(mf), 1);
+    }
+  }
+  if (!mf->auto_block) return false;
+  return (c0 == 0 && c1 == mf->n_cells) || (b1 - b0) >= 30u * (uint32_t)std::max(mf->n_cus, 1);
+}
 // Variant 0 = library default.  The measured choices (profiles/r1): p = 1, 3 x-row team kernel; p = 4 on a mesh
 // handed over in cell blocks that fit three workgroups per CU: block-assembled kernel (no atomics, no zero-fill,
 // bitwise reproducible), whole cell range only; p = 4 affine geometry: team kernel; everything else: pencil kernel.
@@ -1003,24 +1029,11 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
   const int v = mf->apply_variant;
   if (v != 0) return v;
   if (mf->has_hanging && mf->geometry_mode == BP5_GEOM_AFFINE) return 90;
-  if (mf->operator_kind == BP5_OP_HELMHOLTZ || mf->has_hanging) { // pencil kernel, or the block kernel under the same conditions as below
+  uint32_t b0, b1;
+  if (mf->operator_kind == BP5_OP_HELMHOLTZ || mf->has_hanging) { // pencil kernel, or the block kernel (two workgroups per CU, packed indices)
     const int pencil = mf->has_hanging ? 90 : 0;
-    uint32_t hb0, hb1;
-    if (!block_lpc(mf->degree) || mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &hb0, &hb1)) return pencil;
-    if (mf->auto_block < 0) {
-      bp5_mf::DevPlan *dp = nullptr;
-      mf->auto_block = 0;
-      if (get_plan_raw(mf, -block_cpt(mf), &dp, 64) == BP5_OK && dp->packed) {
-        const size_t lds = block_default_lds_bytes(mf->degree, dp->max_list); // (the launcher's own formula)
-        if (!mf->n_cus) {
-          hipDeviceProp_t prop;
-          if (hipGetDeviceProperties(&prop, mf->device) == hipSuccess) mf->n_cus = prop.multiProcessorCount;
-        }
-        mf->auto_block = lds * 2 <= 160 * 1024 && dp->n_groups >= 2u * (uint32_t)std::max(mf->n_cus, 1);
-      }
-    }
-    if (mf->auto_block && (c0 != 0 || c1 != mf->n_cells) && (hb1 - hb0) < 30u * (uint32_t)std::max(mf->n_cus, 1)) return pencil;
-    return mf->auto_block ? 56 : pencil;
+    if (!block_lpc(mf->degree) || mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0, &b1)) return pencil;
+    return block_kernel_pays(mf, c0, c1, b0, b1, 2, true) ? 56 : pencil;
   }
   if ((mf->degree == 1 || mf->degree == 3) && mf->h_block_off.empty()) {
     if (mf->geometry_mode == BP5_GEOM_AFFINE) return 0;
@@ -1033,35 +1046,15 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
   if (!block_lpc(mf->degree)) return 0;
   const int fallback = (mf->degree == 4 && mf->geometry_mode == BP5_GEOM_AFFINE) ? 10 : (mf->degree == 3 || mf->degree == 1) ? 10 : 0; // else the pencil kernel
   if (mf->degree != 4 && mf->geometry_mode == BP5_GEOM_AFFINE) return 0; // the affine block build exists at p = 4 only
-  uint32_t b0_, b1_;
-  if (mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0_, &b1_)) return fallback;
-  if (mf->auto_block < 0) {
-    bp5_mf::DevPlan *dp = nullptr;
-    mf->auto_block = 0;
-    if (get_plan_raw(mf, -block_cpt(mf), &dp, 64) == BP5_OK) {
-      // LDS of the default shape: one transpose tile per cell slot + the brick's accumulator + two run tables; p <= 4 must fit
-      // three workgroups per CU, p >= 5 (more registers per lane: two workgroups per CU anyway) two
-      const size_t lds = block_default_lds_bytes(mf->degree, dp->max_list); // (the launcher's own formula)
-      mf->auto_block = lds * (mf->degree <= 4 ? 3 : 2) <= 160 * 1024 && (mf->degree == 4 || dp->packed);
-      // persistent workgroups need enough bricks each to balance: round 1 measured 3.6 bricks per workgroup (54^3 cells)
-      // 4 % behind the pencil kernel as a bare operator; with the CG dot products fused into the write-out the block kernel
-      // is ahead there too (profiles/r2: 0.439 vs 0.446 ms per iteration), so the bar dropped to 3 bricks per workgroup --
-      // and, measured down the reference's mesh family at p = 4 (profiles/r2 "small meshes"), the fused iteration wins from
-      // 2 bricks per CU on (1.1e6 DoFs: +15 %; 5.4e5 DoFs: par; below: the pencil kernel)
-      if (!mf->n_cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, mf->device) == hipSuccess) mf->n_cus = prop.multiProcessorCount;
-      }
-      if (dp->n_groups < 2u * (uint32_t)std::max(mf->n_cus, 1)) mf->auto_block = 0; // (p = 3: +34 %, p = 6: +14 %, p = 7: +8 %, p = 1: +4 % at 2-7 bricks per CU)
-    }
-  }
-  // sub-ranges: worth it only while the range still feeds the persistent grid (else the pencil kernel)
-  if (mf->auto_block && (c0 != 0 || c1 != mf->n_cells) && (b1_ - b0_) < 30u * (uint32_t)std::max(mf->n_cus, 1)) return fallback;
-  if (mf->auto_block && mf->geometry_mode == BP5_GEOM_AFFINE) { // the affine build needs the packed indices
+  if (mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0, &b1)) return fallback;
+  // LDS of the default shape: one transpose tile per cell slot + the brick's accumulator + two run tables; p <= 4 must fit
+  // three workgroups per CU, p >= 5 (more registers per lane: two workgroups per CU anyway) two
+  if (!block_kernel_pays(mf, c0, c1, b0, b1, mf->degree <= 4 ? 3 : 2, mf->degree != 4)) return fallback;
+  if (mf->geometry_mode == BP5_GEOM_AFFINE) { // the affine build needs the packed indices
     bp5_mf::DevPlan *dp = nullptr;
     if (get_plan_raw(mf, -block_cpt(mf), &dp, 64) != BP5_OK || !dp->packed) return fallback;
   }
-  return mf->auto_block ? 56 : fallback;
+  return 56;
 }
 // kernels that define every entry of dst themselves (owner stores + combine pass) need no zero-fill
 static bool variant_overwrites(const bp5_mf *mf, int ev)
@@ -1070,27 +1063,28 @@ static bool variant_overwrites(const bp5_mf *mf, int ev)
   return ev < 100 && ((v >= 10 && v <= 14) || (v >= 48 && v <= 63)) && !(mf->geometry_mode == BP5_GEOM_AFFINE && mf->degree != 4);
 }
 
-static int launch_apply_impl(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite)
+// One operator application: resolves the variant for the call's range (unless the caller fixed it) and dispatches on the degree
+static int launch_apply(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
 {
+  if (!call.keep_variant) call.set_variant(effective_variant(mf, call.c0, call.c1));
   switch (mf->degree) {
-    case 1: return apply_degree_impl<1>(mf, coef, src, dst, c0, c1, overwrite);
-    case 2: return apply_degree_impl<2>(mf, coef, src, dst, c0, c1, overwrite);
-    case 3: return apply_degree_impl<3>(mf, coef, src, dst, c0, c1, overwrite);
-    case 4: return apply_degree_impl<4>(mf, coef, src, dst, c0, c1, overwrite);
-    case 5: return apply_degree_impl<5>(mf, coef, src, dst, c0, c1, overwrite);
-    case 6: return apply_degree_impl<6>(mf, coef, src, dst, c0, c1, overwrite);
-    case 7: return apply_degree_impl<7>(mf, coef, src, dst, c0, c1, overwrite);
-    case 8: return apply_degree_impl<8>(mf, coef, src, dst, c0, c1, overwrite);
+    case 1: return apply_degree_impl<1>(mf, call, coef, src, dst);
+    case 2: return apply_degree_impl<2>(mf, call, coef, src, dst);
+    case 3: return apply_degree_impl<3>(mf, call, coef, src, dst);
+    case 4: return apply_degree_impl<4>(mf, call, coef, src, dst);
+    case 5: return apply_degree_impl<5>(mf, call, coef, src, dst);
+    case 6: return apply_degree_impl<6>(mf, call, coef, src, dst);
+    case 7: return apply_degree_impl<7>(mf, call, coef, src, dst);
+    case 8: return apply_degree_impl<8>(mf, call, coef, src, dst);
   }
   return fail(BP5_ERR_INVALID, "unsupported degree");
 }
+// ... with nothing asked for but a cell range and the overwrite mode
 static int launch_apply(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite = false)
 {
-  const int user = mf->apply_variant;
-  mf->apply_variant = effective_variant(mf, c0, c1);
-  const int st = launch_apply_impl(mf, coef, src, dst, c0, c1, overwrite);
-  mf->apply_variant = user;
-  return st;
+  ApplyCall call;
+  call.c0 = c0; call.c1 = c1; call.overwrite = overwrite;
+  return launch_apply(mf, call, coef, src, dst);
 }
 
 extern "C" int bp5_apply_cells(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1)
@@ -1468,11 +1462,9 @@ static bool overlap_wanted(const bp5_mf *mf) { return mf->overlap == 1 || (mf->o
 // ghost gather: owners send their interface values (packed through send_indices), ghosts are
 // received straight into the vector's ghost range (contiguous per neighbour)
 static int gather_exchange(bp5_mf *mf, double *v, bool on_comm_stream);
-extern "C" int bp5_halo_gather_start(bp5_mf *mf, double *v)
+// pack + exchange; the caller says which stream the exchange takes (the public call: the handle's overlap setting; the fused solves: their schedule)
+static int gather_start(bp5_mf *mf, double *v, bool on_comm_stream)
 {
-  if (!mf || !v) return fail(BP5_ERR_INVALID, "null argument");
-  if (mf->neighbors.empty()) return BP5_OK;
-  if (!mf->comm) return fail(BP5_ERR_INVALID, "halo exchange needs bp5_mf_set_comm");
   HIP_TRY(hipSetDevice(mf->device));
   BP5_TRY(halo_streams(mf));
   const uint32_t ns = mf->send_off.back();
@@ -1480,7 +1472,14 @@ extern "C" int bp5_halo_gather_start(bp5_mf *mf, double *v)
     hipLaunchKernelGGL(pack_kernel, dim3((ns + 255) / 256), dim3(256), 0, mf->stream, mf->d_send_idx, ns, v, mf->d_sendbuf);
     KERNEL_CHECK();
   }
-  return gather_exchange(mf, v, overlap_wanted(mf));
+  return gather_exchange(mf, v, on_comm_stream);
+}
+extern "C" int bp5_halo_gather_start(bp5_mf *mf, double *v)
+{
+  if (!mf || !v) return fail(BP5_ERR_INVALID, "null argument");
+  if (mf->neighbors.empty()) return BP5_OK;
+  if (!mf->comm) return fail(BP5_ERR_INVALID, "halo exchange needs bp5_mf_set_comm");
+  return gather_start(mf, v, overlap_wanted(mf));
 }
 // the RCCL part of the ghost gather: d_sendbuf is packed (on the compute stream); ghosts arrive in v's ghost range
 static int gather_exchange(bp5_mf *mf, double *v, bool on_comm_stream)
@@ -1542,30 +1541,35 @@ extern "C" int bp5_halo_scatter_add_start(bp5_mf *mf, double *v)
   BP5_TRY(halo_streams(mf));
   return scatter_exchange(mf, v, overlap_wanted(mf));
 }
-extern "C" int bp5_halo_scatter_add_finish(bp5_mf *mf, double *v)
+// fuse != NULL: the unpack kernels also correct the fused dot products and zero the ghost ranges of v and p
+static int scatter_add_finish(bp5_mf *mf, double *v, FuseState *fuse)
 {
-  if (!mf || !v) return fail(BP5_ERR_INVALID, "null argument");
-  if (mf->neighbors.empty()) return BP5_OK;
-  if (!mf->comm || !mf->comm_stream) return fail(BP5_ERR_INVALID, "bp5_halo_scatter_add_finish without bp5_halo_scatter_add_start");
   if (mf->overlap_now) HIP_TRY(hipStreamWaitEvent(mf->stream, mf->ev_halo[3], 0));
   for (size_t k = 0; k < mf->neighbors.size(); ++k) { // per neighbour: indices distinct -> race-free, fixed order
     const uint32_t sc = mf->send_off[k + 1] - mf->send_off[k];
     if (!sc) continue;
-    if (mf->fuse.on) { // fused CG dot products: correct the sums the write-out formed with the local part of these DoFs
+    if (fuse) { // fused CG dot products: correct the sums the write-out formed with the local part of these DoFs
       const uint32_t grid = std::min<uint32_t>((sc + 255) / 256, 1024u / (uint32_t)mf->neighbors.size());
-      const uint32_t ng = mf->fuse.ghosts_zeroed ? 0u : mf->n_ghost; // the first of these launches also zeroes both ghost ranges
+      const uint32_t ng = fuse->ghosts_zeroed ? 0u : mf->n_ghost; // the first of these launches also zeroes both ghost ranges
       hipLaunchKernelGGL(unpack_add_dots_kernel, dim3(grid), dim3(256), 0, mf->stream, mf->d_send_idx + mf->send_off[k],
-                         mf->d_send_dirichlet + mf->send_off[k], sc, mf->d_recvbuf + mf->send_off[k], v, mf->fuse.r, mf->d_partials,
-                         mf->fuse.n_cols, mf->d_st, v + mf->n_owned, const_cast<double *>(mf->fuse.p) + mf->n_owned, ng);
-      mf->fuse.n_cols += grid;
-      mf->fuse.ghosts_zeroed = true;
+                         mf->d_send_dirichlet + mf->send_off[k], sc, mf->d_recvbuf + mf->send_off[k], v, fuse->r, mf->d_partials,
+                         fuse->n_cols, mf->d_st, v + mf->n_owned, const_cast<double *>(fuse->p) + mf->n_owned, ng);
+      fuse->n_cols += grid;
+      fuse->ghosts_zeroed = true;
     } else
       hipLaunchKernelGGL(unpack_add_kernel, dim3((sc + 255) / 256), dim3(256), 0, mf->stream, mf->d_send_idx + mf->send_off[k], sc,
                          mf->d_recvbuf + mf->send_off[k], v);
     KERNEL_CHECK();
   }
-  if (mf->fuse.on && mf->fuse.ghosts_zeroed) return BP5_OK;
+  if (fuse && fuse->ghosts_zeroed) return BP5_OK;
   return bp5_halo_zero_ghosts(mf, v);
+}
+extern "C" int bp5_halo_scatter_add_finish(bp5_mf *mf, double *v)
+{
+  if (!mf || !v) return fail(BP5_ERR_INVALID, "null argument");
+  if (mf->neighbors.empty()) return BP5_OK;
+  if (!mf->comm || !mf->comm_stream) return fail(BP5_ERR_INVALID, "bp5_halo_scatter_add_finish without bp5_halo_scatter_add_start");
+  return scatter_add_finish(mf, v, nullptr);
 }
 extern "C" int bp5_halo_scatter_add(bp5_mf *mf, double *v)
 {
@@ -1585,38 +1589,36 @@ extern "C" int bp5_halo_zero_ghosts(bp5_mf *mf, double *v)
 // chosen for the whole application; the block kernel runs its brick ranges with owner stores + partial slab and a single
 // combine pass at the end, so the result is bitwise the one of the unsplit launch.
 struct ApplyPhases {
-  bool block = false, set = false, overwrite = false;
+  bool block = false, set = false;
   bp5_mf::DevPlan *dp = nullptr;
-  int user_variant = 0;
 };
-static int phases_begin(bp5_mf *mf, double *dst, bool overwrite, ApplyPhases &ph)
+// overwrite: what the whole application is asked for; call: filled in with what every range launch is asked for
+static int phases_begin(bp5_mf *mf, double *dst, bool overwrite, ApplyCall &call, ApplyPhases &ph)
 {
-  ph.user_variant = mf->apply_variant;
   const int ev = effective_variant(mf, 0, mf->n_cells);
   ph.block = ev < 100 && (ev % 100 == 56 || ev % 100 == 48 || ev % 100 == 49 || ev % 100 == 60 || ev % 100 == 61 || ev % 100 == 62 || ev % 100 == 63) && block_lpc(mf->degree) != 0 && (mf->degree == 4 || ev % 100 == 56);
-  ph.overwrite = false;
+  call.overwrite = false;
   if (ph.block) {
     BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &ph.dp));
     ph.set = overwrite && ph.dp->covers_all;
-    ph.overwrite = ph.set;
+    call.overwrite = ph.set;
     if (overwrite && !ph.set) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    mf->defer_combine = true;
-    mf->apply_variant = ev; // every range takes the block kernel, however few bricks it holds
+    call.combine_later = true;
+    call.set_variant(ev); // every range takes the block kernel, however few bricks it holds (and the combine passes the form the variant implies)
+    call.keep_variant = true;
   } else if (overwrite) // atomic kernels accumulate: one zero-fill, then every range adds
     HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
   return BP5_OK;
 }
-static int phases_range(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, ApplyPhases &ph)
+static int phases_range(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1)
 {
   if (c1 <= c0) return BP5_OK;
-  return launch_apply(mf, coef, src, dst, c0, c1, ph.overwrite);
+  call.c0 = c0; call.c1 = c1;
+  return launch_apply(mf, call, coef, src, dst);
 }
-static int phases_end(bp5_mf *mf, double *dst, ApplyPhases &ph, int status, int window = COMBINE_ALL)
+static int phases_end(bp5_mf *mf, ApplyCall &call, double *dst, ApplyPhases &ph, int window = COMBINE_ALL)
 {
-  mf->defer_combine = false;
-  mf->apply_variant = ph.user_variant;
-  BP5_TRY(status);
-  return ph.block ? launch_combine(mf, ph.dp, dst, ph.set, window) : BP5_OK;
+  return ph.block ? launch_combine(mf, call, ph.dp, dst, ph.set, window) : BP5_OK;
 }
 // interior cells [0, split) run under the ghost gather, [split, n_interior) under the scatter-add; split on a brick boundary
 static uint32_t interior_split(const bp5_mf *mf)
@@ -1626,7 +1628,8 @@ static uint32_t interior_split(const bp5_mf *mf)
   const auto it = std::lower_bound(mf->h_block_off.begin(), mf->h_block_off.end(), half);
   return it == mf->h_block_off.end() || *it > mf->n_interior ? mf->n_interior : *it;
 }
-static int apply_overlapped(bp5_mf *mf, const double *coef, double *src, double *dst, bool overwrite)
+// overwrite: of the whole application.  call: the caller's, for its profiling mark; range, overwrite mode and variant of the range launches are set here
+static int apply_overlapped(bp5_mf *mf, ApplyCall &call, const double *coef, double *src, double *dst, bool overwrite)
 {
   // block-kernel ranges must be unions of whole bricks: the generator emits interior and ghost-touching bricks separately;
   // a mesh whose n_interior_cells cuts through a brick runs unsplit (the exchange is then not overlapped)
@@ -1635,31 +1638,31 @@ static int apply_overlapped(bp5_mf *mf, const double *coef, double *src, double 
                        block_aligned(mf, 0, mf->n_interior, &b0, &b1);
   ApplyPhases ph;
   BP5_TRY(bp5_halo_gather_start(mf, src));
-  int st = phases_begin(mf, dst, overwrite, ph);
-  if (st == BP5_OK && (!aligned || !overlap_wanted(mf))) {
-    st = bp5_halo_gather_finish(mf, src);
-    if (st == BP5_OK) st = phases_range(mf, coef, src, dst, 0, mf->n_cells, ph);
-    BP5_TRY(phases_end(mf, dst, ph, st));
+  BP5_TRY(phases_begin(mf, dst, overwrite, call, ph));
+  if (!aligned || !overlap_wanted(mf)) {
+    BP5_TRY(bp5_halo_gather_finish(mf, src));
+    BP5_TRY(phases_range(mf, call, coef, src, dst, 0, mf->n_cells));
+    BP5_TRY(phases_end(mf, call, dst, ph));
     return bp5_halo_scatter_add(mf, dst);
   }
   const uint32_t split = interior_split(mf);
-  if (st == BP5_OK) st = phases_range(mf, coef, src, dst, 0, split, ph);                 // under the gather
-  if (st == BP5_OK) st = bp5_halo_gather_finish(mf, src);
-  if (st == BP5_OK) st = phases_range(mf, coef, src, dst, mf->n_interior, mf->n_cells, ph); // cells that touch ghosts
+  BP5_TRY(phases_range(mf, call, coef, src, dst, 0, split));                      // under the gather
+  BP5_TRY(bp5_halo_gather_finish(mf, src));
+  BP5_TRY(phases_range(mf, call, coef, src, dst, mf->n_interior, mf->n_cells));   // cells that touch ghosts
   // The atomic kernels have completed the ghost entries of dst once the ghost-touching cells are done; the block kernel needs the
   // ghost ROWS of its combine pass on top (ghost DoFs on brick faces go through the partial slab): one small launch over the ghost
   // window.  Either way the ghost contributions travel to their owners under the second part of the interior cells, and the block
   // kernel's owned rows are combined after the last range -- every row once, in the order of the unsplit pass.
   const bool ghost_rows = ph.block && ph.dp->n_shared && mf->n_ghost;                  // ghost rows (may) pass through the partial slab
-  if (ghost_rows && !(ph.dp->cr_tile && !mf->combine_csr)) { // (per-DoF CSR combine pass: no windows -- the ghost rows are final after the last range only)
-    if (st == BP5_OK) st = phases_range(mf, coef, src, dst, split, mf->n_interior, ph);
-    BP5_TRY(phases_end(mf, dst, ph, st));
+  if (ghost_rows && !(ph.dp->cr_tile && !call.csr_combine)) { // (per-DoF CSR combine pass: no windows -- the ghost rows are final after the last range only)
+    BP5_TRY(phases_range(mf, call, coef, src, dst, split, mf->n_interior));
+    BP5_TRY(phases_end(mf, call, dst, ph));
     return bp5_halo_scatter_add(mf, dst);
   }
-  if (st == BP5_OK && ghost_rows) st = launch_combine(mf, ph.dp, dst, ph.set, COMBINE_GHOST);
-  if (st == BP5_OK) st = bp5_halo_scatter_add_start(mf, dst);
-  if (st == BP5_OK) st = phases_range(mf, coef, src, dst, split, mf->n_interior, ph);
-  BP5_TRY(phases_end(mf, dst, ph, st, ghost_rows ? COMBINE_OWNED : COMBINE_ALL));
+  if (ghost_rows) BP5_TRY(launch_combine(mf, call, ph.dp, dst, ph.set, COMBINE_GHOST));
+  BP5_TRY(bp5_halo_scatter_add_start(mf, dst));
+  BP5_TRY(phases_range(mf, call, coef, src, dst, split, mf->n_interior));
+  BP5_TRY(phases_end(mf, call, dst, ph, ghost_rows ? COMBINE_OWNED : COMBINE_ALL));
   return bp5_halo_scatter_add_finish(mf, dst);
 }
 extern "C" int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src, double *dst, int zero_dst)
@@ -1667,8 +1670,10 @@ extern "C" int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src
   if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst must differ");
   HIP_TRY(hipSetDevice(mf->device));
-  if (mf->comm && !mf->neighbors.empty()) BP5_TRY(apply_overlapped(mf, coef, src, dst, zero_dst != 0));
-  else BP5_TRY(launch_apply(mf, coef, src, dst, 0, mf->n_cells, zero_dst != 0));
+  if (mf->comm && !mf->neighbors.empty()) {
+    ApplyCall call;
+    BP5_TRY(apply_overlapped(mf, call, coef, src, dst, zero_dst != 0));
+  } else BP5_TRY(launch_apply(mf, coef, src, dst, 0, mf->n_cells, zero_dst != 0));
   BP5_TRY(bp5_halo_zero_ghosts(mf, src));
   return bp5_copy_constrained(mf, src, dst);
 }
@@ -1741,13 +1746,156 @@ struct ApplyProfile {
   }
 };
 
+// What one solve decided once and every operator application inside it follows; it lives on the solver's stack
+struct SolveState {
+  ApplyProfile prof;
+  // fused dot products across ranks: where the exchange is enqueued (ApplyCall::exchange) and whether whole-range launches walk the
+  // ghost-touching bricks first (ApplyCall::two_parts)
+  int exchange = EXCHANGE_NONE;
+  bool two_parts = false;
+  bool gather_in_flight = false; // the solver started the ghost gather of p under its update kernel
+  // one rank, separate dot-product kernel: dst arrives zeroed (the update kernel stored the zeros) / the Dirichlet copy follows in the dots kernel
+  bool dst_prezeroed = false, copies_dirichlet = false;
+  // profile == 2: stamps of the iteration `phase_it` (0-based; stamps beyond MAX_ITERS are dropped); bit k of phase_recorded[it]: mark k recorded
+  bool phase_on = false;
+  int phase_it = 0;
+  uint8_t phase_recorded[bp5_mf::PhaseProfile::MAX_ITERS] = {};
+};
+
 // profile == 2: stamp k of the iteration being profiled (bp5_cg_result.phase_ms)
-static int phase_mark(bp5_mf *mf, int k)
+static int phase_mark(bp5_mf *mf, SolveState &ss, int k)
 {
-  auto &ph = mf->phase;
-  if (!ph.on || ph.it >= bp5_mf::PhaseProfile::MAX_ITERS) return BP5_OK;
-  HIP_TRY(hipEventRecord(ph.ev[(size_t)ph.it * bp5_mf::PhaseProfile::MARKS + k], mf->stream));
-  ph.recorded[ph.it] |= (uint8_t)(1u << k);
+  if (!ss.phase_on || ss.phase_it >= bp5_mf::PhaseProfile::MAX_ITERS) return BP5_OK;
+  HIP_TRY(hipEventRecord(mf->phase.ev[(size_t)ss.phase_it * bp5_mf::PhaseProfile::MARKS + k], mf->stream));
+  ss.phase_recorded[ss.phase_it] |= (uint8_t)(1u << k);
+  return BP5_OK;
+}
+
+// The three exchange schedules of an operator application with fused dot products across ranks (fused_vmult_distributed).  All of them
+// run the same kernels with the same per-brick sums and the same combine order: v is bitwise the same (the dot products are summed over a
+// different column layout).
+// Unsplit (bp5_mf_set_overlap 0): one launch with its combine pass, then the exchange on the compute stream.
+static int fused_unsplit(bp5_mf *mf, SolveState &ss, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
+  ApplyProfile &prof = ss.prof;
+  if (prof.on) call.mark_event = mf->ev_pool[prof.used + 2];
+  BP5_TRY(launch_apply(mf, call, coef, src, dst));
+  if (!call.mark_recorded) BP5_TRY(prof.mark(2));
+  BP5_TRY(prof.mark(3));
+  if (prof.on) prof.used += 4;
+  BP5_TRY(phase_mark(mf, ss, 3));
+  BP5_TRY(halo_streams(mf));
+  BP5_TRY(scatter_exchange(mf, dst, false));
+  return scatter_add_finish(mf, dst, call.fuse); // (dot-product corrections + ghost zeroing inside)
+}
+// Ghost-rows-first (the automatic choice): all bricks in one launch; then the GHOST rows of the combine pass (a small launch), the exchange on
+// the communication stream, and the owned rows combined underneath it: nothing runs beside the bandwidth-bound brick kernel (a co-running
+// RCCL kernel crawls there -- 300 us for one DoF plane -- and slows it: profiles/r3), the exchange hides behind the owned-row combine
+static int fused_ghost_rows_first(bp5_mf *mf, SolveState &ss, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
+  ApplyProfile &prof = ss.prof;
+  bp5_mf::DevPlan *dp = nullptr;
+  BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));
+  BP5_TRY(halo_streams(mf));
+  call.combine_later = true;
+  BP5_TRY(launch_apply(mf, call, coef, src, dst));
+  BP5_TRY(prof.mark(2));
+  // BP5_TUNE_COMBINE_SIGNAL (A/B knob of the handle): the two combine launches as ONE -- its first workgroups
+  // complete the ghost rows and count themselves in, the communication stream waits for the count (stream wait-value) and starts the
+  // exchange while the same launch walks the owned rows; same tiles and columns as the two launches: same bits.  One launch, one gap and
+  // one cross-stream event less -- and on ONE GPU 16 us per iteration SLOWER than the two launches (0.547 against 0.531 ms on the slab of
+  // rank 3 of 8, profiles/r3 z_*: the RCCL kernel then runs beside the bandwidth-bound combine pass from its first microsecond and both
+  // crawl), hence not the default; whether a longer xGMI transfer pays for the earlier start is for a multi-GPU run to say
+  const bool combine_signal = mf->tune[BP5_TUNE_COMBINE_SIGNAL] != 0;
+  const bool one_combine = combine_signal && mf->can_wait_value == 1 && mf->n_ghost && mf->d_signal && dp->n_shared > dp->n_shared_owned && dp->cr_tile && !call.csr_combine; // (ghost rows among the shared ones: at least one workgroup signals)
+  if (one_combine) {
+    BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_GHOST_THEN_OWNED));
+    HIP_TRY(hipStreamWaitValue64(mf->comm_stream, mf->d_signal, mf->signal_target, hipStreamWaitValueGte, ~0ull));
+    BP5_TRY(scatter_exchange(mf, dst, true, true));
+  } else if (mf->tune[BP5_TUNE_GHOST_COMBINE_ON_COMM] && mf->n_ghost) {
+    // the ghost rows of the combine pass on the COMMUNICATION stream (behind an event that says the brick kernel is done, in front of the send): the
+    // owned rows start right behind the brick kernel on the compute stream -- one small launch and its gap off the critical path (same kernels, same bits)
+    HIP_TRY(hipEventRecord(mf->ev_halo[2], mf->stream));
+    HIP_TRY(hipStreamWaitEvent(mf->comm_stream, mf->ev_halo[2], 0));
+    BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_GHOST, true));
+    BP5_TRY(scatter_exchange(mf, dst, true, true));
+    BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_OWNED));
+  } else {
+    if (mf->n_ghost) BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_GHOST));
+    BP5_TRY(scatter_exchange(mf, dst, true));
+    BP5_TRY(launch_combine(mf, call, dp, dst, true, mf->n_ghost ? COMBINE_OWNED : COMBINE_ALL));
+  }
+  BP5_TRY(prof.mark(3));
+  if (prof.on) prof.used += 4;
+  BP5_TRY(phase_mark(mf, ss, 3));
+  return scatter_add_finish(mf, dst, call.fuse);
+}
+// Boundary-first (bp5_mf_set_overlap 1, the twin of overlap_communication_computation, bp5/step-64.cu:241,274): the bricks that touch ghost
+// DoFs run FIRST, one small combine pass completes the ghost rows, the exchange starts on the communication stream and the interior bricks
+// run underneath it; the owned rows are combined after the last brick.
+static int fused_boundary_first(bp5_mf *mf, SolveState &ss, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
+  ApplyProfile &prof = ss.prof;
+  bp5_mf::DevPlan *dp = nullptr;
+  BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));
+  BP5_TRY(halo_streams(mf));
+  call.set_variant(56);      // every range takes the block kernel, however few bricks it holds
+  call.keep_variant = true;
+  call.combine_later = true; // one combine pass per window, launched here
+  const bool has_boundary = mf->n_interior < mf->n_cells, in_one_launch = mf->can_wait_value == 1 && has_boundary && mf->n_interior > 0 && ss.two_parts;
+  if (in_one_launch) {
+    // ONE launch: every workgroup walks its share of the ghost-touching bricks first and counts itself in; the communication
+    // stream waits for the count, combines the ghost rows and sends them while the same launch works through the interior bricks
+    call.signal = true;
+    BP5_TRY(launch_apply(mf, call, coef, src, dst));
+    HIP_TRY(hipStreamWaitValue64(mf->comm_stream, mf->d_signal, mf->signal_target, hipStreamWaitValueGte, ~0ull));
+    if (mf->n_ghost) BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_GHOST, true)); // on the communication stream, between the wait and the send
+    BP5_TRY(scatter_exchange(mf, dst, true, true));
+  } else if (has_boundary) {
+    call.two_parts = false; // (range launches)
+    call.c0 = mf->n_interior; call.c1 = mf->n_cells; // bricks that touch ghosts
+    BP5_TRY(launch_apply(mf, call, coef, src, dst));
+    if (mf->n_ghost) BP5_TRY(launch_combine(mf, call, dp, dst, true, COMBINE_GHOST));
+    BP5_TRY(scatter_exchange(mf, dst, true)); // send the ghost rows / post the receives: under the interior bricks
+    call.c0 = 0; call.c1 = mf->n_interior;
+    if (mf->n_interior) BP5_TRY(launch_apply(mf, call, coef, src, dst));
+  } else { // (a rank without ghost-touching cells only receives: post the receives, then all bricks)
+    BP5_TRY(scatter_exchange(mf, dst, true));
+    BP5_TRY(launch_apply(mf, call, coef, src, dst));
+  }
+  BP5_TRY(prof.mark(2)); // (the profile brackets the brick launch(es))
+  BP5_TRY(launch_combine(mf, call, dp, dst, true, mf->n_ghost ? COMBINE_OWNED : COMBINE_ALL));
+  BP5_TRY(prof.mark(3));
+  if (prof.on) prof.used += 4;
+  BP5_TRY(phase_mark(mf, ss, 3));
+  return scatter_add_finish(mf, dst, call.fuse);
+}
+// Fused dot products across ranks: gather, fused launch(es) over all cells (p.v is a sum over cells, so it needs no owner
+// bookkeeping; v.v, r.v, r.r run over owned DoFs), then the ghost contributions travel to their owners, whose unpack kernel
+// corrects v.v and r.v for what it adds.  The fused exchanges choose their streams themselves, whatever the handle's overlap setting.
+static int fused_vmult_distributed(bp5_mf *mf, SolveState &ss, const double *coef, double *src, double *dst, const double *fuse_r, uint32_t *n_cols)
+{
+  if (ss.gather_in_flight) { ss.gather_in_flight = false; BP5_TRY(bp5_halo_gather_finish(mf, src)); } // started under the update kernel
+  else {
+    BP5_TRY(gather_start(mf, src, false));
+    BP5_TRY(bp5_halo_gather_finish(mf, src));
+  }
+  BP5_TRY(phase_mark(mf, ss, 2));
+  BP5_TRY(ss.prof.mark(0));
+  BP5_TRY(ss.prof.mark(1));
+  FuseState fuse;
+  fuse.p = src; fuse.r = fuse_r;
+  ApplyCall call;
+  call.c0 = 0; call.c1 = mf->n_cells; call.overwrite = true;
+  call.fuse = &fuse;
+  call.exchange = ss.exchange;
+  call.two_parts = ss.two_parts;
+  if (ss.exchange == EXCHANGE_BOUNDARY_FIRST) BP5_TRY(fused_boundary_first(mf, ss, call, coef, src, dst));
+  else if (ss.exchange == EXCHANGE_GHOST_ROWS_FIRST) BP5_TRY(fused_ghost_rows_first(mf, ss, call, coef, src, dst));
+  else BP5_TRY(fused_unsplit(mf, ss, call, coef, src, dst));
+  *n_cols = fuse.n_cols;
+  if (!fuse.ghosts_zeroed) BP5_TRY(bp5_halo_zero_ghosts(mf, src)); // (a rank that owns no interface DoFs launched no unpack kernel; dst: scatter_add_finish)
+  // no Dirichlet copy: the write-out stored v = p on this rank's Dirichlet rows and the unpack kernel leaves them alone
   return BP5_OK;
 }
 
@@ -1756,148 +1904,21 @@ static int phase_mark(bp5_mf *mf, int k)
 // combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311) and apply the Dirichlet copy; the
 // partial sums land in d_partials, *n_cols columns of them.  fuse_r: the residual vector of the merged solver (D == 1), or NULL when
 // only p.v is wanted (standard CG: rows 2-6 of the sums are then meaningless and r is never read)
-static int solver_vmult(bp5_mf *mf, const double *coef, double *src, double *dst, bool zero, ApplyProfile &prof, const double *fuse_r = nullptr,
+static int solver_vmult(bp5_mf *mf, SolveState &ss, const double *coef, double *src, double *dst, bool zero, const double *fuse_r = nullptr,
                         uint32_t *n_cols = nullptr)
 {
+  ApplyProfile &prof = ss.prof;
   const bool dist = mf->comm && !mf->neighbors.empty(); // halo exchange: whenever there are neighbours (tests: a self neighbour)
   const bool fusing = n_cols != nullptr;
-  if (dist && fusing) {
-    // fused dot products across ranks: gather, fused launch(es) over all cells (p.v is a sum over cells, so it needs no owner
-    // bookkeeping; v.v, r.v, r.r run over owned DoFs), then the ghost contributions travel to their owners, whose unpack kernel
-    // corrects v.v and r.v for what it adds.
-    // Boundary-first schedule (mf->cg_split, the twin of overlap_communication_computation, bp5/step-64.cu:241,274): the bricks that
-    // touch ghost DoFs run FIRST, one small combine pass completes the ghost rows, the exchange starts on the communication stream and
-    // the interior bricks run underneath it; the owned rows are combined after the last brick.  Same kernels, same per-brick sums and
-    // the same combine order as the single launch: v is bitwise the same (the dot products are summed over a different column layout).
-    const bool split = mf->cg_split;
-    if (mf->fuse.gather_in_flight) { mf->fuse.gather_in_flight = false; BP5_TRY(bp5_halo_gather_finish(mf, src)); } // started under the update kernel
-    else BP5_TRY(bp5_halo_gather(mf, src));
-    BP5_TRY(phase_mark(mf, 2));
-    BP5_TRY(prof.mark(0));
-    BP5_TRY(prof.mark(1));
-    mf->fuse.on = true; mf->fuse.p = src; mf->fuse.r = fuse_r; mf->fuse.n_cols = 0;
-    int st = BP5_OK;
-    bool marked = false;
-    if (!split && mf->cg_late) {
-      // all bricks in one launch; then the GHOST rows of the combine pass (a small launch), the exchange on the communication stream,
-      // and the owned rows combined underneath it: nothing runs beside the bandwidth-bound brick kernel (a co-running RCCL kernel
-      // crawls there -- 300 us for one DoF plane -- and slows it: profiles/r3), the exchange hides behind the owned-row combine
-      bp5_mf::DevPlan *dp = nullptr;
-      st = get_plan_raw(mf, -block_cpt(mf), &dp);
-      if (st == BP5_OK) st = halo_streams(mf);
-      mf->defer_combine = true;
-      if (st == BP5_OK) st = launch_apply(mf, coef, src, dst, 0, mf->n_cells, true);
-      mf->defer_combine = false;
-      if (st == BP5_OK) st = prof.mark(2);
-      // BP5_TUNE_COMBINE_SIGNAL (A/B knob of the handle): the two combine launches as ONE -- its first workgroups
-      // complete the ghost rows and count themselves in, the communication stream waits for the count (stream wait-value) and starts the
-      // exchange while the same launch walks the owned rows; same tiles and columns as the two launches: same bits.  One launch, one gap and
-      // one cross-stream event less -- and on ONE GPU 16 us per iteration SLOWER than the two launches (0.547 against 0.531 ms on the slab of
-      // rank 3 of 8, profiles/r3 z_*: the RCCL kernel then runs beside the bandwidth-bound combine pass from its first microsecond and both
-      // crawl), hence not the default; whether a longer xGMI transfer pays for the earlier start is for a multi-GPU run to say
-      const bool combine_signal = mf->tune[BP5_TUNE_COMBINE_SIGNAL] != 0;
-      const bool one_combine = combine_signal && mf->can_wait_value == 1 && mf->n_ghost && mf->d_signal && dp && dp->n_shared > dp->n_shared_owned && dp->cr_tile && !mf->combine_csr; // (ghost rows among the shared ones: at least one workgroup signals)
-      if (one_combine) {
-        if (st == BP5_OK) st = launch_combine(mf, dp, dst, true, COMBINE_GHOST_THEN_OWNED);
-        if (st == BP5_OK && hipStreamWaitValue64(mf->comm_stream, mf->d_signal, mf->signal_target, hipStreamWaitValueGte, ~0ull) != hipSuccess)
-          st = fail(BP5_ERR_HIP, "hipStreamWaitValue64");
-        if (st == BP5_OK) st = scatter_exchange(mf, dst, true, true);
-      } else if (mf->tune[BP5_TUNE_GHOST_COMBINE_ON_COMM] && mf->n_ghost) {
-        // the ghost rows of the combine pass on the COMMUNICATION stream (behind an event that says the brick kernel is done, in front of the send): the
-        // owned rows start right behind the brick kernel on the compute stream -- one small launch and its gap off the critical path (same kernels, same bits)
-        if (st == BP5_OK && hipEventRecord(mf->ev_halo[2], mf->stream) != hipSuccess) st = fail(BP5_ERR_HIP, "hipEventRecord");
-        if (st == BP5_OK && hipStreamWaitEvent(mf->comm_stream, mf->ev_halo[2], 0) != hipSuccess) st = fail(BP5_ERR_HIP, "hipStreamWaitEvent");
-        if (st == BP5_OK) {
-          hipStream_t compute = mf->stream;
-          mf->stream = mf->comm_stream;
-          st = launch_combine(mf, dp, dst, true, COMBINE_GHOST);
-          mf->stream = compute;
-        }
-        if (st == BP5_OK) st = scatter_exchange(mf, dst, true, true);
-        if (st == BP5_OK) st = launch_combine(mf, dp, dst, true, COMBINE_OWNED);
-      } else {
-        if (st == BP5_OK && mf->n_ghost) st = launch_combine(mf, dp, dst, true, COMBINE_GHOST);
-        if (st == BP5_OK) st = scatter_exchange(mf, dst, true);
-        if (st == BP5_OK) st = launch_combine(mf, dp, dst, true, mf->n_ghost ? COMBINE_OWNED : COMBINE_ALL);
-      }
-      if (st == BP5_OK) st = prof.mark(3);
-      if (prof.on) prof.used += 4;
-      if (st == BP5_OK) st = phase_mark(mf, 3);
-      if (st == BP5_OK) st = bp5_halo_scatter_add_finish(mf, dst);
-    } else if (!split) {
-      if (prof.on) mf->prof_mark = mf->ev_pool[prof.used + 2];
-      st = launch_apply(mf, coef, src, dst, 0, mf->n_cells, true);
-      marked = prof.on && mf->prof_mark == nullptr;
-      mf->prof_mark = nullptr;
-      if (st == BP5_OK && !marked) st = prof.mark(2);
-      if (st == BP5_OK) st = prof.mark(3);
-      if (prof.on) prof.used += 4;
-      if (st == BP5_OK) st = phase_mark(mf, 3);
-      if (st == BP5_OK) st = bp5_halo_scatter_add(mf, dst); // (fuse.on: dot-product corrections + ghost zeroing inside)
-    } else {
-      bp5_mf::DevPlan *dp = nullptr;
-      st = get_plan_raw(mf, -block_cpt(mf), &dp);
-      if (st == BP5_OK) st = halo_streams(mf);
-      const int user_variant = mf->apply_variant;
-      mf->apply_variant = 56;    // every range takes the block kernel, however few bricks it holds
-      mf->defer_combine = true;  // one combine pass per window, launched here
-      const bool has_boundary = mf->n_interior < mf->n_cells, in_one_launch = mf->can_wait_value == 1 && has_boundary && mf->n_interior > 0 && mf->blk_two_parts;
-      if (st == BP5_OK && in_one_launch) {
-        // ONE launch: every workgroup walks its share of the ghost-touching bricks first and counts itself in; the communication
-        // stream waits for the count, combines the ghost rows and sends them while the same launch works through the interior bricks
-        mf->blk_signal = true;
-        st = launch_apply(mf, coef, src, dst, 0, mf->n_cells, true);
-        mf->blk_signal = false;
-        if (st == BP5_OK && hipStreamWaitValue64(mf->comm_stream, mf->d_signal, mf->signal_target, hipStreamWaitValueGte, ~0ull) != hipSuccess)
-          st = fail(BP5_ERR_HIP, "hipStreamWaitValue64");
-        if (st == BP5_OK && mf->n_ghost) {
-          hipStream_t compute = mf->stream;
-          mf->stream = mf->comm_stream; // the ghost-row combine runs on the communication stream, between the wait and the send
-          st = launch_combine(mf, dp, dst, true, COMBINE_GHOST);
-          mf->stream = compute;
-        }
-        if (st == BP5_OK) st = scatter_exchange(mf, dst, true, true);
-      } else {
-        if (st == BP5_OK && has_boundary) {
-          const bool two = mf->blk_two_parts;
-          mf->blk_two_parts = false; // (range launches)
-          st = launch_apply(mf, coef, src, dst, mf->n_interior, mf->n_cells, true); // bricks that touch ghosts
-          if (st == BP5_OK && mf->n_ghost) st = launch_combine(mf, dp, dst, true, COMBINE_GHOST);
-          if (st == BP5_OK) st = scatter_exchange(mf, dst, true); // send the ghost rows / post the receives: under the interior bricks
-          if (st == BP5_OK && mf->n_interior) st = launch_apply(mf, coef, src, dst, 0, mf->n_interior, true);
-          mf->blk_two_parts = two;
-        } else { // (a rank without ghost-touching cells only receives: post the receives, then all bricks)
-          if (st == BP5_OK) st = scatter_exchange(mf, dst, true);
-          if (st == BP5_OK) st = launch_apply(mf, coef, src, dst, 0, mf->n_cells, true);
-        }
-      }
-      mf->defer_combine = false;
-      mf->apply_variant = user_variant;
-      if (st == BP5_OK) st = prof.mark(2); // (the profile brackets the brick launch(es))
-      if (st == BP5_OK) st = launch_combine(mf, dp, dst, true, mf->n_ghost ? COMBINE_OWNED : COMBINE_ALL);
-      if (st == BP5_OK) st = prof.mark(3);
-      if (prof.on) prof.used += 4;
-      if (st == BP5_OK) st = phase_mark(mf, 3);
-      if (st == BP5_OK) st = bp5_halo_scatter_add_finish(mf, dst);
-    }
-    *n_cols = mf->fuse.n_cols;
-    const bool ghosts_zeroed = mf->fuse.ghosts_zeroed;
-    mf->fuse = bp5_mf::Fuse{};
-    mf->defer_combine = false;
-    BP5_TRY(st);
-    if (!ghosts_zeroed) BP5_TRY(bp5_halo_zero_ghosts(mf, src)); // (a rank that owns no interface DoFs launched no unpack kernel; dst: scatter_add_finish)
-    // no Dirichlet copy: the write-out stored v = p on this rank's Dirichlet rows and the unpack kernel leaves them alone
-    return BP5_OK;
-  }
+  if (dist && fusing) return fused_vmult_distributed(mf, ss, coef, src, dst, fuse_r, n_cols);
+  ApplyCall call;
+  call.c0 = 0; call.c1 = mf->n_cells;
   if (dist) { // phased application: the exchange overlaps the interior cells (apply_overlapped)
     BP5_TRY(prof.mark(0));
     BP5_TRY(prof.mark(1));
-    if (prof.on) mf->prof_mark = mf->ev_pool[prof.used + 2];
-    const int st = apply_overlapped(mf, coef, src, dst, zero);
-    const bool marked = prof.on && mf->prof_mark == nullptr;
-    mf->prof_mark = nullptr;
-    BP5_TRY(st);
-    if (!marked) BP5_TRY(prof.mark(2));
+    if (prof.on) call.mark_event = mf->ev_pool[prof.used + 2];
+    BP5_TRY(apply_overlapped(mf, call, coef, src, dst, zero));
+    if (!call.mark_recorded) BP5_TRY(prof.mark(2));
     BP5_TRY(prof.mark(3));
     if (prof.on) prof.used += 4;
     BP5_TRY(bp5_halo_zero_ghosts(mf, src));
@@ -1907,22 +1928,21 @@ static int solver_vmult(bp5_mf *mf, const double *coef, double *src, double *dst
   const bool owner_scatter = variant_overwrites(mf, effective_variant(mf, 0, mf->n_cells));
   BP5_TRY(prof.mark(0));
   if (zero && !owner_scatter) {
-    if (!mf->solver_prezeroed) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); // (else: the update kernel stored the zeros)
+    if (!ss.dst_prezeroed) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); // (else: the update kernel stored the zeros)
     zero = false;
   }
   BP5_TRY(prof.mark(1));
-  if (prof.on) mf->prof_mark = mf->ev_pool[prof.used + 2];
-  if (fusing) { mf->fuse.on = true; mf->fuse.p = src; mf->fuse.r = fuse_r; mf->fuse.n_cols = 0; }
-  const int st = launch_apply(mf, coef, src, dst, 0, mf->n_cells, zero);
-  if (fusing) { *n_cols = mf->fuse.n_cols; mf->fuse = bp5_mf::Fuse{}; }
-  const bool marked = prof.on && mf->prof_mark == nullptr;
-  mf->prof_mark = nullptr;
-  BP5_TRY(st);
-  if (!marked) BP5_TRY(prof.mark(2));
+  if (prof.on) call.mark_event = mf->ev_pool[prof.used + 2];
+  FuseState fuse;
+  if (fusing) { fuse.p = src; fuse.r = fuse_r; call.fuse = &fuse; }
+  call.overwrite = zero;
+  BP5_TRY(launch_apply(mf, call, coef, src, dst));
+  if (fusing) *n_cols = fuse.n_cols;
+  if (!call.mark_recorded) BP5_TRY(prof.mark(2));
   BP5_TRY(prof.mark(3));
   if (prof.on) prof.used += 4;
   if (fusing) return BP5_OK; // Dirichlet DoFs were written by the fused write-out
-  if (mf->solver_copies_dirichlet) return BP5_OK; // ... or will be by the solver's dot-product kernel, which reads src and dst anyway
+  if (ss.copies_dirichlet) return BP5_OK; // ... or will be by the solver's dot-product kernel, which reads src and dst anyway
   return bp5_copy_constrained(mf, src, dst);
 }
 
@@ -1936,8 +1956,9 @@ static int poll_state(bp5_mf *mf)
 
 // cg.solve(A, x, b, preconditioner): the solvers need nothing of A but vmult (bp5/solver.h:25-30,377,475).  user == nullptr:
 // the built-in Poisson operator (coef); otherwise the caller's operator through its callback.
+// history != NULL (plain solve): alpha / beta of iteration k into history[2k], history[2k + 1] on the device, k < history_cap (Chebyshev estimate)
 static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void *user_ctx, const double *diag, const double *b, double *x,
-                         const bp5_cg_params *prm, bp5_cg_result *res)
+                         const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr, int history_cap = 0)
 {
   if (!mf || (!user && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
   if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
@@ -1949,26 +1970,21 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
   const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1);
   hipStream_t s = mf->stream;
   double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h;
-  ApplyProfile prof{mf, prm->profile != 0};
+  SolveState ss{ApplyProfile{mf, prm->profile != 0}};
+  ApplyProfile &prof = ss.prof;
   if (prof.on) { // create the bracketing events before the timed region starts
     const size_t want = 4 * (size_t)std::min(prm->max_iter, ApplyProfile::MAX_PROFILED);
     while (mf->ev_pool.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->ev_pool.push_back(e); }
   }
-  {
-    auto &ph = mf->phase;
-    ph.on = prm->profile == 2 && prm->variant == BP5_CG_MERGED;
-    ph.it = 0;
-    if (ph.on) {
-      const size_t want = (size_t)bp5_mf::PhaseProfile::MAX_ITERS * bp5_mf::PhaseProfile::MARKS;
-      while (ph.ev.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ph.ev.push_back(e); }
-      ph.recorded.assign(bp5_mf::PhaseProfile::MAX_ITERS, 0);
-    }
+  ss.phase_on = prm->profile == 2 && prm->variant == BP5_CG_MERGED;
+  if (ss.phase_on) {
+    const size_t want = (size_t)bp5_mf::PhaseProfile::MAX_ITERS * bp5_mf::PhaseProfile::MARKS;
+    while (mf->phase.ev.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->phase.ev.push_back(e); }
   }
-  struct PhaseGuard { bp5_mf *m; ~PhaseGuard() { m->phase.on = false; } } phase_guard{mf};
   const hipEvent_t ev0 = mf->ev_solve[0], ev1 = mf->ev_solve[1];
   // h = A d.  dst is fully defined by the call (the reference zeroes it in update_a* for its atomic scatter)
   auto vmult = [&](double *src, double *dst, const double *fuse_r, uint32_t *n_cols) -> int {
-    if (!user) return solver_vmult(mf, coef, src, dst, true, prof, fuse_r, n_cols);
+    if (!user) return solver_vmult(mf, ss, coef, src, dst, true, fuse_r, n_cols);
     BP5_TRY(prof.mark(0));
     BP5_TRY(prof.mark(1));
     const int st = user(user_ctx, dst, src);
@@ -1987,12 +2003,11 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
   HIP_TRY(hipEventRecord(ev0, s));
   const bool plain = prm->variant == BP5_CG_PLAIN;
   bool fused_dots = false;
-  mf->fuse = bp5_mf::Fuse{}; // (nothing of an earlier, failed solve survives)
   const int check = prm->check_every;
   int status = BP5_OK;
   // fused dot products: whenever the operator resolves to the packed block kernel on all cells of one rank (merged solver: and D == 1;
   // the plain solver takes only d.h = the quadrature-point energy from the kernel, which no preconditioner enters).
-  // Across ranks the fused iteration keeps its dot products in every exchange schedule (solver_vmult): unsplit (bp5_mf_set_overlap 0:
+  // Across ranks the fused iteration keeps its dot products in every exchange schedule (fused_vmult_distributed): unsplit (bp5_mf_set_overlap 0:
   // gather, one launch, combine, scatter-add on the compute stream), boundary-first (1, the reference's setting: the ghost-touching
   // bricks come first, their rows travel to the owners on the communication stream under the interior bricks), and the automatic
   // choice (2): one launch, ghost rows combined first, the exchange under the owned-row combine.
@@ -2010,33 +2025,22 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
       split = possible && mf->overlap == 1;
       if (mf->overlap == 1 && !split) fused_dots = false; // explicit overlap on a mesh that cannot run boundary-first: 3-phase schedule, separate dot products
       // automatic: one launch, ghost rows combined first, exchange under the owned-row combine (needs the run-length combine windows)
-      late = fused_dots && mf->overlap == 2 && (dp->n_shared == 0 || (dp->cr_tile && !mf->combine_csr));
+      late = fused_dots && mf->overlap == 2 && (dp->n_shared == 0 || dp->cr_tile); // (variant 56 / 63: the run-length pass wherever its tables exist)
     }
   }
-  struct OverlapGuard { // the fused exchanges choose their streams themselves (solver_vmult), whatever the slab size
-    bp5_mf *m; int saved;
-    ~OverlapGuard() { m->overlap = saved; m->cg_split = false; m->cg_late = false; m->blk_two_parts = false; m->blk_signal = false; }
-  } overlap_guard{mf, mf->overlap};
-  if (fused_dots && dist_solve) mf->overlap = 0;
-  mf->cg_split = split;
-  mf->cg_late = late;
+  ss.exchange = split ? EXCHANGE_BOUNDARY_FIRST : late ? EXCHANGE_GHOST_ROWS_FIRST : EXCHANGE_NONE;
   // whole-range launches of a distributed fused solve walk the ghost-touching bricks first in EITHER exchange schedule: same workgroup
   // ranges, same dot-product columns -- the two schedules then differ only in where the exchange is enqueued and give the same bits
-  mf->blk_two_parts = fused_dots && dist_solve && split_possible;
+  ss.two_parts = fused_dots && dist_solve && split_possible;
   // one rank, separate dot-product kernel: the two small launches around an operator that scatters with atomics fold into their
   // neighbours -- the update kernel stores the zeros the operator needs in h / v (it holds the values in registers for the last time),
   // the dot-product kernel applies the Dirichlet copy while it reads both vectors (bitmap of the Dirichlet DoFs)
   const bool fold_enabled = mf->tune[BP5_TUNE_FOLD_SMALL] != 0; // A/B knob of the handle
   const bool fold_small = fold_enabled && !fused_dots && !user && !dist_solve;
   const bool prezero = fold_small && mf->n_ghost == 0 && !variant_overwrites(mf, effective_variant(mf, 0, mf->n_cells)); // (the update kernels cover owned entries)
-  struct FoldGuard { bp5_mf *m; ~FoldGuard() { m->solver_prezeroed = m->solver_copies_dirichlet = false; } } fold_guard{mf};
-  auto folded_vmult = [&](double *src, double *dst) -> int { // the operator between a zero-storing update and a copying dot-product kernel
-    mf->solver_prezeroed = prezero;
-    mf->solver_copies_dirichlet = fold_small;
-    const int st_v = vmult(src, dst, nullptr, nullptr);
-    mf->solver_prezeroed = mf->solver_copies_dirichlet = false;
-    return st_v;
-  };
+  // (the operator then sits between a zero-storing update and a copying dot-product kernel; neither holds for a fused application)
+  ss.dst_prezeroed = prezero;
+  ss.copies_dirichlet = fold_small;
 
   if (plain) {
     // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381)
@@ -2053,7 +2057,7 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
         BP5_TRY(vmult(d, h, nullptr, &n_cols)); // (no residual vector: the write-out does not read g)
         hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, (int)n_cols, mf->d_sc + SC_DH, mf->d_st);
       } else {
-        BP5_TRY(folded_vmult(d, h));
+        BP5_TRY(vmult(d, h, nullptr, nullptr));
         if (fold_small) hipLaunchKernelGGL(cg_dh_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_partials, (const uint32_t *)mf->d_constrained_bits);
         else hipLaunchKernelGGL(dot_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_partials);
         hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_DH, mf->d_st);
@@ -2065,7 +2069,7 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
       KERNEL_CHECK();
       BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
       hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-      if (mf->cg_history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, mf->cg_history, mf->cg_history_cap);
+      if (history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, history, history_cap);
       hipLaunchKernelGGL(cg_direction_kernel, dim3(stream_grid_flat(mf, n, 2)), dim3(VB), 0, s, d, g, diag, n, mf->d_sc, mf->d_st);
       KERNEL_CHECK();
       if (check > 0 && it % check == 0 && it < prm->max_iter) {
@@ -2119,36 +2123,36 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
     int it = 1;
     for (; it <= prm->max_iter; ++it) {
       const int mode = it == 1 ? 0 : it % 2 == 0 ? 1 : 2;
-      BP5_TRY(phase_mark(mf, 0));
-      if (early_gather) { BP5_TRY(gather_under_update(mode)); mf->fuse.gather_in_flight = true; }
+      BP5_TRY(phase_mark(mf, ss, 0));
+      if (early_gather) { BP5_TRY(gather_under_update(mode)); ss.gather_in_flight = true; }
       if (mode != 0) launch_update(mode); // (mode 0, p = -D r: written by cgm_init_kernel already)
       KERNEL_CHECK();
-      BP5_TRY(phase_mark(mf, 1));
+      BP5_TRY(phase_mark(mf, ss, 1));
       const bool one_launch = fused && !mf->comm; // no all-reduce between the local sums and the scalar step
       if (fused) {
         uint32_t n_cols = 0;
         BP5_TRY(vmult(d, h, g, &n_cols));
-        BP5_TRY(phase_mark(mf, 4));
+        BP5_TRY(phase_mark(mf, ss, 4));
         if (one_launch) hipLaunchKernelGGL(cgm_finalize4_kernel<true>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
         else hipLaunchKernelGGL(cgm_finalize4_kernel<false>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
       } else {
-        BP5_TRY(folded_vmult(d, h)); // (h: zeroed by cgm_init_kernel before the first, by the update kernel before every later application)
-        BP5_TRY(phase_mark(mf, 4));
+        BP5_TRY(vmult(d, h, nullptr, nullptr)); // (h: zeroed by cgm_init_kernel before the first, by the update kernel before every later application)
+        BP5_TRY(phase_mark(mf, ss, 4));
         hipLaunchKernelGGL(cgm_dots_kernel, dim3(grid2), dim3(VB), 0, s, d, g, h, diag, n, mf->d_st, mf->d_partials,
                            fold_small ? (const uint32_t *)mf->d_constrained_bits : (const uint32_t *)nullptr);
         hipLaunchKernelGGL(finalize_kernel<7>, dim3(7), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_R0, mf->d_st);
       }
       KERNEL_CHECK();
-      BP5_TRY(phase_mark(mf, 5));
+      BP5_TRY(phase_mark(mf, ss, 5));
       if (!one_launch) {
         BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_R0, 7));
-        BP5_TRY(phase_mark(mf, 6));
+        BP5_TRY(phase_mark(mf, ss, 6));
         hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
         KERNEL_CHECK();
       } else
-        BP5_TRY(phase_mark(mf, 6));
-      BP5_TRY(phase_mark(mf, 7));
-      if (mf->phase.on) ++mf->phase.it;
+        BP5_TRY(phase_mark(mf, ss, 6));
+      BP5_TRY(phase_mark(mf, ss, 7));
+      if (ss.phase_on) ++ss.phase_it;
       if (check > 0 && it % check == 0 && it < prm->max_iter) {
         BP5_TRY(poll_state(mf));
         if (mf->h_st[ST_DONE]) break;
@@ -2189,12 +2193,12 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
   memset(res->apply_kernel, 0, sizeof(res->apply_kernel));
   if (!user) strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
   for (double &v : res->phase_ms) v = 0.0;
-  if (mf->phase.on) { // averages over the stamped iterations after the first (whose update kernel is the cheap update_a0)
+  if (ss.phase_on) { // averages over the stamped iterations after the first (whose update kernel is the cheap update_a0)
     using PP = bp5_mf::PhaseProfile;
-    const int n_it = std::min(mf->phase.it, (int)PP::MAX_ITERS);
+    const int n_it = std::min(ss.phase_it, (int)PP::MAX_ITERS);
     int counted = 0;
     for (int i = n_it > 1 ? 1 : 0; i < n_it; ++i) {
-      const uint8_t rec = mf->phase.recorded[i];
+      const uint8_t rec = ss.phase_recorded[i];
       const uint8_t need = (1u << 0) | (1u << 1) | (1u << 4) | (1u << 5) | (1u << 6) | (1u << 7);
       if ((rec & need) != need) continue;
       auto ms = [&](int a, int b, double &out) -> int {
@@ -2253,9 +2257,9 @@ extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_v
   const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1), gridf = stream_grid_flat(mf, n, 2);
   hipStream_t s = mf->stream;
   double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h, *z = mf->ws_z;
-  ApplyProfile prof{mf, false};
+  SolveState ss{ApplyProfile{mf, false}};
   auto apply_A = [&](double *src, double *dst) -> int {
-    if (!vmult) return solver_vmult(mf, coef, src, dst, true, prof);
+    if (!vmult) return solver_vmult(mf, ss, coef, src, dst, true);
     const int st = vmult(ctx, dst, src);
     return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
   };
@@ -2263,7 +2267,6 @@ extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_v
     const int st = precond(precond_ctx, dst, src);
     return st == BP5_OK ? BP5_OK : fail(st, "the preconditioner's vmult callback reported a failure");
   };
-  mf->fuse = bp5_mf::Fuse{};
   mf->h_sc[SC_TOL] = prm->abs_tol;
   HIP_TRY(hipMemcpyAsync(mf->d_sc + SC_TOL, mf->h_sc + SC_TOL, sizeof(double), hipMemcpyHostToDevice, s));
   mf->h_st[ST_MAXIT] = prm->max_iter;
@@ -2423,15 +2426,12 @@ extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn
     double vnorm = 0.0;
     BP5_TRY(bp5_vec_l2_norm(mf, vb, mf->n_owned, &vnorm));
     HIP_TRY(hipMalloc((void **)&hist, 2 * (size_t)m * sizeof(double)));
-    struct FreeHist { bp5_mf *mf; double *h; ~FreeHist() { mf->cg_history = nullptr; mf->cg_history_cap = 0; hipFree(h); } } hguard{mf, hist};
+    struct FreeHist { double *h; ~FreeHist() { hipFree(h); } } hguard{hist};
     HIP_TRY(hipMemsetAsync(hist, 0, 2 * (size_t)m * sizeof(double), mf->stream));
-    mf->cg_history = hist;
-    mf->cg_history_cap = m;
     bp5_cg_params cp{};
     cp.variant = BP5_CG_PLAIN; cp.max_iter = m; cp.abs_tol = 1e-5 * vnorm; cp.check_every = 0; cp.profile = 0;
     bp5_cg_result cr{};
-    BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr));
-    mf->cg_history = nullptr;
+    BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr, hist, m));
     std::vector<double> h(2 * (size_t)m);
     HIP_TRY(hipMemcpy(h.data(), hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int k = cr.iterations;

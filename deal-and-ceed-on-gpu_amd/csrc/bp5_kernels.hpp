@@ -1314,6 +1314,16 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #ifndef BP5_WAVE_PACK
 #define BP5_WAVE_PACK 1
 #endif
+// Build bits of the block kernel (the ABL template argument of BlockPass / apply_block_kernel; what each selects is described at the
+// BlockPass member of the same name).  Bits below 1024 are timing-only ablations (no write-out, no metric loads, no gather ...).  The
+// pencil and team kernels read the AFFINE, HANG and HELM bits of their own mask with the same meaning.
+enum : int {
+  BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_PACK = 262144,
+  BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
+  BLK_ROLL = 67108864, BLK_CARRY = 268435456,
+  // the default shape: metric loaded in its own pass, sequential tiles, run-length write-out, packed indices
+  BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK
+};
 template <int P, bool COLL, int LPC, int SCATTER, int ABL>
 struct BlockPass {
   static constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;

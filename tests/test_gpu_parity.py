@@ -1118,6 +1118,72 @@ def test_solvers_take_any_operator_with_vmult(solver_name):
         getattr(pkg, solver_name)(pkg.IterationNumberControl(3, 0.0)).solve(Broken(), x, b, pkg.DiagonalMatrix())
 
 
+def test_a_failed_solve_leaves_nothing_behind_on_the_handle():
+    """What a solve decides for itself (exchange schedule, fused dot products, phase stamps, the folded zero-fill and Dirichlet copy) ends
+    with the solve, also when the solve fails half-way: a SolverCGFullMerge(profile=2) solve whose operator raises on its third vmult,
+    then the built-in solve on the SAME handle in every exchange schedule -- not one bit and not one reported property differs from the
+    same solves on a fresh handle.  The handle: the slab with a ghost plane and a self neighbour of
+    test_block_kernel_behind_the_halo_exchange (block kernel, dot products fused across the exchange)."""
+    from types import SimpleNamespace
+    torch = _t()
+    p, cells = 4, (9, 8, 10)
+
+    def make():
+        m1 = pkg.BrickMesh(p, cells, deform_amp=0.03, rank=1, n_ranks=2, cell_block=(4, 4, 4), dof_numbering=1, cell_block_order=1)
+        ng, no = m1.n_ghost, m1.n_owned
+        mesh = SimpleNamespace(degree=p, n=p + 1, cells=cells, n_cells=m1.n_cells, n_interior_cells=m1.n_interior_cells, n_owned=no, n_ghost=ng,
+                               n_local=no + ng, n_global_dofs=no, l2g=m1.l2g, coords=m1.coords, global_ids=m1.global_ids, constrained=m1.constrained,
+                               cell_block_offsets=m1.cell_block_offsets, rank=0, n_ranks=1, h=1.0, deform_amp=0.03,
+                               n_neighbors=1, neighbor_rank=np.zeros(1, np.int32), send_offsets=np.asarray([0, ng], np.uint32),
+                               send_indices=_consistent_self_glue(m1), recv_offsets=np.asarray([0, ng], np.uint32))
+        comm = pkg.Communicator(0, 1)
+        op = pkg.PoissonOperator(mesh, 0, pkg.COEF_STEP64, comm=comm)
+        op.mf_data.set_apply_variant(56)
+        op.mf_data.set_block_workgroups(8)
+        return op, comm
+
+    def builtin_solves(op, b):
+        L, h, out = pkg.lib(), op.mf_data.handle, []
+        for overlap in (1, 2, 0):
+            assert L.bp5_mf_set_overlap(h, overlap) == 0
+            x = op.initialize_dof_vector()
+            ctl = pkg.IterationNumberControl(10, 0.0)
+            pkg.SolverCGFullMerge(ctl).solve(op, x, b, pkg.DiagonalMatrix())
+            out.append((x, ctl.exchange_schedule, ctl.dot_products_fused, ctl.apply_kernel, ctl.last_step()))
+        return out
+
+    op, comm = make()
+    b = op.assemble_rhs()                      # (assembled once: the right-hand side is summed with atomics, its last bits vary from call to call)
+    fresh = builtin_solves(op, b)
+    assert [(f[1], f[2]) for f in fresh] == [(2, True), (4, True), (1, True)]
+    op.mf_data.synchronize()
+    op.mf_data.close()
+    comm.close()
+
+    op, comm = make()
+
+    class FailsOnThirdVmult:
+        mf_data = op.mf_data
+        calls = 0
+
+        def vmult(self, dst, src):
+            FailsOnThirdVmult.calls += 1
+            if FailsOnThirdVmult.calls == 3:
+                raise ValueError("operator failure")
+            op.vmult(dst, src)
+
+    assert pkg.lib().bp5_mf_set_overlap(op.mf_data.handle, 1) == 0
+    with pytest.raises(ValueError):            # (the binding turns the exception into status 1: the solve returns at once)
+        pkg.SolverCGFullMerge(pkg.IterationNumberControl(10, 0.0), profile=2).solve(FailsOnThirdVmult(), op.initialize_dof_vector(),
+                                                                                   b, pkg.DiagonalMatrix())
+    assert FailsOnThirdVmult.calls == 3
+    for again, first in zip(builtin_solves(op, b), fresh):
+        assert torch.equal(again[0], first[0]) and again[1:] == first[1:]
+    op.mf_data.synchronize()
+    op.mf_data.close()
+    comm.close()
+
+
 def test_p4_variable_coefficient_deformed_cg_golden():
     z = np.load(os.path.join(G, "p4_kappa_deformed_cg.npz"))
     op = pkg.PoissonOperator(pkg.BrickMesh(4, (4, 3, 3), h=0.25, deform_amp=0.04), 0, pkg.COEF_STEP64)
@@ -1509,7 +1575,7 @@ def _consistent_self_glue(m1):
     return send
 
 
-@pytest.mark.parametrize("variant,neighbours", [(56, 1), (3, 1), (56, 2)])
+@pytest.mark.parametrize("variant,neighbours", [(56, 1), (3, 1), (56, 2), (48, 1)])
 def test_block_kernel_behind_the_halo_exchange(variant, neighbours):
     """The bench's rank-local configuration for ranks > 0 (brick-ordered slab mesh with a ghost plane, block kernel with
     packed indices, overwrite mode) inside bp5_apply_distributed with real RCCL traffic (self neighbour): equals the
@@ -1550,6 +1616,21 @@ def test_block_kernel_behind_the_halo_exchange(variant, neighbours):
         assert L.bp5_apply_distributed(h, ptr(op.coef), ptr(s_in), ptr(d), 1) == 0
         outs.append(d)
     assert float((outs[1] - outs[0]).abs().max()) < 1e-12 * float(outs[0].abs().max())
+    if variant == 48:
+        # 48 = 56 with the per-DoF CSR combine pass in place of the run-length one, for the immediate pass (sequential schedule) and for
+        # the deferred one (phased schedule) alike; both passes add a DoF's slots in team order: not one bit of v differs from variant 56
+        for overlap in (1, 0):
+            assert L.bp5_mf_set_overlap(h, overlap) == 0
+            pair = []
+            for v in (56, 48):
+                op.mf_data.set_apply_variant(v)
+                d = op.initialize_dof_vector()
+                d.fill_(float("nan"))
+                s_in = src.clone()
+                assert L.bp5_apply_distributed(h, ptr(op.coef), ptr(s_in), ptr(d), 1) == 0
+                pair.append(d)
+            assert torch.equal(pair[0], pair[1]), overlap
+        assert L.bp5_mf_set_overlap(h, 1) == 0
     # the overlapped 3-phase schedule (default, the reference's overlap_communication_computation, bp5/step-64.cu:241:
     # exchange on the communication stream under the interior bricks, ghost-touching bricks after it) against the
     # sequential one (overlap off: exchange and one unsplit launch on the compute stream).  Same kernels, same
