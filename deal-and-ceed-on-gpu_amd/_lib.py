@@ -176,6 +176,8 @@ def lib():
         "bp5_mf_set_overlap": (i32, [vp, i32]),
         "bp5_mf_set_cg_fusion": (i32, [vp, i32]),
         "bp5_mf_set_operator": (i32, [vp, i32]),
+        "bp5_mf_set_metric_precision": (i32, [vp, i32]),
+        "bp5_mf_get_metric_precision": (i32, [vp, C.POINTER(C.c_int)]),
         "bp5_mf_block_plan_lattice": (i32, [vp, vp]),
         "bp5_mf_block_plan_carry": (i32, [vp, vp, vp, vp]),
         "bp5_halo_scatter_add": (i32, [vp, vp]),

@@ -227,12 +227,37 @@ extern "C" int bp5_mf_coef_size(const bp5_mf *mf, size_t *n)
 {
   if (!mf || !n) return fail(BP5_ERR_INVALID, "null argument");
   *n = (size_t)mf->n_planes() * mf->n_cells * mf->n3;
+  if (mf->f32_metric()) *n = (*n + 1) / 2; // float entries: the doubles that hold them
   mf->coef_planes_committed = mf->n_planes();
+  return BP5_OK;
+}
+extern "C" int bp5_mf_set_metric_precision(bp5_mf *mf, int precision)
+{
+  if (!mf) return fail(BP5_ERR_INVALID, "null handle");
+  if (precision != BP5_METRIC_F64 && precision != BP5_METRIC_F32) return fail(BP5_ERR_INVALID, "unknown metric precision");
+  if (precision == mf->metric_precision) return BP5_OK;
+  if (mf->coef_planes_committed)
+    return fail(BP5_ERR_INVALID, "the metric array of this handle has been sized or filled in another precision: set the metric precision before bp5_mf_coef_size / bp5_mf_compute_merged_metric");
+  if (precision == BP5_METRIC_F32) {
+    if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: meshes with hanging nodes keep double planes");
+    if (mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the Helmholtz operator keeps double planes");
+    if (mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the affine geometry mode has no six-plane stream to shrink");
+    if (mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
+  }
+  mf->metric_precision = precision;
+  mf->auto_block = -1; // (decided per precision: the FP32 block builds need the packed indices at every degree)
+  return BP5_OK;
+}
+extern "C" int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision)
+{
+  if (!mf || !precision) return fail(BP5_ERR_INVALID, "null argument");
+  *precision = mf->metric_precision;
   return BP5_OK;
 }
 extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
 {
   if (!mf || (op != BP5_OP_POISSON && op != BP5_OP_HELMHOLTZ)) return fail(BP5_ERR_INVALID, "unknown operator");
+  if (op == BP5_OP_HELMHOLTZ && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator keeps double metric planes (bp5_mf_set_metric_precision)");
   if (op == BP5_OP_HELMHOLTZ && (mf->has_hanging || mf->geometry_mode == BP5_GEOM_AFFINE))
     return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs a conforming mesh and the six-plane geometry (hanging nodes: the facade's FEEvaluation)");
   if (op == BP5_OP_HELMHOLTZ && mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 and 56");
@@ -270,6 +295,7 @@ extern "C" int bp5_mf_set_apply_variant(bp5_mf *mf, int v)
     return BP5_OK;
   }
   if (v == 90) return fail(BP5_ERR_INVALID, "apply variant 90 is the hanging-node kernel: the mesh has no constraint masks");
+  if (mf->f32_metric() && v != 0 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
 #ifndef BP5_TIMING_BUILDS
   if (mf->operator_kind == BP5_OP_HELMHOLTZ && v != 0 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
 #endif
@@ -346,8 +372,12 @@ static int launch_geometry(bp5_mf *mf, GeomOut o)
   const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
   o.hang_mask = mf->has_hanging ? mf->d_hang_mask : nullptr;
   o.hang_I = mf->d_hang_I;
-  hipLaunchKernelGGL(geometry_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient,
-                     mf->n_cells, o);
+  if (o.coef && mf->f32_metric()) // float planes behind o.coef (affine / Data-mirror launches write no planes: the double build)
+    hipLaunchKernelGGL((geometry_kernel<n, float>), dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient,
+                       mf->n_cells, o);
+  else
+    hipLaunchKernelGGL(geometry_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient,
+                       mf->n_cells, o);
   KERNEL_CHECK();
   return BP5_OK;
 }
@@ -370,6 +400,7 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
   if (mode != BP5_GEOM_MERGED6 && mode != BP5_GEOM_AFFINE) return fail(BP5_ERR_INVALID, "unknown geometry mode");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mode == BP5_GEOM_AFFINE && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes need the six-plane geometry (the affine mode has no six-plane stream to shrink)");
   if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs the six-plane geometry");
   if (mode == BP5_GEOM_AFFINE && mf->has_hanging && mf->apply_variant == 56) return fail(BP5_ERR_UNSUPPORTED, "hanging nodes in the affine geometry mode run the pencil kernel: set apply variant 0 or 90 first");
   if (mode == BP5_GEOM_AFFINE && !mf->d_scalar_plane) {
@@ -415,8 +446,12 @@ template <int n>
 static int launch_permute(bp5_mf *mf, const double *in, double *out)
 {
   const uint64_t total = (uint64_t)mf->n_planes() * mf->n_cells * mf->n3;
-  hipLaunchKernelGGL(metric_permute_kernel<n>, dim3(2048), dim3(256), 0, mf->stream, in, out, total, (uint64_t)mf->n_cells, mf->coef_plane_stride,
-                     mf->coef_cell_stride);
+  if (mf->f32_metric())
+    hipLaunchKernelGGL((metric_permute_kernel<n, float>), dim3(2048), dim3(256), 0, mf->stream, reinterpret_cast<const float *>(in), out, total, (uint64_t)mf->n_cells,
+                       mf->coef_plane_stride, mf->coef_cell_stride);
+  else
+    hipLaunchKernelGGL(metric_permute_kernel<n>, dim3(2048), dim3(256), 0, mf->stream, in, out, total, (uint64_t)mf->n_cells, mf->coef_plane_stride,
+                       mf->coef_cell_stride);
   KERNEL_CHECK();
   return BP5_OK;
 }
@@ -1030,6 +1065,10 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
   if (v != 0) return v;
   if (mf->has_hanging && mf->geometry_mode == BP5_GEOM_AFFINE) return 90;
   uint32_t b0, b1;
+  if (mf->f32_metric()) { // FP32 planes: the degree's pencil kernel, or the block kernel under the conditions of the double planes (packed indices at every degree)
+    if (!block_lpc(mf->degree) || mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0, &b1)) return 0;
+    return block_kernel_pays(mf, c0, c1, b0, b1, mf->degree <= 4 ? 3 : 2, true) ? 56 : 0;
+  }
   if (mf->operator_kind == BP5_OP_HELMHOLTZ || mf->has_hanging) { // pencil kernel, or the block kernel (two workgroups per CU, packed indices)
     const int pencil = mf->has_hanging ? 90 : 0;
     if (!block_lpc(mf->degree) || mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0, &b1)) return pencil;
@@ -1147,6 +1186,10 @@ static int launch_diagonal(bp5_mf *mf, const double *coef, double *diag)
 {
   const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65536u);
   const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
+  if (mf->f32_metric()) // (conforming, six planes: bp5_mf_set_metric_precision refuses everything else)
+    hipLaunchKernelGGL((diagonal_kernel<n, float>), dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, reinterpret_cast<const float *>(coef), mf->coef_plane_stride,
+                       mf->coef_cell_stride, (const double *)nullptr, mf->d_tab, mf->n_cells, diag, (const uint32_t *)nullptr, mf->n_planes());
+  else
   hipLaunchKernelGGL(diagonal_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, affine ? mf->d_scalar_plane : coef,
                      affine ? (uint64_t)mf->n_cells * mf->n3 : mf->coef_plane_stride, mf->coef_cell_stride, affine ? mf->d_gcell : (const double *)nullptr, mf->d_tab, mf->n_cells, diag,
                      mf->has_hanging ? (const uint32_t *)mf->d_hang_mask : (const uint32_t *)nullptr, mf->n_planes());
@@ -2013,7 +2056,7 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
   // choice (2): one launch, ghost rows combined first, the exchange under the owned-row combine.
   const bool dist_solve = mf->comm && !mf->neighbors.empty();
   bool split = false, split_possible = false, late = false;
-  if (!user && mf->cg_fusion && (plain || !diag) && block_lpc(mf->degree) != 0 && mf->geometry_mode == BP5_GEOM_MERGED6 &&
+  if (!user && mf->cg_fusion && !mf->f32_metric() /* no fused build reads float planes */ && (plain || !diag) && block_lpc(mf->degree) != 0 && mf->geometry_mode == BP5_GEOM_MERGED6 &&
       (effective_variant(mf, 0, mf->n_cells) == 56 || (mf->degree == 4 && effective_variant(mf, 0, mf->n_cells) == 63))) {
     bp5_mf::DevPlan *dp = nullptr;
     BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));

@@ -55,6 +55,11 @@ struct bp5_mf {
   int operator_kind = 0; // BP5_OP_POISSON | BP5_OP_HELMHOLTZ (seven planes: six merged + the mass plane a JxW)
   mutable int coef_planes_committed = 0; // planes of the metric array the caller has sized (bp5_mf_coef_size) or filled: set_operator may not change the count afterwards
   int n_planes() const { return operator_kind == BP5_OP_HELMHOLTZ ? 7 : 6; }
+  // BP5_METRIC_F64 | BP5_METRIC_F32 (bp5_mf_set_metric_precision): entry type of the merged-metric planes behind every `coef` argument.  F32: the
+  // same pair layout with float entries (coef_plane_stride / coef_cell_stride then count floats), read by the BLK_F32M builds of the pencil
+  // and block kernel; fixed once the array has been sized or filled (coef_planes_committed)
+  int metric_precision = BP5_METRIC_F64;
+  bool f32_metric() const { return metric_precision == BP5_METRIC_F32; }
   int block_max_wg = 0; // 0: persistent grid sized from the CU count; > 0: cap (tests force several blocks per workgroup)
   int streaming = -1; // bp5_mf_set_streaming: -1 chosen by size, 0 ordinary accesses, 1 non-temporal accesses to once-used data
   int auto_team = -1;  // -1 not decided; 1: the x-row team plan could be built (p = 1, 3 default)
@@ -607,6 +612,33 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
   const uint32_t c0 = call.c0, c1 = call.c1;
   const bool overwrite = call.overwrite;
   const bool coll = mf->quadrature == BP5_QUAD_GLL;
+  if (mf->f32_metric()) {
+    // FP32 metric planes (bp5_mf_set_metric_precision): the BLK_F32M builds of what the dispatch picks for an unfused application of the Poisson
+    // operator on six planes -- variant 56: the block kernel's default shape (packed indices; lattice blocks in closed form, with the face carry
+    // at p = 4), cell ranges and two-part launches included; variant 0: the degree's default pencil kernel.  Ordinary (not non-temporal) metric
+    // loads in every build: the results are the same bits either way
+    if (mf->operator_kind != BP5_OP_POISSON || mf->has_hanging || mf->geometry_mode != BP5_GEOM_MERGED6)
+      return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: Poisson operator on a conforming mesh with the six-plane geometry only");
+    if (call.fuse) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: no fused dot products");
+    if (c1 <= c0) { if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); return BP5_OK; }
+    if (call.variant == 56) {
+      if constexpr (block_lpc(DEG) != 0) {
+        constexpr int LPCB = block_lpc(DEG);
+        if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
+        bp5_mf::DevPlan *dp_ = nullptr;
+        BP5_TRY(get_plan_raw(mf, -(256 / LPCB), &dp_));
+        if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: variant 56 needs packed indices (<= 128 runs per cell block)");
+        constexpr int LATF = DEG == 4 ? (BLK_LATT | BLK_CARRY) : BLK_LATT; // (the face carry exists at p = 4, as for double planes)
+        if (dp_->lattice && dp_->n_lattice_blocks == dp_->n_groups) return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | LATF | BLK_F32M), coef, src, dst, overwrite);
+        return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_F32M), coef, src, dst, overwrite);
+      }
+    }
+    if (call.variant != 0) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
+    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+    constexpr int n2f = (DEG + 1) * (DEG + 1);
+    constexpr int TWF = DEG <= 3 ? 1 : 4, TPBF = DEG <= 3 ? 4 : 1; // the shapes of APPLY_CASE(P, 0, ...)
+    return LAUNCH_COLL(launch_apply_t, DEG, (TWF, n2f, TPBF, true, BLK_F32M), coef, src, dst, c0, c1);
+  }
   if (mf->operator_kind == BP5_OP_HELMHOLTZ) {
     // step-64's Helmholtz operator (step-64/step-64.cu:154-160,201-219) as a build of the same fused kernels: the degree's default pencil
     // shape (any mesh), or the deterministic block kernel on cell bricks (variant 56; with the CG dot products fused when the solver asks)

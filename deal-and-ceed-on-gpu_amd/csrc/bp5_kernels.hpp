@@ -61,6 +61,26 @@ __device__ __forceinline__ void load_pencil(const double *base, int ab, double (
   if constexpr (n & 1) S[n - 1] = NT ? __builtin_nontemporal_load(base + (n / 2) * (2 * n * n) + ab) : base[(n / 2) * (2 * n * n) + ab];
 }
 
+// FP32 metric planes (bp5_mf_set_metric_precision, builds with ABL & BLK_F32M): the SAME pair layout with float entries -- offsets and strides
+// count floats, a lane fetches 8 bytes per load, a wave's load is one contiguous run of n^2 * 8 bytes per cell.  The pencil stays float in
+// registers (half the VGPRs of the double pencil); the quadrature-point loop widens each entry where it uses it (exact), all arithmetic is double.
+typedef float bp5_f2u __attribute__((ext_vector_type(2), aligned(4))); // 8-byte load from a 4-byte aligned address
+template <int n, bool NT = false>
+__device__ __forceinline__ void load_pencil(const float *base, int ab, float (&S)[n])
+{
+#pragma unroll
+  for (int m = 0; m < n / 2; ++m) {
+    const bp5_f2u *q = reinterpret_cast<const bp5_f2u *>(base + m * (2 * n * n) + 2 * ab);
+    const bp5_f2u v = NT ? __builtin_nontemporal_load(q) : *q;
+    S[2 * m] = v.x;
+    S[2 * m + 1] = v.y;
+  }
+  if constexpr (n & 1) S[n - 1] = NT ? __builtin_nontemporal_load(base + (n / 2) * (2 * n * n) + ab) : base[(n / 2) * (2 * n * n) + ab];
+}
+// build bit of the fused operator kernels (pencil and block kernel; the ABL template argument): the metric planes are float
+constexpr int BLK_F32M = 536870912;
+template <int ABL> using metric_t = typename std::conditional<(ABL & BLK_F32M) != 0, float, double>::type;
+
 // pieces of load_pencil: pair m (qi = 2m, 2m + 1) and the unpaired last qi of an odd n -- the rolling metric prefetch of the block kernel
 // (BlockPass::ROLL) refills a pencil piece by piece, each piece right after the quadrature-point loop has consumed it
 template <int n, bool NT = false>
@@ -82,8 +102,8 @@ struct ApplyArgs {
   const double *coef;
   const double *src;
   double *dst;
-  uint64_t plane_stride; // doubles between two planes of one cell: n_cells_total * n^3 (plane-major) or n^3 (cell-major)
-  uint64_t cell_stride;  // doubles between two cells of one plane: n^3 (plane-major, affine scalar plane) or 6 n^3 (cell-major)
+  uint64_t plane_stride; // entries (doubles; floats on an FP32-metric handle) between two planes of one cell: n_cells_total * n^3 (plane-major) or n^3 (cell-major)
+  uint64_t cell_stride;  // entries between two cells of one plane: n^3 (plane-major, affine scalar plane) or 6 n^3 (cell-major)
   uint32_t cell_begin, cell_end;
   uint32_t n_teams;      // teams needed for the range
   uint32_t teams_per_xcd;
@@ -348,15 +368,17 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
     }
   }
   // ---- metric planes (x-owner: a_ = j, b_ = k; registers hold i), layout [c][cell][i][j+n k]
-  const double *cf = a.coef + cell * a.cell_stride; // cell base; lane offsets through coef_off / load_pencil
+  using MT = metric_t<ABL>; // plane entries: double, or float on an FP32-metric handle (BLK_F32M)
+  const MT *cf = reinterpret_cast<const MT *>(a.coef) + cell * a.cell_stride; // cell base; lane offsets through coef_off / load_pencil
   constexpr bool AFFINE = (ABL & 1024) != 0; // affine geometry: one scalar plane + six per-cell numbers
   // HELM: step-64's Helmholtz operator (grad v, grad u) + (v, a u) (step-64/step-64.cu:154-160,201-219): evaluate(true, true) /
   // integrate(true, true) cost ONE more 1-D contraction each way (the value path shares the y- and z-contractions with the x-derivative),
   // submit_value(a * get_value()) one more plane: a(x_q) JxW behind the six merged planes
   constexpr bool HELM = (ABL & 8388608) != 0;
   static_assert(!HELM || (PF && !AFFINE), "Helmholtz build: prefetched planes, six-plane geometry");
+  static_assert((ABL & BLK_F32M) == 0 || (!HELM && !AFFINE), "FP32 metric planes: Poisson operator, six-plane geometry");
   constexpr int NPL = HELM ? 7 : 6;
-  double S[(PF && !AFFINE) ? NPL : 1][n];
+  MT S[(PF && !AFFINE) ? NPL : 1][n];
   double um[HELM ? n : 1]; // HELM: u at the quadrature points of this lane's x-pencil, then a JxW u
   double Gc[6] = {0, 0, 0, 0, 0, 0};
   if constexpr (AFFINE) {
@@ -1267,11 +1289,11 @@ struct BlockPlan {
 };
 
 // register set of one pass (cell ids, positions, gathered values, metric)
-template <int n, bool AFFINE, int NPL = 6, bool ROLL = false>
+template <int n, bool AFFINE, int NPL = 6, bool ROLL = false, typename MT = double>
 struct PassRegs {
   uint16_t ps[n];
   double u[n];
-  double S[(AFFINE || ROLL) ? 1 : NPL][ROLL ? 1 : n]; // affine: one scalar plane ... (NPL = 7: the Helmholtz build's mass plane behind the six merged ones; ROLL: the metric lives in ONE register set shared by all passes)
+  MT S[(AFFINE || ROLL) ? 1 : NPL][ROLL ? 1 : n]; // affine: one scalar plane ... (NPL = 7: the Helmholtz build's mass plane behind the six merged ones; ROLL: the metric lives in ONE register set shared by all passes)
   double Gc[AFFINE ? 6 : 1];   // ... and the cell's constant K K^T
   uint32_t idx[n];
   uint32_t ent; // pass_cell entry
@@ -1320,7 +1342,7 @@ __device__ __forceinline__ unsigned long long stamp_now()
 enum : int {
   BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_PACK = 262144,
   BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
-  BLK_ROLL = 67108864, BLK_CARRY = 268435456,
+  BLK_ROLL = 67108864, BLK_CARRY = 268435456, // (BLK_F32M = 536870912: FP32 metric planes, defined next to load_pencil)
   // the default shape: metric loaded in its own pass, sequential tiles, run-length write-out, packed indices
   BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK
 };
@@ -1350,7 +1372,11 @@ struct BlockPass {
   // at 168 registers it spills and takes 4.73 -- this kernel lives on its twelve waves per CU, not on its prefetch depth.  Kept for libbp5_timing.so
   static constexpr bool ROLL = (ABL & 67108864) != 0;
   static_assert(!ROLL || (((ABL & 2048) != 0) && ((ABL & 8192) != 0) && !AFFINE), "rolling prefetch: single-buffered build, sequential tiles, plane geometry");
-  using R = PassRegs<n, AFFINE, NPL, ROLL>;
+  // F32M: the metric planes are float (bp5_mf_set_metric_precision): half the bytes of the stream this kernel lives on; the pencils stay float in
+  // registers until the quadrature-point loop widens them, the arithmetic is double as in every other build
+  using MT = metric_t<ABL>;
+  static_assert((ABL & BLK_F32M) == 0 || (!AFFINE && !HELM && !ROLL && (ABL & 1048576) == 0), "FP32 metric planes: Poisson operator, six-plane geometry, no fused dot products");
+  using R = PassRegs<n, AFFINE, NPL, ROLL, MT>;
   // all lanes of a cell slot sit in one wave when LPC divides 64: the tile exchanges then need no block barrier
   // WPACK (round 4, p = 2): 9 lanes per cell do not divide a wave, but SEVEN whole cells fit one (63 lanes) and 4 x 7 = 28 = 256 / 9 cells fill the pass
   // all the same: with the cells packed wave by wave no cell spans two waves, every tile exchange is wave-local again (no workgroup barrier, no second
@@ -1429,7 +1455,7 @@ struct BlockPass {
   {
     if constexpr (ROLL) return;
     const uint64_t cell = r.ent & 0x7fffffffu;
-    const double *cf = a.coef + cell * a.cell_stride; // cell base (pair layout, load_pencil)
+    const MT *cf = reinterpret_cast<const MT *>(a.coef) + cell * a.cell_stride; // cell base (pair layout, load_pencil)
     if constexpr (AFFINE) {
       load_pencil<n>(cf, abm, r.S[0]);
 #pragma unroll
@@ -2555,7 +2581,9 @@ __device__ __forceinline__ double invert3(const double (&J)[3][3], double (&K)[3
 }
 
 // == JacobianFunctor (bp5/step-64.cu:84-114) fused with the geometry part of MatrixFree::reinit
-template <int n>
+// MT: entry type of the merged-metric planes behind o.coef (float on an FP32-metric handle: every entry is computed in double exactly as for
+// double planes and rounded ONCE, to nearest, when it is stored; strides count entries)
+template <int n, typename MT = double>
 __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, const double *coords, const double *tab,
                                                           int kappa_mode, uint32_t n_cells, GeomOut o)
 {
@@ -2577,14 +2605,14 @@ __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, 
     if (o.coef) {
       const double kap = kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
       const double s = o.helmholtz ? jxw : jxw * kap;
-      double *c = o.coef + cell * o.cell_stride + coef_off<n>(i, j + n * k); // pair layout (coef_off)
-      if (o.helmholtz) c[6 * o.plane_stride] = jxw * kap;
-      c[0 * o.plane_stride] = s * (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]);
-      c[1 * o.plane_stride] = s * (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]);
-      c[2 * o.plane_stride] = s * (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]);
-      c[3 * o.plane_stride] = s * (K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2]);
-      c[4 * o.plane_stride] = s * (K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2]);
-      c[5 * o.plane_stride] = s * (K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2]);
+      MT *c = reinterpret_cast<MT *>(o.coef) + cell * o.cell_stride + coef_off<n>(i, j + n * k); // pair layout (coef_off)
+      if (o.helmholtz) c[6 * o.plane_stride] = (MT)(jxw * kap);
+      c[0 * o.plane_stride] = (MT)(s * (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]));
+      c[1 * o.plane_stride] = (MT)(s * (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]));
+      c[2 * o.plane_stride] = (MT)(s * (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]));
+      c[3 * o.plane_stride] = (MT)(s * (K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2]));
+      c[4 * o.plane_stride] = (MT)(s * (K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2]));
+      c[5 * o.plane_stride] = (MT)(s * (K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2]));
     }
     if (o.scalar) {
       double Gq[6] = {K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2], K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2],
@@ -2619,8 +2647,9 @@ __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, 
 }
 
 // permute merged metric between the device layout (x slowest) and the reference layout
-template <int n>
-__global__ void metric_permute_kernel(const double *in, double *out, uint64_t total /*6*n_cells*n3*/, uint64_t n_cells, uint64_t plane_stride,
+// (MT: entry type of the device planes; the reference layout is always double -- float entries widened, exactly)
+template <int n, typename MT = double>
+__global__ void metric_permute_kernel(const MT *in, double *out, uint64_t total /*6*n_cells*n3*/, uint64_t n_cells, uint64_t plane_stride,
                                       uint64_t cell_stride)
 {
   constexpr int n2 = n * n, n3 = n2 * n;
@@ -2670,8 +2699,9 @@ __global__ void __launch_bounds__(n *n *n) rhs_kernel(const uint32_t *l2g, const
 // N*N, D*D, N*D as 1-D factors (six transposed tensor contractions per cell).  Setup-time kernel: one block per cell,
 // one thread per local DoF.  coef: the handle's six planes (device layout, q index = a*n*n + b + n*c), or, in affine
 // mode (gcell != NULL), the scalar plane times the cell's constant K K^T.
-template <int n>
-__global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, const double *coef, uint64_t plane_stride, uint64_t cell_stride, const double *gcell,
+// MT: entry type of the planes (float on an FP32-metric handle; widened on load, the arithmetic is double)
+template <int n, typename MT = double>
+__global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, const MT *coef, uint64_t plane_stride, uint64_t cell_stride, const double *gcell,
                                                           const double *tab, uint32_t n_cells, double *diag, const uint32_t *hang_mask, int n_planes = 6)
 {
   constexpr int n2 = n * n, n3 = n2 * n;

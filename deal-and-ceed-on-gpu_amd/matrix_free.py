@@ -157,6 +157,21 @@ class MatrixFree:
         """OP_POISSON (bp5/step-64.cu:147-194, default) or OP_HELMHOLTZ (step-64/step-64.cu:154-160,201-219: seven planes)."""
         _lib.check(_lib.lib().bp5_mf_set_operator(self.handle, int(op)))
 
+    METRIC_PRECISION = {"float64": 0, "float32": 1}   # bp5.h: BP5_METRIC_*
+
+    def set_metric_precision(self, precision):
+        """"float64" (default) or "float32": storage type of the merged-metric planes (bp5_mf_set_metric_precision; arithmetic and vectors
+        stay double).  Before coef_size / evaluate_coefficients.  The coef tensor of a float32 handle is opaque: float64 storage of
+        ceil(6 n_cells n^3 / 2) entries that holds the floats; coef_reference_layout widens them."""
+        if precision not in self.METRIC_PRECISION:
+            raise BP5Error(1, f"metric precision must be 'float64' or 'float32', not {precision!r}")
+        _lib.check(_lib.lib().bp5_mf_set_metric_precision(self.handle, self.METRIC_PRECISION[precision]))
+
+    def get_metric_precision(self):
+        v = C.c_int()
+        _lib.check(_lib.lib().bp5_mf_get_metric_precision(self.handle, C.byref(v)))
+        return "float32" if v.value == 1 else "float64"
+
     def set_block_workgroups(self, n):
         _lib.check(_lib.lib().bp5_mf_set_block_workgroups(self.handle, int(n)))
 
@@ -226,9 +241,13 @@ class MatrixFree:
         return coef
 
     def coef_reference_layout(self, coef):
+        """The planes in the reference layout [c][cell][q], as doubles (float32 planes widened: the operator the kernels apply)."""
         torch = _torch()
-        out = torch.empty_like(coef)
-        _lib.check(_lib.lib().bp5_mf_metric_to_reference_layout(self.handle, _ptr(coef), _ptr(out)))
+        if self.get_metric_precision() == "float32":      # the opaque tensor holds floats: one double per entry comes back
+            out = torch.empty(6 * self.mesh.n_cells * (self.mesh.degree + 1) ** 3, dtype=torch.float64, device=coef.device)
+        else:
+            out = torch.empty_like(coef)
+        _lib.check(_lib.lib().bp5_mf_metric_to_reference_layout(self.handle, _ptr(coef, self.coef_size()), _ptr(out)))
         return out
 
     def cell_loop(self, coef, src, dst, cell_begin=0, cell_end=None):
@@ -253,9 +272,14 @@ class MatrixFree:
 class PoissonOperator:
     """== BP5::PoissonOperator<3,fe_degree>, bp5/step-64.cu:198-276."""
 
-    def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, device=0, comm=None, stream=None, geometry=0):
+    def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, device=0, comm=None, stream=None, geometry=0, metric_precision="float64"):
+        if metric_precision not in MatrixFree.METRIC_PRECISION:       # (before a handle exists: nothing to release)
+            raise BP5Error(1, f"metric precision must be 'float64' or 'float32', not {metric_precision!r}")
         self.mf_data = MatrixFree().reinit(mesh, quadrature, coefficient, device, stream, comm)
         self.geometry = geometry
+        self.metric_precision = metric_precision
+        if metric_precision != "float64":         # "float32": float planes, double arithmetic (MatrixFree.set_metric_precision)
+            self.mf_data.set_metric_precision(metric_precision)
         if geometry == _lib.GEOM_AFFINE:          # per-cell metric + one scalar plane, no 6-plane array at all
             self.mf_data.set_geometry_mode(geometry)
             self.coef = None
@@ -304,6 +328,7 @@ class HelmholtzOperator(PoissonOperator):
         self.mf_data = MatrixFree().reinit(mesh, quadrature, coefficient, device, stream, comm)
         self.mf_data.set_operator(_lib.OP_HELMHOLTZ)
         self.geometry = 0
+        self.metric_precision = "float64"
         self.coef = self.mf_data.evaluate_coefficients()
         self.n_owned_cells = mesh.n_cells
         self.do_zero_out = True
@@ -598,25 +623,36 @@ def mg_coarse_degrees(degree):
     return degrees
 
 
-def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
+def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4, metric_precision=None):
     """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same operator class, cells, block order
     and numbering scheme, coefficient, quadrature, geometry mode, device, stream and communicator at degrees p // 2, ..., 1; then, at
     degree 1, up to
     h_levels geometric levels (an int, or "max": as many as the mesh allows), each on BrickMesh.coarsen(min_cells) of the one above
     (half the cells per direction, twice h, the same domain), stopping where coarsen returns None.  h_levels = 0 (default): the p-levels
-    only.  Returns [fine_op, ...]."""
+    only.  Returns [fine_op, ...].
+    metric_precision = None (default): nothing changes -- the coarse levels are built with FP64 planes whatever fine_op's own planes are (a
+    fine_op that is itself float32 gets FP64 levels below it; pass "float32" for an all-float hierarchy).  "float32": EVERY level operator keeps its metric planes as floats (deal.II's
+    mixed-precision multigrid, step-37 / step-75, as far as the planes go: arithmetic and vectors stay double) -- level 0 included, which
+    is then NOT fine_op but a new float32 twin of it on the same mesh object, quadrature, coefficient, stream and communicator.  The caller
+    keeps fine_op as the outer CG's operator (the solution is then the FP64 solution) and passes the returned list to PreconditionMG."""
     from .mesh import BrickMesh
     if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
         raise BP5Error(1, f"make_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
     mf, m = fine_op.mf_data, fine_op.mf_data.mesh
-    ops = [fine_op]
     stream = _torch().cuda.current_stream(mf.device).cuda_stream
 
     geometry = dict(geometry=fine_op.geometry) if fine_op.geometry else {}     # (HelmholtzOperator: six-plane geometry only)
+    if metric_precision is not None:
+        if metric_precision not in MatrixFree.METRIC_PRECISION:
+            raise BP5Error(1, f"make_mg_hierarchy: metric_precision must be None, 'float64' or 'float32', not {metric_precision!r}")
+        if type(fine_op) is not PoissonOperator:
+            raise BP5Error(5, "make_mg_hierarchy: metric_precision needs a PoissonOperator")
+        geometry["metric_precision"] = metric_precision
 
     def level(mesh):
         return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream, **geometry)
 
+    ops = [fine_op if metric_precision in (None, getattr(fine_op, "metric_precision", "float64")) else level(m)]
     for p in mg_coarse_degrees(m.degree)[1:]:
         ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
                                    dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)))

@@ -3,13 +3,16 @@
 // levels on 2:1 coarser meshes (step-75's global coarsening), PreconditionMG (V-cycle, Chebyshev smoothers, Chebyshev coarse solver),
 // SolverCG.  Prints the iteration count, the levels and the solution's norm.
 //
-//   bp5_multigrid <p> <nx> <ny> <nz> <deform> <rel_tol> [coefficient] [h_levels]
+//   bp5_multigrid <p> <nx> <ny> <nz> <deform> <rel_tol> [coefficient] [h_levels] [metric_precision]
 //     coefficient: 0 = kappa 1, 1 = step-64's kappa (default)
 //     h_levels: h-levels below degree 1 (default 0); coarsening stops at an odd cell count or below 4 cells in a direction
+//     metric_precision: float64 (default) | float32 = the level operators of the preconditioner keep their metric planes as floats
+//       (step-37's mixed-precision multigrid as far as the planes go); the outer CG runs on an FP64 operator of the fine level
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "bp5_dealii_facade.hpp"
@@ -19,7 +22,7 @@ using namespace bp5::dealii_facade;
 // the library's own Poisson operator on a brick mesh: handle() + coef() make the facade's solvers and PreconditionMG run it natively
 class LaplaceOperator {
 public:
-  LaplaceOperator(const bp5_mesh_view &mv, int coefficient)
+  LaplaceOperator(const bp5_mesh_view &mv, int coefficient, int metric_precision = BP5_METRIC_F64)
   {
     bp5_mf_desc d{};
     d.dim = 3; d.degree = mv.degree; d.quadrature = BP5_QUAD_GAUSS; d.coefficient = coefficient;
@@ -28,6 +31,7 @@ public:
     d.constrained_host = mv.constrained_host; d.n_constrained = mv.n_constrained;
     d.n_cell_blocks = mv.n_cell_blocks; d.cell_block_offsets_host = mv.cell_block_offsets_host;
     mf_data.reinit(d);
+    if (metric_precision != BP5_METRIC_F64) mf_data.set_metric_precision(metric_precision);
     n_owned = mv.n_owned;
     size_t nc;
     check(bp5_mf_coef_size(mf_data.handle(), &nc));
@@ -51,12 +55,17 @@ private:
 int main(int argc, char **argv)
 {
   if (argc < 7) {
-    fprintf(stderr, "usage: %s p nx ny nz deform rel_tol [coefficient] [h_levels]\n", argv[0]);
+    fprintf(stderr, "usage: %s p nx ny nz deform rel_tol [coefficient] [h_levels] [float64|float32]\n", argv[0]);
     return 2;
   }
   try {
     const int coefficient = argc > 7 ? atoi(argv[7]) : BP5_COEF_STEP64;
     const int h_levels = argc > 8 ? atoi(argv[8]) : 0;
+    if (argc > 9 && std::string(argv[9]) != "float32" && std::string(argv[9]) != "float64") {
+      fprintf(stderr, "unknown metric precision '%s'\nusage: %s p nx ny nz deform rel_tol [coefficient] [h_levels] [float64|float32]\n", argv[9], argv[0]);
+      return 2;
+    }
+    const int precision = argc > 9 && std::string(argv[9]) == "float32" ? BP5_METRIC_F32 : BP5_METRIC_F64;
     std::vector<bp5_mesh *> meshes;
     std::vector<bp5_mesh_view> views;
     for (int p = atoi(argv[1]);; p = p / 2 > 1 ? p / 2 : 1) { // the hierarchy p, p / 2, ..., 1 on the same cells
@@ -101,15 +110,18 @@ int main(int argc, char **argv)
       std::vector<const LaplaceOperator *> levels;
       PreconditionMG::AdditionalData data;
       for (const bp5_mesh_view &mv : views) {
-        ops.emplace_back(new LaplaceOperator(mv, coefficient));
+        ops.emplace_back(new LaplaceOperator(mv, coefficient, precision));
         levels.push_back(ops.back().get());
         data.start_ids_host.push_back(mv.global_ids_host);
       }
+      // float planes on the levels: the outer CG's operator is an FP64 twin of level 0, so the solution is the FP64 solution
+      std::unique_ptr<LaplaceOperator> outer;
+      if (precision != BP5_METRIC_F64) outer.reset(new LaplaceOperator(views[0], coefficient));
       for (size_t l = 0; l < parents.size(); ++l) {
         data.parent_cells.push_back(parents[l].empty() ? nullptr : parents[l].data());
         data.child.push_back(children[l].empty() ? nullptr : children[l].data());
       }
-      const LaplaceOperator &A = *ops[0];
+      const LaplaceOperator &A = outer ? *outer : *ops[0];
       double *b, *x;
       A.initialize_dof_vector(&b); A.initialize_dof_vector(&x);
       check(bp5_assemble_rhs(A.handle(), b));
@@ -127,6 +139,7 @@ int main(int argc, char **argv)
         const bp5_mg_level o = P.level_info(l);
         printf("level%d %d %u %.12e %.12e\n", l, o.degree, o.n_owned, o.min_used, o.max_used);
       }
+      if (outer) printf("metric_precision float32\n");
       printf("solution_norm %.15e\nsolve_ms %.3f\n", xnorm, cg.result.solve_ms);
       P.clear();
       bp5_vec_free(b); bp5_vec_free(x);

@@ -205,7 +205,34 @@ int bp5_mf_sync(bp5_mf *mf); /* hipStreamSynchronize */
  * Set before bp5_mf_coef_size / bp5_mf_compute_merged_metric. */
 enum { BP5_OP_POISSON = 0, BP5_OP_HELMHOLTZ = 1 };
 int bp5_mf_set_operator(bp5_mf *mf, int op);
-/* number of doubles of the merged-metric array: 6 * n_cells * (p+1)^3  (bp5/step-64.cu:253-254); 7 planes for BP5_OP_HELMHOLTZ */
+/* Storage precision of the merged-metric planes (per handle, like bp5_mf_set_operator):
+ *   BP5_METRIC_F64  (default) the planes are doubles;
+ *   BP5_METRIC_F32  the planes are FLOATS: half the bytes of the stream the operator kernels live on (p = 4, unfused application on lattice
+ *                   bricks: 16 + 24 r instead of 16 + 48 r bytes per DoF, r = cell entries per DoF).  All arithmetic and all vectors stay
+ *                   double: a kernel widens each entry where it uses it.  bp5_mf_compute_merged_metric computes every entry in double exactly
+ *                   as for double planes and rounds it ONCE, to nearest, when it stores it.  The operator applied is then the FP64 operator
+ *                   of the ROUNDED planes: an O(1e-8) relative perturbation of the FP64 operator, always symmetric, positive definite as long
+ *                   as rounding keeps every 3 x 3 tensor SPD (any cell whose metric condition number is far below 1e7; not checked at run
+ *                   time).  Meant for the level operators of a multigrid preconditioner under an FP64 outer CG (deal.II step-37 / step-75).
+ * The `coef` buffer of such a handle is OPAQUE: every entry point keeps its `const double *coef` signature and reads the buffer as the
+ * handle says (bp5_apply, bp5_apply_cells, bp5_apply_distributed, bp5_compute_diagonal, bp5_cg_solve, bp5_cg_solve_preconditioned,
+ * bp5_chebyshev_create, bp5_mg_create -- whose levels may mix precisions: each level brings its own handle and coef).  bp5_mf_coef_size
+ * returns ceil(6 n_cells (p+1)^3 / 2), the doubles that hold the floats, so allocation through bp5_vec_alloc keeps working;
+ * bp5_mf_metric_to_reference_layout returns DOUBLES (the floats widened, exactly): a host sees exactly the operator the kernels apply.
+ * Set before bp5_mf_coef_size / bp5_mf_compute_merged_metric (afterwards: BP5_ERR_INVALID).  BP5_ERR_UNSUPPORTED for handles with
+ * hanging-node masks, BP5_OP_HELMHOLTZ and BP5_GEOM_AFFINE (which has no six-plane stream to shrink) -- in either order of the two calls --
+ * and for apply variants other than 0 and 56.  Variant 0 resolves to the block kernel under the conditions of double planes (packed indices
+ * needed at every degree), else to the degree's PLAIN atomic pencil kernel -- not always the kernel a double-plane handle runs by default:
+ * p = 1, 3 without cell blocks run the x-row team kernel there, and p >= 5 on a mesh that numbers cell-interior DoFs first
+ * (bp5_mesh_desc.dof_numbering = 2) the pencil build with plain interior stores; neither has a float-plane build.
+ * Fused CG dot products (bp5_mf_set_cg_fusion) do not exist for float planes: both solvers run their separate dot-product kernels
+ * (the path Jacobi-preconditioned merged CG takes) and bp5_cg_result.dot_products_fused is 0.  The block kernel reads float planes with
+ * ordinary loads (bp5_mf_set_streaming has no effect on them; same bits either way). */
+enum { BP5_METRIC_F64 = 0, BP5_METRIC_F32 = 1 };
+int bp5_mf_set_metric_precision(bp5_mf *mf, int precision);
+int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision);
+/* number of doubles of the merged-metric array: 6 * n_cells * (p+1)^3  (bp5/step-64.cu:253-254); 7 planes for BP5_OP_HELMHOLTZ;
+ * BP5_METRIC_F32: ceil(6 * n_cells * (p+1)^3 / 2) */
 int bp5_mf_coef_size(const bp5_mf *mf, size_t *n_doubles);
 
 /* == mf_data.evaluate_coefficients(JacobianFunctor), bp5/step-64.cu:84-114,256-258:
@@ -214,7 +241,10 @@ int bp5_mf_coef_size(const bp5_mf *mf, size_t *n_doubles);
  *      coef[c*n_cells*nq + cell*nq + off(qi, qj + n*qk)],   n = p+1, nq = n^3, ab = qj + n*qk,
  *      off(qi, ab) = (qi/2)*2n^2 + 2ab + (qi&1)  for qi < 2(n/2);   (n/2)*2n^2 + ab  for the last qi of odd n
  *    i.e. per cell the x-pencils of the n^2 (qj,qk) positions, stored as pairs (qi, qi+1) position after position:
- *    the kernels fetch 16 bytes per lane and a wave's load is one contiguous run. */
+ *    the kernels fetch 16 bytes per lane and a wave's load is one contiguous run.
+ *    BP5_METRIC_F32: the SAME index formula over an array of floats (`coef` reinterpreted as float *): the pair layout with float entries,
+ *    a lane fetches 8 bytes per load, a wave's load is one contiguous run of n^2 * 8 bytes per cell.  (A layout of quads (qi .. qi+3) that
+ *    keeps 16-byte loads -- 12 instead of 18 metric load instructions per lane and cell at p = 4 -- has not been built: DESIGN 7e.) */
 int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef);
 /* Geometry representation used by bp5_apply / bp5_cg_solve:
  *   BP5_GEOM_MERGED6  the reference's six stored planes per q-point (G = 6 doubles per q-point), `coef`
@@ -226,7 +256,7 @@ int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef);
  *                     Fails with BP5_ERR_UNSUPPORTED if K K^T varies by more than 1e-10 (relative) inside a cell. */
 enum { BP5_GEOM_MERGED6 = 0, BP5_GEOM_AFFINE = 1 };
 int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode);
-/* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop) */
+/* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop); coef_ref: 6 n_cells (p+1)^3 DOUBLES in either precision */
 int bp5_mf_metric_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref);
 
 /* MatrixFree::Data mirror (bp5/fe_evaluation_gl.h:112-120, bp5/step-64.cu:94-97):

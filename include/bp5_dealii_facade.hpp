@@ -195,6 +195,9 @@ public:
 
   Data get_data(unsigned int /*color*/ = 0) const { return data; }
   bp5_mf *handle() const { return mf; }
+  // storage precision of the merged-metric planes (BP5_METRIC_F64 default | BP5_METRIC_F32: float planes, double arithmetic -- the level
+  // operators of a mixed-precision multigrid, step-37 / step-75); before bp5_mf_coef_size / bp5_mf_compute_merged_metric (include/bp5.h)
+  void set_metric_precision(int precision) { check(bp5_mf_set_metric_precision(mf, precision)); }
   unsigned int n_local() const { return n_owned + n_ghost; }
 
   // launch geometry of [upstream] C4

@@ -14,6 +14,9 @@ make_mg_hierarchy(h_levels=...)) the same legs run on that hierarchy, and
   setup   also reports each level's cells
   cycle   also times the first geometric transfer and reads mg_geo_prolongate_kernel / mg_geo_restrict_kernel from the kernel statistics
   solve   runs coarse degrees 10, 20, 30 and 60 on the hybrid hierarchy, and the p-only default (coarse degree 60) beside them
+--metric-precision float32: the level operators keep their metric planes as floats (make_mg_hierarchy(metric_precision="float32")); the
+outer CG of the solve leg runs on the FP64 fine operator; `apply_bytes_per_dof_p<k>` (cycle leg: the unfused application's algorithmic
+bytes, 16 + 6 e r with e = 4 or 8 bytes per plane entry, index streams not counted) follows the precision.
 --degree sets the fine degree (default 4), e.g. --degree 1 --cells 256 256 256 --h-levels max against --h-levels 0 (one level).
 
 Driver (default): runs every leg in a fresh child process under `timeout -k 10 <limit>` and stops at the first leg that fails; one JSON
@@ -33,13 +36,17 @@ sys.path.insert(0, ROOT)
 LEGS = {"setup": 240, "cycle": 300, "solve": 420}
 
 
-def _hierarchy(pkg, cells, degree=4, h_levels=None):
+def _hierarchy(pkg, cells, degree=4, h_levels=None, metric_precision=None):
+    """(outer operator, level operators): the same list unless metric_precision makes level 0 a float32 twin of the outer operator"""
     mesh = pkg.BrickMesh(degree, cells, h=1.0 / cells[0], cell_block=(4, 4, 4), dof_numbering=1, cell_block_order=1)
     op = pkg.PoissonOperator(mesh, pkg.QUAD_GAUSS, pkg.COEF_STEP64)
-    ops = pkg.make_mg_hierarchy(op) if h_levels is None else pkg.make_mg_hierarchy(op, h_levels=h_levels)
-    for o in ops:
+    kw = {} if h_levels is None else dict(h_levels=h_levels)
+    if metric_precision is not None:
+        kw["metric_precision"] = metric_precision
+    ops = pkg.make_mg_hierarchy(op, **kw)
+    for o in [op] + ops:
         o.mf_data.set_apply_variant(56)
-    return ops
+    return op, ops
 
 
 def _timed(torch, fn, reps):
@@ -71,17 +78,19 @@ def geo_transfer_bytes(n, n_cells, n_fine, n_coarse):
             "mg_combine_kernel": n_cells * 12 * n3 + 12 * n_coarse}
 
 
-def leg(name, cells, degree=4, h_levels=None):
+def leg(name, cells, degree=4, h_levels=None, metric_precision=None):
     import torch
     import bp5_pkg
     pkg = bp5_pkg.load()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ops = _hierarchy(pkg, cells, degree, h_levels)
+    outer, ops = _hierarchy(pkg, cells, degree, h_levels, metric_precision)
     fine = ops[0]
     n = fine.mf_data.n_owned
     out = {"leg": name, "cells": list(cells), "n_dofs": int(fine.mf_data.mesh.n_global_dofs), "degrees": [o.mf_data.mesh.degree for o in ops],
            "level_dofs": [int(o.mf_data.mesh.n_global_dofs) for o in ops]}
+    if metric_precision is not None:
+        out["metric_precision"] = metric_precision
     if h_levels is not None:
         out.update(h_levels=h_levels, level_cells=[list(o.mf_data.mesh.cells) for o in ops])
     if name == "setup":
@@ -103,6 +112,8 @@ def leg(name, cells, degree=4, h_levels=None):
             dst = ops[l].initialize_dof_vector()
             cyc.append(_timed(torch, lambda: mg.vmult(dst, src), reps))
             out[f"apply_ms_p{ops[l].mf_data.mesh.degree}"] = _timed(torch, lambda: ops[l].vmult(dst, src), reps)
+            ml = ops[l].mf_data.mesh
+            out[f"apply_bytes_per_dof_p{ml.degree}"] = 16 + 6 * (4 if metric_precision == "float32" else 8) * ml.n_cells * (ml.degree + 1) ** 3 / ops[l].mf_data.n_owned
         out["v_cycle_ms"] = cyc[0]
         out["level_ms"] = [cyc[l] - (cyc[l + 1] if l + 1 < len(cyc) else 0.0) for l in range(len(cyc))]
         if len(ops) > 1 and not mgs[0].transfers[0].geometric:
@@ -140,10 +151,10 @@ def leg(name, cells, degree=4, h_levels=None):
             for rep in range(2):
                 ctl = pkg.SolverControl(500, tol)
                 x = fine.initialize_dof_vector()
-                pkg.SolverCG(ctl).solve(fine, x, b, mg)
+                pkg.SolverCG(ctl).solve(outer, x, b, mg)
             rows[key % cdeg] = dict(n_levels=len(lops), iterations=ctl.last_step(), solve_ms=ctl.solve_ms, setup_ms=setup_ms, residual=ctl.last_value(),
                                                 converged=ctl.last_value() <= tol, ms_per_iteration=ctl.solve_ms / max(ctl.last_step(), 1),
-                                                solution_l2=fine.l2_norm_solution(x))
+                                                solution_l2=outer.l2_norm_solution(x))
             mg.clear()
         out["solves"] = rows
     return out
@@ -179,19 +190,23 @@ def main():
     ap.add_argument("--cells", type=int, nargs=3, default=[116, 116, 120])
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--h-levels", default=None, help="N or max: the hybrid hierarchy (default: the p-levels only, today's legs)")
+    ap.add_argument("--metric-precision", choices=["float64", "float32"], default=None, help="float32: level operators with float metric planes under the FP64 outer CG")
+    ap.add_argument("--legs", nargs="+", choices=sorted(LEGS), default=list(LEGS), help="the driver's legs (default: all)")
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out"))
     args = ap.parse_args()
     h_levels = None if args.h_levels is None else (args.h_levels if args.h_levels == "max" else int(args.h_levels))
     if args.leg:
-        print(json.dumps(leg(args.leg, tuple(args.cells), args.degree, h_levels)), flush=True)
+        print(json.dumps(leg(args.leg, tuple(args.cells), args.degree, h_levels, args.metric_precision)), flush=True)
         return 0
     os.makedirs(args.out, exist_ok=True)
     results = []
     prof_dir = os.path.join(os.path.abspath(args.out), "bench_multigrid_prof")
-    for name, limit in LEGS.items():
+    for name, limit in ((k, v) for k, v in LEGS.items() if k in args.legs):
         leg_cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--degree", str(args.degree), "--cells"] + [str(c) for c in args.cells]
         if h_levels is not None:
             leg_cmd += ["--h-levels", str(h_levels)]
+        if args.metric_precision is not None:
+            leg_cmd += ["--metric-precision", args.metric_precision]
         profiled = name == "cycle" and shutil.which("rocprofv3") is not None
         if profiled:   # kernel statistics only: no counter collection, no other tracing
             leg_cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof_dir, "-o", "cycle", "--"] + leg_cmd
@@ -206,7 +221,7 @@ def main():
             row["kernel_stats"] = kernel_rows(stats[0], row) if stats else "no kernel_stats.csv written"
         print(json.dumps(row), flush=True)
         results.append(row)
-        tag = "" if h_levels is None else f"_p{args.degree}_h{h_levels}"
+        tag = ("" if h_levels is None else f"_p{args.degree}_h{h_levels}") + ("" if args.metric_precision is None else f"_{args.metric_precision}")
         with open(os.path.join(args.out, f"bench_multigrid{tag}.json"), "w") as f:
             json.dump(results, f, indent=1)
     return 0
