@@ -16,6 +16,7 @@ CG_PLAIN, CG_MERGED = 0, 1
 GEOM_MERGED6, GEOM_AFFINE = 0, 1
 OP_POISSON, OP_HELMHOLTZ = 0, 1
 UNIQUE_ID_BYTES = 128
+MAX_COMPONENTS = 8          # bp5.h: BP5_MAX_COMPONENTS
 
 
 class BP5Error(RuntimeError):
@@ -143,6 +144,7 @@ def lib():
         "bp5_mf_get_data": (i32, [vp, i32, C.POINTER(MFData)]),
         "bp5_apply": (i32, [vp, vp, vp, vp, i32]),
         "bp5_apply_cells": (i32, [vp, vp, vp, vp, u32, u32]),
+        "bp5_apply_components": (i32, [vp, vp, i32, sz, vp, vp, i32]),
         "bp5_copy_constrained": (i32, [vp, vp, vp]),
         "bp5_set_constrained": (i32, [vp, f64, vp]),
         "bp5_mf_set_apply_variant": (i32, [vp, i32]),
@@ -184,6 +186,7 @@ def lib():
         "bp5_halo_zero_ghosts": (i32, [vp, vp]),
         "bp5_apply_distributed": (i32, [vp, vp, vp, vp, i32]),
         "bp5_cg_solve": (i32, [vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_cg_solve_components": (i32, [vp, vp, i32, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_operator": (i32, [vp, VMULT_FN, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_preconditioned": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_chebyshev_create": (i32, [vp, vp, vp, vp, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),

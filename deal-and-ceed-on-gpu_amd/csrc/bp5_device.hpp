@@ -109,6 +109,8 @@ struct bp5_mf {
   double *ws_g = nullptr, *ws_d = nullptr, *ws_h = nullptr, *d_evec = nullptr;
   char *ws_base = nullptr;
   double *ws_z = nullptr;     // preconditioner output of bp5_cg_solve_preconditioned (allocated on first use)
+  double *wsc_base = nullptr; // bp5_cg_solve_components: g, d, h as block vectors (3 n_components ld doubles), grown on demand
+  size_t wsc_cap = 0;         // ... doubles allocated
   // bp5_cg_solve_preconditioned with check_every = 0: the stop flag of iteration k copied to h_done[k % 3] behind ev_done[k % 3]
   int *h_done = nullptr; // pinned
   hipEvent_t ev_done[3] = {nullptr, nullptr, nullptr};
@@ -299,6 +301,42 @@ inline int launch_apply_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
                      sh);
   KERNEL_CHECK();
   return BP5_OK;
+}
+
+// bp5_apply_components: all cells, every component through ONE pass over the metric planes and local_to_global (the caller has validated
+// the layout and zeroed dst where asked)
+template <int P, bool COLL, int TW, int LPC, int TPB>
+inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
+{
+  constexpr int n = P + 1;
+  constexpr int CPT = 64 * TW / LPC;
+  using L = LdsLayout<n, LPC>;
+  ApplyArgs a{};
+  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
+  a.plane_stride = mf->coef_plane_stride; a.cell_stride = mf->coef_cell_stride;
+  a.cell_begin = 0; a.cell_end = mf->n_cells;
+  a.n_cells_total = mf->n_cells;
+  a.n_teams = (mf->n_cells + CPT - 1) / CPT;
+  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
+  a.teams_per_xcd = (nblk + 7) / 8;
+  ComponentArgs ca{(uint32_t)n_components, (uint64_t)ld};
+  ShapeArg<n> sh;
+  fill_shape(sh, mf);
+  const size_t lds = (size_t)TPB * CPT * L::CS * sizeof(double);
+  snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_components_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", TW, LPC, TPB);
+  hipLaunchKernelGGL((apply_pencil_components_kernel<P, COLL, TW, LPC, TPB>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a, ca, sh);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+// the degree's default pencil shape (APPLY_CASE(P, 0, ...)), both quadratures
+template <int DEG>
+int apply_components_degree_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
+{
+  constexpr int n2 = (DEG + 1) * (DEG + 1);
+  constexpr int TW = DEG <= 3 ? 1 : 4, TPB = DEG <= 3 ? 4 : 1;
+  if (mf->n_cells == 0) return BP5_OK;
+  if (mf->quadrature == BP5_QUAD_GLL) return launch_apply_components_t<DEG, true, TW, n2, TPB>(mf, coef, n_components, ld, src, dst);
+  return launch_apply_components_t<DEG, false, TW, n2, TPB>(mf, coef, n_components, ld, src, dst);
 }
 
 // LDS bytes of one block-kernel workgroup: transpose tiles of the cell slots (two per slot where the cells span waves: BlockPass::PP),
@@ -977,3 +1015,7 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
 
 #define BP5_EXTERN_DEGREE(N) extern template int apply_degree_impl<N>(bp5_mf *, ApplyCall &, const double *, const double *, double *);
 BP5_EXTERN_DEGREE(1) BP5_EXTERN_DEGREE(2) BP5_EXTERN_DEGREE(3) BP5_EXTERN_DEGREE(4) BP5_EXTERN_DEGREE(5) BP5_EXTERN_DEGREE(6) BP5_EXTERN_DEGREE(7) BP5_EXTERN_DEGREE(8)
+
+#define BP5_EXTERN_COMPONENTS_DEGREE(N) extern template int apply_components_degree_impl<N>(bp5_mf *, const double *, int, size_t, const double *, double *);
+BP5_EXTERN_COMPONENTS_DEGREE(1) BP5_EXTERN_COMPONENTS_DEGREE(2) BP5_EXTERN_COMPONENTS_DEGREE(3) BP5_EXTERN_COMPONENTS_DEGREE(4)
+BP5_EXTERN_COMPONENTS_DEGREE(5) BP5_EXTERN_COMPONENTS_DEGREE(6) BP5_EXTERN_COMPONENTS_DEGREE(7) BP5_EXTERN_COMPONENTS_DEGREE(8)

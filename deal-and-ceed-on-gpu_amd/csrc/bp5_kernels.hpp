@@ -1205,6 +1205,224 @@ __device__ __forceinline__ void load_pencil_idx(const T *base, int ab, T (&v)[n]
 // rare wrong sums in multi-round passes at full size).  tools/check_lds_barrier.py checks the ISA for this pattern.
 __device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// ------------------------------------------------------------------------------------ fused operator on a block vector
+// FEEvaluation<dim, p, n_q, n_components> on a BlockVector over ONE scalar DoFHandler (the reference carries n_components_ and asserts it
+// to 1: bp5/fe_evaluation_gl.h:29,137,165,331): component c of src / dst starts at src + c ld / dst + c ld, each block laid out like a scalar
+// vector.  The metric and the index stream are the same for every component: a cell loads its six pencils and its local_to_global entries
+// ONCE, keeps them in registers and runs the components through them -- 16 + (4 + 48) r / NC bytes per DoF-component instead of 16 + 52 r
+// (r: cell-local entries per DoF).  The trip count is a run-time argument: one kernel per (P, COLL).
+// Launch shape, lanes, tiles and the per-component arithmetic are apply_pencil_kernel's (prefetched planes, Poisson operator, six-plane
+// geometry); the scatter is by atomics, so the result is not bitwise reproducible.
+struct ComponentArgs {
+  uint32_t n_components;
+  uint64_t ld; // doubles between two components (even; >= n_owned + n_ghost)
+};
+// GPF: the next component's gathers are issued before the current component's integrate (n more live registers); decided per degree from
+// the ISA: on where neither quadrature's build spills or loses a wave of occupancy to it -- p <= 6 (p = 7: 250 -> 268 VGPRs,
+// p = 8 collocated: 248 -> 266: two waves per SIMD become one).  The macro is the A/B knob.
+#ifndef BP5_COMPONENTS_PREFETCH_MAX_DEGREE
+#define BP5_COMPONENTS_PREFETCH_MAX_DEGREE 6
+#endif
+constexpr bool components_gather_prefetch(int degree) { return degree <= BP5_COMPONENTS_PREFETCH_MAX_DEGREE; }
+// waves per SIMD asked of the compiler.  p = 8 Gauss: left alone the build takes 282 VGPRs -- one wave per SIMD where the scalar kernel (251) has
+// two; capped at 256 it spills 13 doubles (108 B of scratch) and keeps the two waves.  The macro is the A/B knob (1: no cap).
+#ifndef BP5_COMPONENTS_P8_WAVES
+#define BP5_COMPONENTS_P8_WAVES 2
+#endif
+constexpr int components_waves_per_simd(int degree, bool coll) { return degree == 8 && !coll ? BP5_COMPONENTS_P8_WAVES : 1; }
+template <int P, bool COLL, int TW, int LPC, int TPB>
+__global__ void __launch_bounds__(64 * TW * TPB, components_waves_per_simd(P, COLL)) apply_pencil_components_kernel(ApplyArgs a, ComponentArgs ca, ShapeArg<P + 1> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  constexpr bool GPF = components_gather_prefetch(P);
+  static_assert(LPC >= n2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<n, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // XCD-aware mapping, as apply_pencil_kernel
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < n2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  // idle lanes mirror a valid lane: every load is unconditional and in bounds; LDS writes and the atomics are predicated, for every component
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < n2 ? ab : ab % n2;
+  const int a_ = abm % n, b_ = abm / n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * L::CS;
+#define TL(f, k, j, i) T[(f) * (n * L::PS) + (k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- once per cell: indices (z-owner) and the six metric pencils (x-owner)
+  uint32_t idx[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+  const double *cf = a.coef + cell * a.cell_stride;
+  double S[6][n];
+#pragma unroll
+  for (int pl = 0; pl < 6; ++pl) load_pencil<n>(cf + pl * a.plane_stride, abm, S[pl]);
+  double u[n];
+#pragma unroll
+  for (int k = 0; k < n; ++k) u[k] = a.src[idx[k]];
+
+  for (uint32_t comp = 0; comp < ca.n_components; ++comp) {
+    if constexpr (!GPF) {
+      const double *src_c = a.src + (uint64_t)comp * ca.ld;
+#pragma unroll
+      for (int k = 0; k < n; ++k) u[k] = src_c[idx[k]];
+    }
+    double g0[n], g1[n], g2[n];
+    if constexpr (!COLL) {
+      double aN[n], aD[n];
+      MV_N(sh.N, u, aN);
+      MV_D(sh.D, u, aD);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = aN[k]; TL(1, k, b_, a_) = aD[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], vD[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { vN[j] = TL(0, b_, j, a_); vD[j] = TL(1, b_, j, a_); }
+      double c1[n], c2[n], c3[n];
+      MV_N(sh.N, vN, c1);
+      MV_D(sh.D, vN, c2);
+      MV_N(sh.N, vD, c3);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = c1[j]; TL(1, b_, j, a_) = c2[j]; TL(2, b_, j, a_) = c3[j]; }
+      }
+      team_sync<TW>();
+      double r1[n], r2[n], r3[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        r2[i] = TL(1, b_, a_, i);
+        r3[i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g0);
+      MV_N(sh.N, r2, g1);
+      MV_N(sh.N, r3, g2);
+    } else {
+      double gz[n];
+      MV_D(sh.D, u, gz);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = u[k]; TL(2, k, b_, a_) = gz[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], c2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) vN[j] = TL(0, b_, j, a_);
+      MV_D(sh.D, vN, c2);
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(1, b_, j, a_) = c2[j];
+      }
+      team_sync<TW>();
+      double r1[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        g1[i] = TL(1, b_, a_, i);
+        g2[i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g0);
+    }
+    if constexpr (GPF) { // the next component's gathers travel under this component's integrate (the last component re-reads its own: in bounds)
+      const double *src_n = a.src + (uint64_t)(comp + 1 < ca.n_components ? comp + 1 : comp) * ca.ld;
+#pragma unroll
+      for (int k = 0; k < n; ++k) u[k] = src_n[idx[k]];
+    }
+
+    // ---- quadrature-point operation: t = S ghat (symmetric 3x3, bp5/step-64.cu:166-177)
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      const double x0 = g0[i], x1 = g1[i], x2 = g2[i];
+      g0[i] = S[0][i] * x0 + S[3][i] * x1 + S[4][i] * x2;
+      g1[i] = S[3][i] * x0 + S[1][i] * x1 + S[5][i] * x2;
+      g2[i] = S[4][i] * x0 + S[5][i] * x1 + S[2][i] * x2;
+    }
+
+    // ---- integrate (transpose sequence)
+    double y[n];
+    if constexpr (!COLL) {
+      double e1[n], e2[n], e3[n];
+      MV_DT(sh.D, g0, e1);
+      MV_NT(sh.N, g1, e2);
+      MV_NT(sh.N, g2, e3);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = e2[i]; TL(2, b_, a_, i) = e3[i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n], w3[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        w1[j] = TL(0, b_, j, a_);
+        w2[j] = TL(1, b_, j, a_);
+        w3[j] = TL(2, b_, j, a_);
+      }
+      double f1[n], f2[n];
+      MV_NT(sh.N, w1, f1);
+      MV_DT_ADD(sh.D, w2, f1);
+      MV_NT(sh.N, w3, f2);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = f1[j]; TL(1, b_, j, a_) = f2[j]; }
+      }
+      team_sync<TW>();
+      double z1[n], z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { z1[k] = TL(0, k, b_, a_); z2[k] = TL(1, k, b_, a_); }
+      MV_NT(sh.N, z1, y);
+      MV_DT_ADD(sh.D, z2, y);
+    } else {
+      double e1[n];
+      MV_DT(sh.D, g0, e1);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = g1[i]; TL(2, b_, a_, i) = g2[i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { w1[j] = TL(0, b_, j, a_); w2[j] = TL(1, b_, j, a_); }
+      MV_DT_ADD(sh.D, w2, w1);
+      if (active) { // each y-owner lane rewrites only the column it has just read
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(0, b_, j, a_) = w1[j];
+      }
+      team_sync<TW>();
+      double z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { y[k] = TL(0, k, b_, a_); z2[k] = TL(2, k, b_, a_); }
+      MV_DT_ADD(sh.D, z2, y);
+    }
+
+    // ---- scatter-add into this component's block (distribute_local_to_global, bp5/fe_evaluation_gl.h:170-180)
+    if (active) {
+      double *dst_c = a.dst + (uint64_t)comp * ca.ld;
+#pragma unroll
+      for (int k = 0; k < n; ++k) atomic_add_f64(dst_c + idx[k], y[k]);
+    }
+    // the next component's first tile write follows this component's last tile read: a barrier on the loop's back-edge, so the drain is
+    // explicit (see lds_drain())
+    lds_drain();
+    team_sync<TW>();
+  }
+#undef TL
+}
+
 // degrees whose block-kernel cells span waves (n^2 lanes per cell: p = 2, 5, 8) and exchange their tiles through the workgroup barrier: two
 // tiles used alternately halve the barriers of a pass (BlockPass::PP) where the second tile still fits the LDS share of the workgroup
 #ifndef BP5_PINGPONG_P2
@@ -3373,6 +3591,90 @@ static __global__ void __launch_bounds__(VB) cg_direction_kernel(double *d, cons
                                                          const int *st)
 {
   if (st[ST_DONE]) return;
+  const double beta = sc[SC_BETA];
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      double2 dv = *reinterpret_cast<double2 *>(d + i);
+      const double2 gv = *reinterpret_cast<const double2 *>(g + i);
+      dv.x = beta * dv.x - (diag ? diag[i] * gv.x : gv.x);
+      dv.y = beta * dv.y - (diag ? diag[i + 1] * gv.y : gv.y);
+      *reinterpret_cast<double2 *>(d + i) = dv;
+    } else
+      d[i] = beta * d[i] - (diag ? diag[i] * g[i] : g[i]);
+  }
+}
+
+// ---- plain CG on a block vector (bp5_cg_solve_components): the kernels above with the component as the second grid dimension.
+// Component c = blockIdx.y works on the block at + c ld; its partial sums land in columns [c gridDim.x, (c + 1) gridDim.x) of the rows, so the
+// finalize pass sums block-wise partials, components in order (fixed order).  diag is per scalar DoF, shared by the components.
+static __global__ void copy_constrained_components_kernel(const uint32_t *cdofs, uint32_t n, const double *src, double *dst, size_t ld)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { const size_t c = cdofs[i] + blockIdx.y * ld; dst[c] = src[c]; }
+}
+static __global__ void __launch_bounds__(VB) cgc_init_kernel(const double *b, const double *diag, double *x, double *g, double *d, size_t n, size_t ld,
+                                                             double *partials)
+{
+  const size_t o = blockIdx.y * ld;
+  b += o; x += o; g += o; d += o;
+  double acc[2] = {0.0, 0.0};
+  const size_t stride = (size_t)gridDim.x * VB;
+  for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
+    const double gi = -b[i], hi = diag ? diag[i] * gi : gi;
+    x[i] = 0.0; g[i] = gi; d[i] = -hi;
+    acc[0] += gi * gi; acc[1] += gi * hi;
+  }
+  block_reduce_store<2>(acc, partials + blockIdx.y * gridDim.x);
+}
+static __global__ void __launch_bounds__(VB) cgc_dot_kernel(const double *x, const double *y, size_t n, size_t ld, double *partials, const int *st)
+{
+  if (st[ST_DONE]) return;
+  x += blockIdx.y * ld; y += blockIdx.y * ld;
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
+      acc[0] += a.x * b.x + a.y * b.y;
+    } else
+      acc[0] += x[i] * y[i];
+  }
+  block_reduce_store<1>(acc, partials + blockIdx.y * gridDim.x);
+}
+static __global__ void __launch_bounds__(VB) cgc_update_kernel(double *x, double *g, const double *d, const double *h, const double *diag, size_t n, size_t ld,
+                                                               const double *sc, const int *st, double *partials)
+{
+  if (st[ST_DONE]) return;
+  const size_t o = blockIdx.y * ld;
+  x += o; g += o; d += o; h += o;
+  const double alpha = sc[SC_GH] / sc[SC_DH];
+  double acc[2] = {0.0, 0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      double2 xv = *reinterpret_cast<double2 *>(x + i), gv = *reinterpret_cast<double2 *>(g + i);
+      const double2 dv = *reinterpret_cast<const double2 *>(d + i), hv = *reinterpret_cast<const double2 *>(h + i);
+      xv.x += alpha * dv.x; xv.y += alpha * dv.y;
+      gv.x += alpha * hv.x; gv.y += alpha * hv.y;
+      *reinterpret_cast<double2 *>(x + i) = xv;
+      *reinterpret_cast<double2 *>(g + i) = gv;
+      const double z0 = diag ? diag[i] * gv.x : gv.x, z1 = diag ? diag[i + 1] * gv.y : gv.y;
+      acc[0] += gv.x * gv.x + gv.y * gv.y;
+      acc[1] += gv.x * z0 + gv.y * z1;
+    } else {
+      const double xi = x[i] + alpha * d[i], gi = g[i] + alpha * h[i];
+      x[i] = xi; g[i] = gi;
+      acc[0] += gi * gi; acc[1] += gi * (diag ? diag[i] * gi : gi);
+    }
+  }
+  block_reduce_store<2>(acc, partials + blockIdx.y * gridDim.x);
+}
+static __global__ void __launch_bounds__(VB) cgc_direction_kernel(double *d, const double *g, const double *diag, size_t n, size_t ld, const double *sc,
+                                                                  const int *st)
+{
+  if (st[ST_DONE]) return;
+  d += blockIdx.y * ld; g += blockIdx.y * ld;
   const double beta = sc[SC_BETA];
   const size_t stride = (size_t)gridDim.x * VB * 2;
   for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {

@@ -14,7 +14,11 @@ C ABI (include/bp5.h).  Names, argument meaning and error behaviour follow the r
                            h-coarsening at degree 1 (step-75's global coarsening)
 
 Vectors are torch float64 CUDA tensors of n_owned + n_ghost entries (torch is plumbing for
-device memory / streams / the process group only -- no torch op is on the hot path)."""
+device memory / streams / the process group only -- no torch op is on the hot path).
+
+Block vectors (deal.II BlockVector over one scalar DoFHandler; CEED BP6): a contiguous 2-D tensor of shape (n_components, ld), component c
+in row c laid out like a scalar vector, ld = n_local rounded up to even (initialize_block_vector).  PoissonOperator.vmult and
+SolverCG.solve take them (bp5_apply_components, bp5_cg_solve_components); everything else refuses them with status 5."""
 import ctypes as C
 
 import numpy as np
@@ -227,6 +231,13 @@ class MatrixFree:
         torch = _torch()
         return torch.zeros(self.n_local, dtype=torch.float64, device=f"cuda:{self.device}")
 
+    def initialize_block_vector(self, n_components):
+        """Zero-filled block vector: contiguous (n_components, ld) with ld = n_local rounded up to even (include/bp5.h: block vectors)."""
+        torch = _torch()
+        if not 1 <= int(n_components) <= _lib.MAX_COMPONENTS:
+            raise BP5Error(1, f"n_components must be 1 .. {_lib.MAX_COMPONENTS}, not {n_components!r}")
+        return torch.zeros((int(n_components), self.n_local + (self.n_local & 1)), dtype=torch.float64, device=f"cuda:{self.device}")
+
     def coef_size(self):
         n = C.c_size_t()
         _lib.check(_lib.lib().bp5_mf_coef_size(self.handle, C.byref(n)))
@@ -292,10 +303,18 @@ class PoissonOperator:
     def initialize_dof_vector(self, vec=None):
         return self.mf_data.initialize_dof_vector(vec)
 
+    def initialize_block_vector(self, n_components):
+        return self.mf_data.initialize_block_vector(n_components)
+
     def vmult(self, dst, src):
-        """dst = [0 +] A src; dst[c] = src[c] on Dirichlet DoFs (bp5/step-64.cu:263-276)."""
+        """dst = [0 +] A src; dst[c] = src[c] on Dirichlet DoFs (bp5/step-64.cu:263-276).  Block vectors (2-D tensors): the same on every
+        component with one pass over the metric (bp5_apply_components)."""
         L, mf = _lib.lib(), self.mf_data
         dst, src = _vals(dst), _vals(src)
+        if _is_block(dst) or _is_block(src):
+            nc, ld = _block_args(mf, dst, src)
+            _lib.check(L.bp5_apply_components(mf.handle, _ptr(self.coef), nc, ld, _ptr(src), _ptr(dst), 1 if self.do_zero_out else 0))
+            return
         fn = L.bp5_apply_distributed if self.distributed else L.bp5_apply
         _lib.check(fn(mf.handle, _ptr(self.coef), _ptr(src, mf.n_local), _ptr(dst, mf.n_local), 1 if self.do_zero_out else 0))
 
@@ -425,6 +444,27 @@ def _vals(v):
     return v.values if isinstance(v, Vector) else v
 
 
+def _is_block(t):
+    """a block vector: a 2-D tensor (n_components, ld)"""
+    return getattr(t, "dim", None) is not None and t.dim() == 2
+
+
+def _refuse_blocks(who, *vectors):
+    if any(_is_block(_vals(v)) for v in vectors):
+        raise BP5Error(5, f"{who} does not take block vectors (2-D tensors): PoissonOperator.vmult and SolverCG with a DiagonalMatrix do")
+
+
+def _block_args(mf, *vectors):
+    """(n_components, ld) of block vectors of one shape, checked against the handle's layout"""
+    shapes = {tuple(v.shape) for v in vectors}
+    if len(shapes) != 1 or not all(_is_block(v) for v in vectors):
+        raise BP5Error(1, f"block vectors of one shape (n_components, ld) expected, got {sorted(tuple(v.shape) for v in vectors)}")
+    nc, ld = vectors[0].shape
+    if ld < mf.n_local:
+        raise BP5Error(1, f"block vector has ld = {ld}, need at least n_local = {mf.n_local}")
+    return int(nc), int(ld)
+
+
 class DiagonalMatrix:
     """== DiagonalMatrix<Vector>; `None` vector == identity (the reference sets it to 1,
     bp5/step-64.cu:432, and still streams it; here identity costs no bytes)."""
@@ -537,6 +577,7 @@ class PreconditionChebyshev:
 
     def _run(self, fn, dst, src):
         mf = self.mf_data
+        _refuse_blocks("PreconditionChebyshev", dst, src)
         status = fn(self.handle, _ptr(_vals(dst), mf.n_local), _ptr(_vals(src), mf.n_local))
         if self._failure:
             raise self._failure.pop(0)
@@ -719,6 +760,7 @@ class PreconditionMG:
     def vmult(self, dst, src):
         """dst = V src: one V-cycle (dst's prior content ignored); enqueued on the operators' stream."""
         n = self.mf_data.n_local
+        _refuse_blocks("PreconditionMG", dst, src)
         _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(_vals(dst), n), _ptr(_vals(src), n)))
 
     def level_info(self):
@@ -772,7 +814,15 @@ class _SolverBase:
         res = _lib.CGResult()
         failure = []
         native = isinstance(A, PoissonOperator)
-        if general:
+        if _is_block(x) or _is_block(b):
+            # the stacked system diag(A, ..., A) x = b: ONE Krylov space for all components (bp5_cg_solve_components)
+            if self.variant != CG_PLAIN or general or not native:
+                raise BP5Error(5, "block vectors (2-D tensors): SolverCG on a PoissonOperator with None / DiagonalMatrix only")
+            nc, ld = _block_args(mf, x, b)
+            diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None
+            status = _lib.lib().bp5_cg_solve_components(mf.handle, _ptr(A.coef), nc, ld, _ptr(diag, mf.n_owned) if diag is not None else None,
+                                                        _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
+        elif general:
             if isinstance(preconditioner, PreconditionChebyshev):
                 pfn, pctx = C.cast(_lib.lib().bp5_chebyshev_vmult, C.c_void_p), preconditioner.handle
             elif isinstance(preconditioner, PreconditionMG):

@@ -288,6 +288,20 @@ int bp5_copy_constrained(bp5_mf *mf, const double *src, double *dst);
 /* == MatrixFree::set_constrained_values(val, dst) [upstream] */
 int bp5_set_constrained(bp5_mf *mf, double value, double *dst);
 
+/* Block vectors (deal.II BlockVector over ONE scalar DoFHandler; CEED BP6 = BP5 with three components): n_components local vectors in
+ * one allocation, component c at v + c * ld, each block laid out like a scalar vector (owned entries, then ghosts).  ld >= n_owned +
+ * n_ghost and even, the base pointer 16-byte aligned (every block then is); entries [n_owned + n_ghost, ld) of a block are padding:
+ * never read, never written.  Index plans, the Dirichlet set and the diagonal stay per scalar DoF and are shared by all components. */
+#define BP5_MAX_COMPONENTS 8
+/* dst_c = [0 +] A src_c ; dst_c[constrained] = src_c[constrained], c = 0 .. n_components-1: bp5_apply on every block, with ONE pass over the
+ * metric planes and local_to_global (FEEvaluation<dim,p,n_q,n_components> on a BlockVector; the reference asserts n_components == 1:
+ * bp5/fe_evaluation_gl.h:137,165).  One kernel of its own (apply_pencil_components_kernel) for every n_components, 1 included; it scatters
+ * with atomics: not bitwise reproducible.  Refused before any launch (reason in bp5_last_error) -- BP5_ERR_INVALID: null pointer,
+ * n_components outside 1..BP5_MAX_COMPONENTS, ld < n_owned + n_ghost, odd ld, misaligned base, overlapping src / dst;
+ * BP5_ERR_UNSUPPORTED: FP32-metric, Helmholtz, hanging-node and affine-geometry handles, a handle with a communicator and neighbours
+ * (a rank-local mesh with ghost DoFs but no communicator is fine: the ghost slots are just entries of the block). */
+int bp5_apply_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, int zero_dst);
+
 /* kernel variant selection for the fused operator (tuning / A-B tests):
  * 0 = library default: the measured best kernel for the degree, the geometry mode and the way the
  * cells were handed over (a mesh given in cell blocks runs the block-assembled kernel at p = 4) */
@@ -489,6 +503,15 @@ int bp5_cg_solve(bp5_mf *mf, const double *coef, const double *diag, const doubl
 typedef int (*bp5_vmult_fn)(void *ctx, double *dst, double *src);
 int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, const double *diag, const double *b, double *x,
                           const bp5_cg_params *params, bp5_cg_result *result_host);
+
+/* SolverCG (bp5/step-64.cu:446-453) on the stacked system diag(A, ..., A) x = b of a block vector (bp5_apply_components; CEED BP6): ONE
+ * Krylov space -- alpha, beta and the stop test (||g||_2 of the stacked residual against abs_tol, capped by max_iter) are shared by all
+ * components, so the iterates differ from n_components separate solves unless the right-hand sides coincide.  The BP5_CG_PLAIN recurrence
+ * of bp5_cg_solve; inv_diag (n_owned entries, or NULL == 1) is applied to every block; dot products run over the owned entries of all
+ * blocks in a fixed order.  Refusals as for bp5_apply_components; params->variant: an unknown value is BP5_ERR_INVALID, BP5_CG_MERGED
+ * (known, not offered on block vectors) BP5_ERR_UNSUPPORTED.  The work vectors (3 n_components ld doubles) belong to the handle. */
+int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *inv_diag, const double *b, double *x,
+                            const bp5_cg_params *params, bp5_cg_result *result_host);
 
 /* BP5_CG_MERGED on the packed block kernel (cell bricks, one rank's cells, diag == NULL): by default the operator's
  * write-out and combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311: p.v, v.v, r.v, r.r)

@@ -16,7 +16,10 @@
 //   SolverControl / IterationNumberControl / SolverCG / SolverCGFullMerge / DiagonalMatrix,
 //   LinearAlgebra::distributed::Vector<Number, MemorySpace::CUDA> (the part of its surface the path uses:
 //        reinit, = scalar, all_zero, add, equ, sadd, l2_norm, get_values, local_size, size, import,
-//        update_ghost_values, compress(add), zero_out_ghosts) and LinearAlgebra::ReadWriteVector.
+//        update_ghost_values, compress(add), zero_out_ghosts) and LinearAlgebra::ReadWriteVector,
+//   LinearAlgebra::distributed::BlockVector<Number, MemorySpace::CUDA> (reinit(n_blocks, ...), block(c), n_blocks, l2_norm; one allocation,
+//        the layout of bp5_apply_components / bp5_cg_solve_components: an operator with n_components on ONE scalar DoFHandler, CEED BP6;
+//        the device-side FEEvaluation below stays scalar).
 //
 // This generic path is the functional twin of the reference's apply_kernel_shmem (one thread per
 // local DoF = per q-point, values + gradients[dim] in shared memory, FP64 atomics): it exists for
@@ -26,6 +29,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -587,6 +591,59 @@ private:
   bool owns = true;
   mutable size_type n_global = 0;
 };
+// == LinearAlgebra::distributed::BlockVector<Number>: n_blocks vectors of one layout in ONE allocation, block c at get_values() + c *
+// leading_dimension() (include/bp5.h: block vectors -- the leading dimension is n_owned + n_ghost rounded up to even, the padding entry is never
+// read or written by the library).  block(c) is a non-owning Vector view, so everything a Vector can do works per block; the operator's
+// vmult(BlockVector &, const BlockVector &) (bp5_apply_components) and SolverCG::solve take the whole thing.
+template <typename Number, typename MemorySpaceType = MemorySpace::CUDA>
+class BlockVector {
+  static_assert(sizeof(Number) == sizeof(double), "the library computes in FP64");
+
+public:
+  using BlockType = Vector<Number, MemorySpaceType>;
+  using value_type = Number;
+  using size_type = size_t;
+  BlockVector() = default;
+  BlockVector(const BlockVector &) = delete;
+  BlockVector &operator=(const BlockVector &) = delete;
+  ~BlockVector() { if (val) bp5_vec_free(val); }
+  // == reinit(n_blocks, partitioner): the partitioner is what Vector::reinit takes -- the handle and its owned / ghost counts; zero-filled
+  void reinit(unsigned int n_blocks_, bp5_mf *handle, size_t n_owned_, size_t n_ghost_)
+  {
+    if (n_blocks_ < 1 || n_blocks_ > BP5_MAX_COMPONENTS) throw std::runtime_error("BlockVector::reinit: 1 .. BP5_MAX_COMPONENTS blocks");
+    if (val) bp5_vec_free(val);
+    val = nullptr; blocks.clear();
+    mf = handle; n_owned = n_owned_; n_ghost = n_ghost_;
+    ld = (n_owned + n_ghost + 1) / 2 * 2;
+    check(bp5_vec_alloc((size_t)n_blocks_ * ld, &val)); // zero-filled, 16-byte aligned (hipMalloc)
+    for (unsigned int c = 0; c < n_blocks_; ++c) blocks.push_back(BlockType::view(mf, val + c * ld, n_owned, n_ghost));
+  }
+  void reinit(const BlockVector &v) { reinit(v.n_blocks(), v.mf, v.n_owned, v.n_ghost); }
+  unsigned int n_blocks() const { return (unsigned int)blocks.size(); }
+  BlockType &block(unsigned int c) { return blocks.at(c); }
+  const BlockType &block(unsigned int c) const { return blocks.at(c); }
+  BlockVector &operator=(Number s)
+  {
+    for (auto &b : blocks) b = s;
+    return *this;
+  }
+  Number l2_norm() const
+  {
+    double sum = 0;
+    for (const auto &b : blocks) { const double r = b.l2_norm(); sum += r * r; }
+    return std::sqrt(sum);
+  }
+  Number *get_values() const { return val; }
+  size_type leading_dimension() const { return ld; }
+  size_type local_size() const { return n_owned; }
+  bp5_mf *handle() const { return mf; }
+
+private:
+  bp5_mf *mf = nullptr;
+  Number *val = nullptr;
+  size_t n_owned = 0, n_ghost = 0, ld = 0;
+  std::vector<BlockType> blocks;
+};
 } // namespace distributed
 } // namespace LinearAlgebra
 
@@ -819,6 +876,20 @@ public:
       if (s != BP5_OK && !ctx.what.empty()) throw std::runtime_error("operator vmult failed inside the solver: " + ctx.what);
       finish(res, s);
     }
+  }
+  // cg.solve(A, x, b, DiagonalMatrix) on BlockVectors (CEED BP6): the stacked system diag(A, ..., A) x = b in ONE Krylov space
+  // (bp5_cg_solve_components; the library's own operator, SolverCG only: SolverCGFullMerge is refused with BP5_ERR_UNSUPPORTED); the
+  // DiagonalMatrix holds the scalar operator's inverse diagonal and is applied to every block
+  template <typename MatrixType>
+  void solve(const MatrixType &A, LinearAlgebra::distributed::BlockVector<double, MemorySpace::CUDA> &x,
+             const LinearAlgebra::distributed::BlockVector<double, MemorySpace::CUDA> &b, const DiagonalMatrix &preconditioner)
+  {
+    static_assert(internal::has_coef<MatrixType>::value, "BlockVector solve: the library's own operator (handle() + coef())");
+    if (x.n_blocks() != b.n_blocks() || x.leading_dimension() != b.leading_dimension()) throw std::runtime_error("SolverCG::solve: BlockVectors of different layouts");
+    bp5_cg_params prm{VARIANT, (int)control.max_steps, control.tolerance, 0, 0};
+    bp5_cg_result res{};
+    const int s = bp5_cg_solve_components(A.handle(), A.coef(), (int)x.n_blocks(), x.leading_dimension(), preconditioner.get_vector(), b.get_values(), x.get_values(), &prm, &res);
+    finish(res, s);
   }
   // cg.solve(A, x, b, PreconditionChebyshev): bp5_cg_solve_preconditioned with bp5_chebyshev_vmult (SolverCG only: SolverCGFullMerge's
   // recurrence takes a diagonal, the library refuses it with BP5_ERR_INVALID).  check_every = 0: the library itself looks at the device's stop
