@@ -22,13 +22,51 @@ def _config1():
     return _cache["c1"]
 
 
-def diag_case():
+def diag_case(n_components=3):
     """the preconditioned fixed-iteration case of the GPU test: p = 4, (4,4,4), deformed, step-64 kappa, inverse diagonal, 10 iterations"""
     if "d" not in _cache:
         pr = O.Problem(4, (4, 4, 4), O.QUAD_GAUSS, deform_amp=0.04, kappa=O.kappa_step64)
         inv = 1.0 / O.operator_diagonal(pr.mesh, pr.coef, pr.N, pr.D)
-        _cache["d"] = (pr, R.rhs_blocks(pr.rhs()), inv)
-    return _cache["d"]
+        _cache["d"] = (pr, pr.rhs(), inv)
+    pr, b, inv = _cache["d"]
+    return pr, R.rhs_blocks(b, n_components), inv
+
+
+EDGES = [(3, 1), (8, 6)]       # (components, the block whose right-hand side is zeroed) of the GPU tests of the solver's edges
+
+
+def zero_block_case(n_components, zeroed):
+    """diag_case with one right-hand side zeroed"""
+    pr, B, inv = diag_case(n_components)
+    B[zeroed] = 0.0
+    return pr, B, inv
+
+
+# the solves the GPU test runs one after the other on one handle: (components, ld - n_local rounded up to even, with the inverse diagonal)
+SEQUENCE, SEQUENCE_CELLS, SEQUENCE_ITERATIONS = ((2, 2, False), (8, 2, True), (3, 64, True), (2, 2, False)), (8, 8, 4), 5
+
+
+def sequence_case():
+    """p = 4, (8,8,4), deformed, step-64 kappa: (problem, scalar right-hand side, inverse diagonal)"""
+    if "seq" not in _cache:
+        pr = O.Problem(4, SEQUENCE_CELLS, O.QUAD_GAUSS, deform_amp=0.04, kappa=O.kappa_step64)
+        _cache["seq"] = (pr, pr.rhs(), 1.0 / O.operator_diagonal(pr.mesh, pr.coef, pr.N, pr.D))
+    return _cache["seq"]
+
+
+CAPPED_CELLS, CAPPED_ITERATIONS = (21, 21, 21), 3
+
+
+def capped_case():
+    """the case of the GPU test at the capped grid: p = 4, Gauss, (21,21,21) cells = 85^3 DoFs, deformed, step-64 kappa; (problem, scalar
+    right-hand side, inverse diagonal), built once per process"""
+    if "capped" not in _cache:
+        pr = O.Problem(4, CAPPED_CELLS, O.QUAD_GAUSS, deform_amp=0.04, kappa=O.kappa_step64)
+        b, inv = pr.rhs(), 1.0 / O.operator_diagonal(pr.mesh, pr.coef, pr.N, pr.D)
+        for a in (b, inv):
+            a.setflags(write=False)
+        _cache["capped"] = (pr, b, inv)
+    return _cache["capped"]
 
 
 def test_symbols_are_exported_and_listed():
@@ -120,3 +158,54 @@ def test_fixed_iteration_references_are_stable_under_operator_noise():
     d2 = R.noise_drift(prd.vmult, Bd, 10, inv_diag=inv)
     print(f"noise drift: config 1 {d1:.3e}, p = 4 (4,4,4) with inverse diagonal {d2:.3e}")
     assert d1 < 1e-14 and d2 < 1e-13, (d1, d2)
+
+
+@pytest.mark.parametrize("nc", [1, 2, 5, 8])
+def test_fixed_iteration_references_are_stable_at_every_component_count(nc):
+    """the same two cases with the component counts the GPU tests add: two decades under TOL_CG"""
+    pr, b = _config1()
+    d1 = R.noise_drift(pr.vmult, R.rhs_blocks(b, nc), 10)
+    prd, Bd, inv = diag_case(nc)
+    d2 = R.noise_drift(prd.vmult, Bd, 10, inv_diag=inv)
+    print(f"noise drift, {nc} components: config 1 {d1:.3e}, p = 4 (4,4,4) with inverse diagonal {d2:.3e}")
+    assert Bd.shape[0] == nc and d1 < 1e-13 and d2 < 1e-13, (d1, d2)
+
+
+@pytest.mark.parametrize("nc,zeroed", EDGES)
+def test_zero_block_reference_is_stable_under_operator_noise(nc, zeroed):
+    """One right-hand side zeroed, inverse diagonal, 10 iterations: two decades under TOL_CG.  Without the preconditioner this operator
+    (step-64 kappa) does not give that: the residual stagnates and the ten-iteration reference moves by 5e-13 ... 3e-12, printed here."""
+    pr, B, inv = zero_block_case(nc, zeroed)
+    d, plain = R.noise_drift(pr.vmult, B, 10, inv_diag=inv), R.noise_drift(pr.vmult, B, 10)
+    x, _, _ = R.cg(pr.vmult, B, 10, inv_diag=inv)
+    print(f"noise drift, {nc} components, block {zeroed} zero: {d:.3e} with the inverse diagonal, {plain:.3e} without")
+    assert d < 1e-13 and not x[zeroed].any() and x[(zeroed + 1) % nc].any(), d
+
+
+def test_sequence_references_are_stable_under_operator_noise():
+    pr, b, inv = sequence_case()
+    drifts = [R.noise_drift(pr.vmult, R.rhs_blocks(b, nc), SEQUENCE_ITERATIONS, inv_diag=inv if with_diag else None) for nc, _, with_diag in SEQUENCE[:3]]
+    print("noise drift, the solves of the sequence on one handle:", " ".join(f"{d:.3e}" for d in drifts))
+    assert max(drifts) < 1e-13, drifts
+
+
+def test_one_component_tolerance_stop_reference_is_stable_under_operator_noise():
+    """the GPU test compares the one-component solve that stops at 1e-8 ||b|| with the scalar solver at TOL_CG: over that many iterations (53)
+    the reference has to stay two decades below it as well"""
+    pr, b = _config1()
+    B = R.rhs_blocks(b, 1)
+    _, k, _ = R.cg(pr.vmult, B, 1000, tol=1e-8 * np.linalg.norm(B))
+    d = R.noise_drift(pr.vmult, B, k)
+    print(f"noise drift, config 1, one component, {k} iterations: {d:.3e}")
+    assert 40 < k < 70 and d < 1e-13, (k, d)
+
+
+@pytest.mark.parametrize("with_diag", [False, True])
+@pytest.mark.parametrize("nc", [7, 8])
+def test_capped_grid_references_are_stable_under_operator_noise(nc, with_diag):
+    """The GPU test at the capped grid (85^3 DoFs, 7 and 8 components, 3 iterations, with and without the inverse diagonal) compares to
+    TOL_CG = 1e-11: its references have to stay two decades below that under 1e-16 operator noise."""
+    pr, b, inv = capped_case()
+    d = R.noise_drift(pr.vmult, R.rhs_blocks(b, nc), CAPPED_ITERATIONS, inv_diag=inv if with_diag else None)
+    print(f"noise drift, {pr.mesh.n_dofs} DoFs, {nc} components, {'inverse diagonal' if with_diag else 'no preconditioner'}: {d:.3e}")
+    assert pr.mesh.n_dofs == 85 ** 3 and d < 1e-13, d

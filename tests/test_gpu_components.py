@@ -1,7 +1,8 @@
 """Block vectors on the GPU (bp5_apply_components, bp5_cg_solve_components; CEED BP6): the n_components operator against the oracle per
 component (O.vmult) and against the scalar entry points on every block, the stacked CG against its numpy statement (tests/components_ref.py:
-O.cg_plain on concat(A v_c)), the refusals, the Python mirror and the facade example.  The multi-component kernel scatters with atomics: results
-are compared to the project's tolerances (1e-13 operator, 1e-11 CG), never bitwise."""
+O.cg_plain on concat(A v_c)), the refusals, the Python mirror and the facade example.  Every component count the header offers (1 ... 8) at
+every degree; many workgroups at every degree; the CG where its grid is capped by the partial-sum row; the solver's edges.  The multi-component
+kernel scatters with atomics: results are compared to the project's tolerances (1e-13 operator, 1e-11 CG), never bitwise."""
 import ctypes as C
 import os
 import subprocess
@@ -12,13 +13,15 @@ import pytest
 import bp5_oracle as O
 import bp5_pkg
 import components_ref as R
-from test_components_cpu import diag_case
+from test_components_cpu import (CAPPED_CELLS, CAPPED_ITERATIONS, EDGES, SEQUENCE, SEQUENCE_CELLS, SEQUENCE_ITERATIONS, capped_case, diag_case,
+                                 sequence_case, zero_block_case)
 
 pytestmark = pytest.mark.gpu
 pkg = bp5_pkg.load()
 TOL_OP = 1e-13     # one operator application (rounding + atomic summation order)
 TOL_CG = 1e-11     # CG solution vector at a fixed iteration count
 SENTINEL = -7.25e30
+N_BLOCKS = 8       # BP5_MAX_COMPONENTS: every count the header offers
 _cache = {}
 
 
@@ -36,12 +39,12 @@ def _cells(p):
 
 
 def _problem(p, quad, cells=None, amp=0.04):
-    """oracle problem, three source blocks (different seeds, non-zero on the boundary) and O.vmult of each -- computed once, never changed"""
+    """oracle problem, eight source blocks (different seeds, non-zero on the boundary) and O.vmult of each -- computed once, never changed"""
     cells = cells or _cells(p)
     key = (p, quad, cells, amp)
     if key not in _cache:
         pr = O.Problem(p, cells, quad, deform_amp=amp, kappa=O.kappa_step64)
-        src = np.stack([O.deterministic_src(pr.mesh.n_dofs, seed=40 + c) for c in range(3)])
+        src = np.stack([O.deterministic_src(pr.mesh.n_dofs, seed=40 + c) for c in range(N_BLOCKS)])
         ref = R.vmult(pr, src)
         for a in (src, ref):
             a.setflags(write=False)
@@ -57,7 +60,7 @@ def _operator(p, quad, cells=None, amp=0.04, **kw):
 
 
 def block(values, n_local, pad_value=float("nan"), extra=2):
-    """(n_components, ld) tensor, ld = n_local rounded up to even + extra; rows hold `values` (or one number), the padding pad_value"""
+    """(n_components, ld) tensor, ld = n_local rounded up to even + extra (even); rows hold `values`, the padding pad_value"""
     torch = _t()
     values = np.asarray(values)
     nc = values.shape[0]
@@ -73,7 +76,7 @@ def check_padding(t, n_local, value):
 
 
 # ------------------------------------------------------------------ 1. operator parity
-@pytest.mark.parametrize("nc", [1, 2, 3])
+@pytest.mark.parametrize("nc", range(1, N_BLOCKS + 1))
 @pytest.mark.parametrize("quad", [0, 1])
 @pytest.mark.parametrize("p", range(1, 9))
 def test_operator_parity(p, quad, nc):
@@ -102,19 +105,19 @@ def test_operator_parity(p, quad, nc):
 
 
 # ------------------------------------------------------------------ 2. add mode
-@pytest.mark.parametrize("p", [2, 4, 5])
-def test_add_mode(p):
+def _add_mode(p, nc):
     pr, src, ref = _problem(p, 0)
+    src = src[:nc]
     op = pkg.PoissonOperator(pkg.BrickMesh(p, _cells(p), deform_amp=0.04), 0, pkg.COEF_STEP64)
     op.do_zero_out = False
     n = op.mf_data.n_local
-    pre = np.random.default_rng(5).uniform(-1, 1, (3, n))
+    pre = np.random.default_rng(5).uniform(-1, 1, (nc, n))
     s, d = block(src, n), block(pre, n, pad_value=SENTINEL)
     op.vmult(d, s)
     got = d[:, :n].cpu().numpy()
     check_padding(d, n, SENTINEL)
     cst = pr.mesh.constrained.astype(np.int64)
-    for c in range(3):
+    for c in range(nc):
         want = pre[c] + O.apply_cells(pr.mesh, pr.coef, pr.N, pr.D, src[c])
         want[cst] = src[c][cst]
         scalar = _t().from_numpy(pre[c].copy()).to("cuda:0")
@@ -123,18 +126,86 @@ def test_add_mode(p):
         assert np.array_equal(got[c][cst], src[c][cst])
 
 
+@pytest.mark.parametrize("p", [2, 4, 5])
+def test_add_mode(p):
+    _add_mode(p, 3)
+
+
+@pytest.mark.parametrize("p", [2, 4, 5])
+def test_add_mode_eight_components(p):
+    _add_mode(p, N_BLOCKS)
+
+
 # ------------------------------------------------------------------ 3. one cell
-@pytest.mark.parametrize("p", [4, 8])
-def test_one_cell(p):
-    """a single, partially filled team: every other cell slot idle"""
+def _one_cell(p, nc):
     pr, src, ref = _problem(p, 0, cells=(1, 1, 1))
     op = _operator(p, 0, cells=(1, 1, 1))
     n = op.mf_data.n_local
-    s, d = block(src, n), block(np.full((3, n), np.nan), n, pad_value=SENTINEL)
+    s, d = block(src[:nc], n), block(np.full((nc, n), np.nan), n, pad_value=SENTINEL)
     op.vmult(d, s)
     check_padding(d, n, SENTINEL)
-    for c in range(3):
-        assert rel(d[c, :n].cpu().numpy(), ref[c]) <= TOL_OP
+    got = d[:, :n].cpu().numpy()
+    assert not np.isnan(got).any()
+    for c in range(nc):
+        assert rel(got[c], ref[c]) <= TOL_OP
+
+
+@pytest.mark.parametrize("p", [4, 8])
+def test_one_cell(p):
+    """a single, partially filled team: every other cell slot idle"""
+    _one_cell(p, 3)
+
+
+@pytest.mark.parametrize("p", [4, 8])
+def test_one_cell_eight_components(p):
+    """... and the longest component loop on it"""
+    _one_cell(p, N_BLOCKS)
+
+
+# ------------------------------------------------------------------ 3b. many workgroups at every degree
+def launch_shape(p, n_cells):
+    """(cells per team, teams, workgroups) of apply_pencil_components_kernel as bp5_device.hpp launches it: teams of 64 TW lanes, (p+1)^2 lanes
+    per cell, TPB teams per workgroup -- one wave per team and four teams per workgroup up to p = 3, four waves and one team beyond"""
+    tw, tpb = (1, 4) if p <= 3 else (4, 1)
+    cpt = 64 * tw // (p + 1) ** 2
+    teams = -(-n_cells // cpt)
+    return cpt, teams, -(-teams // tpb)
+
+
+# (cells, expected workgroups): more than one round of the eight XCDs (teams_per_xcd = 2 or 3), a count that is no multiple of 8 (idle trailing
+# workgroups after the remap) and a partly filled last team -- and for p <= 3 a partly filled last workgroup too
+MANY_WORKGROUPS = {1: ((12, 9, 6), 11), 2: ((8, 6, 5), 9), 3: ((6, 5, 5), 10), 4: ((9, 6, 4), 22), 5: ((6, 5, 4), 18), 6: ((7, 4, 3), 17),
+                   7: ((9, 3, 3), 21), 8: ((5, 5, 2), 17)}
+
+
+@pytest.mark.parametrize("nc", [1, N_BLOCKS])
+@pytest.mark.parametrize("quad", [0, 1])
+@pytest.mark.parametrize("p", range(1, 9))
+def test_many_workgroups(p, quad, nc):
+    """the XCD remap blk = (blockIdx.x & 7) teams_per_xcd + (blockIdx.x >> 3) with teams_per_xcd > 1, idle trailing workgroups and a partly
+    filled last team, at a stride far from n_local"""
+    cells, expected = MANY_WORKGROUPS[p]
+    n_cells = cells[0] * cells[1] * cells[2]
+    cpt, teams, workgroups = launch_shape(p, n_cells)
+    assert workgroups == expected >= 9 and workgroups % 8 != 0 and n_cells % cpt != 0, (cpt, teams, workgroups)
+    pr, src, ref = _problem(p, quad, cells=cells)
+    op = _operator(p, quad, cells=cells)
+    n = op.mf_data.n_local
+    assert n == pr.mesh.n_dofs and op.mf_data.mesh.n_cells == n_cells
+    s = block(src[:nc], n, extra=1024)
+    d = block(np.full((nc, n), np.nan), n, pad_value=SENTINEL, extra=1024)
+    assert d.shape[1] == n + (n & 1) + 1024
+    op.vmult(d, s)
+    got = d[:, :n].cpu().numpy()
+    assert not np.isnan(got).any()
+    check_padding(d, n, SENTINEL)
+    check_padding(s, n, float("nan"))
+    cst = pr.mesh.constrained.astype(np.int64)
+    errs = [rel(got[c], ref[c]) for c in range(nc)]
+    print(f"p={p} quad={quad} nc={nc} cells={cells} workgroups={workgroups}: max error vs oracle {max(errs):.2e}")
+    assert max(errs) <= TOL_OP
+    for c in range(nc):
+        assert np.array_equal(got[c][cst], src[c][cst])
 
 
 # ------------------------------------------------------------------ 4. any numbering
@@ -142,6 +213,7 @@ def test_one_cell(p):
                                         (2, (9, 8, 5), dict(cell_block=(8, 8, 4), dof_numbering=1, cell_block_order=1))])
 def test_brick_numbering_equals_lexicographic_through_the_permutation(p, cells, kw):
     pr, src, ref = _problem(p, 0, cells=cells)
+    src = src[:3]
     lex = pkg.PoissonOperator(pkg.BrickMesh(p, cells, deform_amp=0.04), 0, pkg.COEF_STEP64)
     brk = pkg.PoissonOperator(pkg.BrickMesh(p, cells, deform_amp=0.04, **kw), 0, pkg.COEF_STEP64)
     n = lex.mf_data.n_local
@@ -297,17 +369,41 @@ def _solve(op, B, max_iter, tol=0.0, inv=None, check_every=0):
     return x[:, :n].cpu().numpy(), ctl
 
 
-def test_cg_is_the_stacked_recurrence():
-    """config 1, 10 iterations, three different right-hand sides: one Krylov space (three separate solves are 1.3e-2 away, tests/test_components_cpu.py)"""
+OTHER_COUNTS = [1, 2, 5, 8]     # besides 3: the scalar case, the truncating PARTIAL_STRIDE / n_components (5), the full row (8)
+
+
+def _scalar_solve(op, b, max_iter, tol=0.0, inv=None):
+    """the scalar SolverCG on the same handle: (solution, control)"""
+    xs = op.initialize_dof_vector()
+    ctl = pkg.IterationNumberControl(max_iter, tol)
+    pkg.SolverCG(ctl).solve(op, xs, _t().from_numpy(np.array(b)).to("cuda:0"), pkg.DiagonalMatrix(inv))
+    return xs.cpu().numpy(), ctl
+
+
+def _stacked_recurrence(nc):
     pr, b, op = _config1()
-    B = R.rhs_blocks(b)
+    B = R.rhs_blocks(b, nc)
     xr, k, res = R.cg(pr.vmult, B, 10)
     x, ctl = _solve(op, B, 10)
-    errs = [rel(x[c], xr[c]) for c in range(3)]
-    print("config 1, per component:", " ".join(f"{e:.2e}" for e in errs))
-    assert ctl.last_step() == k == 10 and max(errs) <= TOL_CG
+    errs = [rel(x[c], xr[c]) for c in range(nc)]
+    print(f"config 1, {nc} components, per component:", " ".join(f"{e:.2e}" for e in errs))
+    assert x.shape[0] == nc and ctl.last_step() == k == 10 and max(errs) <= TOL_CG
     assert abs(ctl.last_value() - res) <= 1e-10 * res
     assert ctl.apply_kernel.startswith("apply_pencil_components_kernel<2,false,")
+    if nc == 1:
+        xs, _ = _scalar_solve(op, B[0], 10)
+        assert rel(xs, xr[0]) <= TOL_CG and rel(x[0], xs) <= TOL_CG
+
+
+def test_cg_is_the_stacked_recurrence():
+    """config 1, 10 iterations, three different right-hand sides: one Krylov space (three separate solves are 1.3e-2 away, tests/test_components_cpu.py)"""
+    _stacked_recurrence(3)
+
+
+@pytest.mark.parametrize("nc", OTHER_COUNTS)
+def test_cg_is_the_stacked_recurrence_at_other_component_counts(nc):
+    """... and 1, 2, 5 and 8 of them (noise drift of these references: tests/test_components_cpu.py); one component is the scalar SolverCG"""
+    _stacked_recurrence(nc)
 
 
 def test_cg_identical_right_hand_sides_reproduce_the_scalar_solver():
@@ -319,31 +415,228 @@ def test_cg_identical_right_hand_sides_reproduce_the_scalar_solver():
         assert rel(x[c], xs.cpu().numpy()) <= TOL_CG
 
 
-def test_cg_with_the_inverse_diagonal():
-    """p = 4 (4,4,4), deformed, step-64 kappa, bp5_compute_diagonal(invert = 1), 10 iterations: the reference's noise drift on this case is
-    3.8e-16 (tests/test_components_cpu.py asserts < 1e-13), so the fixed-iteration comparison holds to TOL_CG"""
-    prd, Bd, inv = diag_case()
-    op = pkg.PoissonOperator(pkg.BrickMesh(4, (4, 4, 4), deform_amp=0.04), pkg.QUAD_GAUSS, pkg.COEF_STEP64)
+def _with_the_inverse_diagonal(nc):
+    prd, Bd, inv = diag_case(nc)
+    op = _operator(4, pkg.QUAD_GAUSS, cells=(4, 4, 4))
     dinv = op.compute_diagonal(invert=True)
     assert rel(dinv.cpu().numpy(), inv) <= 1e-13
     xr, k, _ = R.cg(prd.vmult, Bd, 10, inv_diag=inv)
     x, ctl = _solve(op, Bd, 10, inv=dinv)
-    errs = [rel(x[c], xr[c]) for c in range(3)]
-    print("p = 4 with inverse diagonal, per component:", " ".join(f"{e:.2e}" for e in errs))
-    assert ctl.last_step() == k == 10 and max(errs) <= TOL_CG
+    errs = [rel(x[c], xr[c]) for c in range(nc)]
+    print(f"p = 4 with inverse diagonal, {nc} components, per component:", " ".join(f"{e:.2e}" for e in errs))
+    assert x.shape[0] == nc and ctl.last_step() == k == 10 and max(errs) <= TOL_CG
+    if nc == 1:
+        xs, _ = _scalar_solve(op, Bd[0], 10, inv=dinv)
+        assert rel(xs, xr[0]) <= TOL_CG and rel(x[0], xs) <= TOL_CG
+
+
+def test_cg_with_the_inverse_diagonal():
+    """p = 4 (4,4,4), deformed, step-64 kappa, bp5_compute_diagonal(invert = 1), 10 iterations: the reference's noise drift on this case is
+    3.8e-16 (tests/test_components_cpu.py asserts < 1e-13), so the fixed-iteration comparison holds to TOL_CG"""
+    _with_the_inverse_diagonal(3)
+
+
+@pytest.mark.parametrize("nc", OTHER_COUNTS)
+def test_cg_with_the_inverse_diagonal_at_other_component_counts(nc):
+    _with_the_inverse_diagonal(nc)
+
+
+def _tolerance_stop(check_every, nc):
+    pr, b, op = _config1()
+    B = R.rhs_blocks(b, nc)
+    tol = 1e-8 * np.linalg.norm(B)
+    xr, k, _ = R.cg(pr.vmult, B, 1000, tol=tol)
+    x, ctl = _solve(op, B, 1000, tol=tol, check_every=check_every)
+    assert x.shape[0] == nc and ctl.last_step() == k and ctl.last_value() <= tol
+    true_res = np.linalg.norm(B - R.vmult(pr, x))
+    print(f"{nc} components: iterations {k}, recomputed FP64 residual {true_res:.3e}, tolerance {tol:.3e}")
+    assert true_res <= tol * (1 + 1e-6)
+    if nc == 1:      # 53 iterations; the reference moves by 2.3e-16 under operator noise over that many, so TOL_CG holds here too
+        xs, cs = _scalar_solve(op, B[0], 1000, tol=tol)
+        assert cs.last_step() == k and rel(xs, xr[0]) <= TOL_CG and rel(x[0], xs) <= TOL_CG
 
 
 @pytest.mark.parametrize("check_every", [0, 3])
 def test_cg_tolerance_stop(check_every):
-    pr, b, op = _config1()
-    B = R.rhs_blocks(b)
-    tol = 1e-8 * np.linalg.norm(B)
-    xr, k, _ = R.cg(pr.vmult, B, 1000, tol=tol)
-    x, ctl = _solve(op, B, 1000, tol=tol, check_every=check_every)
-    assert ctl.last_step() == k and ctl.last_value() <= tol
-    true_res = np.linalg.norm(B - R.vmult(pr, x))
-    print(f"iterations {k}, recomputed FP64 residual {true_res:.3e}, tolerance {tol:.3e}")
-    assert true_res <= tol * (1 + 1e-6)
+    _tolerance_stop(check_every, 3)
+
+
+@pytest.mark.parametrize("nc", OTHER_COUNTS)
+@pytest.mark.parametrize("check_every", [0, 3])
+def test_cg_tolerance_stop_at_other_component_counts(check_every, nc):
+    _tolerance_stop(check_every, nc)
+
+
+# ------------------------------------------------------------------ 7b. the CG at the capped grid
+VB, MAXBLK, PARTIAL_STRIDE = 256, 2048, 8192      # bp5_kernels.hpp: threads of a streaming workgroup, their grid cap, the length of a partial-sum row
+
+
+def cg_grids(n_owned, nc):
+    """(uncapped workgroups of the kernels that take two DoFs per thread, of the one that takes one, columns of a partial-sum row per component):
+    bp5_cg_solve_components launches min(uncapped, columns) workgroups per component"""
+    return min(-(-n_owned // (2 * VB)), MAXBLK), min(-(-n_owned // VB), MAXBLK), PARTIAL_STRIDE // nc
+
+
+def _capped():
+    """the numpy problem of tests/test_components_cpu.py: capped_case() and the operator on it, built once"""
+    if "capped" not in _cache:
+        pr, b, inv = capped_case()
+        op = pkg.PoissonOperator(pkg.BrickMesh(4, CAPPED_CELLS, deform_amp=0.04), pkg.QUAD_GAUSS, pkg.COEF_STEP64)
+        dinv = op.compute_diagonal(invert=True)
+        assert op.mf_data.n_owned == op.mf_data.n_local == pr.mesh.n_dofs == 85 ** 3 and rel(dinv.cpu().numpy(), inv) <= 1e-13
+        _cache["capped"] = (pr, b, inv, op, dinv)
+    return _cache["capped"]
+
+
+@pytest.mark.parametrize("with_diag", [False, True])
+@pytest.mark.parametrize("nc,workgroups", [(7, 1170), (8, 1024)])
+def test_cg_at_the_capped_grid(nc, workgroups, with_diag):
+    """85^3 DoFs: more than 512 PARTIAL_STRIDE / n_components, so every reducing kernel runs on as many workgroups per component as the row has
+    columns for it and takes a second grid-stride trip; eight components fill the row to its last word, with the next row right behind it.
+    Three iterations: the references move by < 3e-16 under operator noise (tests/test_components_cpu.py)"""
+    pr, b, inv, op, dinv = _capped()
+    n = 85 ** 3
+    two, one, cols = cg_grids(n, nc)
+    assert cols == workgroups < two <= one and n > workgroups * 2 * VB, (two, one, cols)      # the cap bites; a second trip at two DoFs per thread
+    assert nc * cols == (8190 if nc == 7 else PARTIAL_STRIDE)
+    B = R.rhs_blocks(b, nc)
+    xr, k, res = R.cg(pr.vmult, B, CAPPED_ITERATIONS, inv_diag=inv if with_diag else None)
+    x, ctl = _solve(op, B, CAPPED_ITERATIONS, inv=dinv if with_diag else None)
+    errs = [rel(x[c], xr[c]) for c in range(nc)]
+    print(f"capped grid, {nc} components on {workgroups} workgroups each, {'inverse diagonal' if with_diag else 'no preconditioner'}: "
+          f"max error {max(errs):.2e}, residual {ctl.last_value():.6e} (numpy {res:.6e})")
+    assert ctl.last_step() == k == CAPPED_ITERATIONS == 3 and max(errs) <= TOL_CG
+    assert abs(ctl.last_value() - res) <= 1e-10 * res
+    assert ctl.apply_kernel.startswith("apply_pencil_components_kernel<4,false,")
+
+
+def test_operator_at_the_capped_grid_size():
+    """the same handle and sources, eight components: 927 teams, atomics under contention"""
+    pr, b, inv, op, dinv = _capped()
+    n = op.mf_data.n_local
+    assert launch_shape(4, op.mf_data.mesh.n_cells)[1:] == (927, 927)
+    B = R.rhs_blocks(b, N_BLOCKS)
+    ref = R.vmult(pr, B)
+    s, d = block(B, n), block(np.full((N_BLOCKS, n), np.nan), n, pad_value=SENTINEL)
+    op.vmult(d, s)
+    check_padding(d, n, SENTINEL)
+    got = d[:, :n].cpu().numpy()
+    errs = [rel(got[c], ref[c]) for c in range(N_BLOCKS)]
+    print(f"85^3 DoFs, eight components: max error vs oracle {max(errs):.2e}")
+    assert not np.isnan(got).any() and max(errs) <= TOL_OP
+
+
+# ------------------------------------------------------------------ 7c. the solver's edges
+# EDGES (tests/test_components_cpu.py): (components, the block whose right-hand side is zeroed where one is)
+def _edge_case(nc):
+    """p = 4 (4,4,4), deformed, step-64 kappa (diag_case): (problem, right-hand sides, operator)"""
+    pr, B, _ = diag_case(nc)
+    return pr, B, _operator(4, pkg.QUAD_GAUSS, cells=(4, 4, 4))
+
+
+def _solve_prefilled(op, B, max_iter, inv=None, fill=3.0):
+    """x = `fill` on every DoF, sentinel padding"""
+    n = op.mf_data.n_local
+    x, b = block(np.full(B.shape, fill), n, pad_value=SENTINEL), block(B, n)
+    ctl = pkg.IterationNumberControl(max_iter, 0.0)
+    pkg.SolverCG(ctl).solve(op, x, b, pkg.DiagonalMatrix(inv))
+    check_padding(x, n, SENTINEL)
+    return x[:, :n].cpu().numpy(), ctl
+
+
+@pytest.mark.parametrize("nc,zeroed", EDGES)
+def test_cg_zero_right_hand_side(nc, zeroed):
+    pr, B, op = _edge_case(nc)
+    x, ctl = _solve_prefilled(op, np.zeros_like(B), 5)
+    assert ctl.last_step() == 0 and ctl.last_value() == 0.0 and np.array_equal(x, np.zeros_like(B))
+
+
+@pytest.mark.parametrize("nc,zeroed", EDGES)
+def test_cg_zero_right_hand_side_in_one_block(nc, zeroed):
+    """g, d and A d of that block are exact zeros (sums of zeros, whatever the order of the atomics), so its x is; the others do not notice.
+    With the inverse diagonal: the ten-iteration reference without it moves by 1e-12 under operator noise (tests/test_components_cpu.py)"""
+    pr, B, inv = zero_block_case(nc, zeroed)
+    op = _edge_case(nc)[2]
+    dinv = op.compute_diagonal(invert=True)
+    assert rel(dinv.cpu().numpy(), inv) <= 1e-13 and not B[zeroed].any()
+    xr, k, res = R.cg(pr.vmult, B, 10, inv_diag=inv)
+    x, ctl = _solve_prefilled(op, B, 10, inv=dinv)
+    assert ctl.last_step() == k == 10 and abs(ctl.last_value() - res) <= 1e-10 * res
+    assert np.array_equal(x[zeroed], np.zeros(B.shape[1])) and not xr[zeroed].any()
+    errs = [rel(x[c], xr[c]) for c in range(nc) if c != zeroed]
+    print(f"{nc} components, block {zeroed} zero: max error of the others {max(errs):.2e}")
+    assert len(errs) == nc - 1 and max(errs) <= TOL_CG
+
+
+@pytest.mark.parametrize("nc,zeroed", EDGES)
+def test_cg_zero_iterations(nc, zeroed):
+    pr, B, op = _edge_case(nc)
+    x, ctl = _solve_prefilled(op, B, 0)
+    assert ctl.last_step() == 0 and np.array_equal(x, np.zeros_like(B))
+    assert abs(ctl.last_value() - np.linalg.norm(B)) <= 1e-12 * np.linalg.norm(B)
+
+
+@pytest.mark.parametrize("nc,zeroed", EDGES)
+def test_cg_breakdown_is_reported_and_does_not_stick(nc, zeroed):
+    """d.Ad == 0 (an all-zero metric) is BP5_ERR_BREAKDOWN, as from the scalar solver (tests/test_gpu_parity.py); the flag does not outlive the
+    solve on that handle (metric restored), and a fresh operator is not affected"""
+    pr = O.Problem(2, (2, 2, 2), O.QUAD_GAUSS)
+    B = R.rhs_blocks(pr.rhs(), nc)
+    xr, k, _ = R.cg(pr.vmult, B, 3)
+    op = pkg.PoissonOperator(pkg.BrickMesh(2, (2, 2, 2)), pkg.QUAD_GAUSS)
+    metric = op.coef.clone()
+    op.coef.zero_()
+    n = op.mf_data.n_local
+    with pytest.raises(pkg.BP5Error) as e:
+        pkg.SolverCG(pkg.IterationNumberControl(5, 0.0)).solve(op, op.initialize_block_vector(nc), block(B, n, extra=0), pkg.DiagonalMatrix())
+    assert e.value.status == 6
+    op.coef.copy_(metric)
+    for healthy in (op, pkg.PoissonOperator(pkg.BrickMesh(2, (2, 2, 2)), pkg.QUAD_GAUSS)):
+        x, ctl = _solve(healthy, B, 3)
+        assert ctl.last_step() == k == 3 and max(rel(x[c], xr[c]) for c in range(nc)) <= TOL_CG
+
+
+def test_cg_sequence_on_one_handle():
+    """The workspace of bp5_cg_solve_components grows (2 -> 8 components) and is reused at other component counts and strides, and the partial
+    sums, scalars and state words are the scalar solvers': every block solve against numpy (noise drift of these references:
+    tests/test_components_cpu.py), and the scalar SolverCG and vmult of the handle (block kernel: no atomics) give the same bits before and after"""
+    torch = _t()
+    p, cells, iters = 4, SEQUENCE_CELLS, SEQUENCE_ITERATIONS
+    pr, b_lex, inv = sequence_case()
+    op = pkg.PoissonOperator(pkg.BrickMesh(p, cells, deform_amp=0.04, cell_block=(4, 4, 4), dof_numbering=1, cell_block_order=1), pkg.QUAD_GAUSS,
+                             pkg.COEF_STEP64)
+    op.mf_data.set_apply_variant(56)
+    n = op.mf_data.n_local
+    perm = op.mf_data.mesh.global_ids.astype(np.int64)       # local index -> lexicographic id of the oracle
+    dinv = op.compute_diagonal(invert=True)
+    assert rel(dinv.cpu().numpy(), inv[perm]) <= 1e-13
+    b, s = torch.from_numpy(b_lex[perm]).to("cuda:0"), torch.from_numpy(O.deterministic_src(n, seed=9)).to("cuda:0")
+
+    def scalar():
+        x, v = op.initialize_dof_vector(), op.initialize_dof_vector()
+        ctl = pkg.IterationNumberControl(iters, 0.0)
+        pkg.SolverCG(ctl).solve(op, x, b, pkg.DiagonalMatrix(dinv))
+        assert ctl.last_step() == iters and ctl.apply_kernel.startswith("apply_block_kernel")
+        op.vmult(v, s)
+        return x, v, ctl.last_value()
+
+    before = scalar()
+    xs, _, _ = O.cg_plain(pr.vmult, b_lex, iters, diag=inv)
+    assert rel(before[0].cpu().numpy(), xs[perm]) <= TOL_CG
+    for nc, extra, with_diag in SEQUENCE:
+        B = R.rhs_blocks(b_lex, nc)
+        xr, k, res = R.cg(pr.vmult, B, iters, inv_diag=inv if with_diag else None)
+        x = block(np.full((nc, n), np.nan), n, pad_value=SENTINEL, extra=extra)
+        assert x.shape[1] == n + (n & 1) + extra
+        ctl = pkg.IterationNumberControl(iters, 0.0)
+        pkg.SolverCG(ctl).solve(op, x, block(B[:, perm], n, extra=extra), pkg.DiagonalMatrix(dinv if with_diag else None))
+        check_padding(x, n, SENTINEL)
+        errs = [rel(x[c, :n].cpu().numpy(), xr[c][perm]) for c in range(nc)]
+        print(f"{nc} components, ld = n_local + {x.shape[1] - n}: max error {max(errs):.2e}")
+        assert ctl.last_step() == k == iters and max(errs) <= TOL_CG and abs(ctl.last_value() - res) <= 1e-10 * res
+        assert ctl.apply_kernel.startswith("apply_pencil_components_kernel<4,false,")
+    after = scalar()
+    assert torch.equal(before[0], after[0]) and torch.equal(before[1], after[1]) and before[2] == after[2]
 
 
 # ------------------------------------------------------------------ 8. facade
