@@ -273,9 +273,10 @@ extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
 static bool product_variant(int degree, int v)
 {
   if (v == 0) return true;
-  if (v >= 100) return v < 200 && product_variant(degree, v - 100) && v - 100 >= 10 && v - 100 <= 14; // team kernel, atomic scatter
+  const VariantInfo d = decode_variant(v);
+  if (d.atomic_scatter) return v < 200 && d.family == VARIANT_TEAM && product_variant(degree, v - 100); // team kernel, atomic scatter
   if (v == 10 || v == 50 || v == 70) return true;
-  if (v == 56 && block_lpc(degree) != 0) return true;
+  if (d.family == VARIANT_BLOCK && block_lpc(degree) != 0) return true;
   switch (degree) {
     case 1: case 3: return v == 1;
     case 4: return (v >= 1 && v <= 6) || (v >= 11 && v <= 14) || (v >= 48 && v <= 62) || v == 71 || v == 72;
@@ -1098,8 +1099,7 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
 // kernels that define every entry of dst themselves (owner stores + combine pass) need no zero-fill
 static bool variant_overwrites(const bp5_mf *mf, int ev)
 {
-  const int v = ev % 100;
-  return ev < 100 && ((v >= 10 && v <= 14) || (v >= 48 && v <= 63)) && !(mf->geometry_mode == BP5_GEOM_AFFINE && mf->degree != 4);
+  return decode_variant(ev).overwrites && !(mf->geometry_mode == BP5_GEOM_AFFINE && mf->degree != 4); // (affine: the pencil kernel but at p = 4)
 }
 
 // One operator application: resolves the variant for the call's range (unless the caller fixed it) and dispatches on the degree

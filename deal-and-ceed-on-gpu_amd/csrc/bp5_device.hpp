@@ -1,6 +1,9 @@
-// Shared by the device translation units of libbp5: the handle, the launch templates of the fused operator kernels and the
-// per-degree variant dispatch.  bp5_device.hip holds the C ABI; bp5_apply_pN.hip instantiate apply_degree_impl<N> (one
-// translation unit per degree so that `make -j` compiles them side by side).
+// Shared by the device translation units of libbp5, in this order: the handle (bp5_mf); what an apply variant number means (decode_variant) and
+// what one operator application carries (ApplyCall); one launcher per kernel family (launch_apply_t: pencil, launch_apply_components_t,
+// launch_block_t, launch_team_t, launch_march_t), which share apply_args and zero_dst; the list of builds of the default block kernel and its
+// resolver (DefaultBlockBuilds, launch_block_default: variant 56 of every operator class); and the per-degree dispatch apply_degree_impl.
+// bp5_device.hip holds the C ABI; bp5_apply_pN.hip instantiate apply_degree_impl<N> and apply_components_degree_impl<N> (one translation unit
+// per degree so that `make -j` compiles them side by side).
 #pragma once
 #include "bp5_internal.hpp"
 #include "bp5_kernels.hpp"
@@ -172,6 +175,25 @@ struct FuseState {
   uint32_t n_cols = 0;        // columns of d_partials written so far (block kernel workgroups, then the combine pass, then the unpack kernels)
   bool ghosts_zeroed = false; // the exchange's unpack kernel has zeroed the ghost ranges of v and p
 };
+// What an apply variant number means (include/bp5.h: bp5_mf_set_apply_variant), the ONE place that knows the ranges: 1xx = variant xx with the
+// global-atomic scatter, 0-6 pencil shapes, 10-14 team kernel, 48-63 block kernel (56 its default shape, the others A/B siblings and older shapes),
+// 70-72 z-marching, 90 the pencil kernel of hanging-node meshes; anything else is a timing-only build (libbp5_timing.so) or unknown
+enum VariantFamily { VARIANT_PENCIL, VARIANT_TEAM, VARIANT_MARCH, VARIANT_BLOCK, VARIANT_BLOCK_SIBLING, VARIANT_HANGING_PENCIL, VARIANT_OTHER };
+struct VariantInfo {
+  VariantFamily family;
+  bool atomic_scatter;    // 1xx: the team kernel with the global-atomic scatter (A/B tests)
+  bool shared_by_atomics; // 54 / 55: brick-surface DoFs by atomics
+  bool csr_combine;       // 48: per-DoF CSR combine kernel instead of the run-length one
+  bool overwrites;        // owner stores + combine pass define every entry of dst: no zero-fill needed (team and block kernels, not 1xx)
+};
+constexpr VariantInfo decode_variant(int v)
+{
+  const int b = v % 100;
+  const VariantFamily f = b <= 6 ? VARIANT_PENCIL : b >= 10 && b <= 14 ? VARIANT_TEAM : b == 56 ? VARIANT_BLOCK : b >= 48 && b <= 63 ? VARIANT_BLOCK_SIBLING
+                        : b >= 70 && b <= 72 ? VARIANT_MARCH : b == 90 ? VARIANT_HANGING_PENCIL : VARIANT_OTHER;
+  return {f, v >= 100, b == 54 || b == 55, b == 48, v < 100 && (f == VARIANT_TEAM || f == VARIANT_BLOCK || f == VARIANT_BLOCK_SIBLING)};
+}
+
 // What ONE operator application is asked to do, and what its launches report back.  It lives on the caller's stack and travels by
 // reference down launch_apply -> apply_degree_impl -> launch_*_t -> launch_combine: nothing of it is kept on the handle.
 enum { EXCHANGE_NONE = 0, EXCHANGE_BOUNDARY_FIRST = 1, EXCHANGE_GHOST_ROWS_FIRST = 2 };
@@ -180,13 +202,15 @@ struct ApplyCall {
   bool overwrite = false;      // the launch must leave dst = A src (no prior zeroing by the caller); otherwise dst += A src
   int variant = 0;             // resolved apply variant: launch_apply takes it from effective_variant(handle, range) ...
   bool keep_variant = false;   // ... unless the caller fixed it (phased applications: ONE kernel family for every range)
-  // the switches a variant implies (set_variant).  Derived from the variant number alone, for every degree and operator; their only readers are
-  // the p = 4 block / team launches and the combine pass behind them (other degrees, Helmholtz and hanging-node meshes reject 48, 54, 55
-  // before any launch)
-  bool atomic_scatter = false;    // variants >= 100: the team kernel with the global-atomic scatter (A/B tests)
-  bool shared_by_atomics = false; // variants 54 / 55: brick-surface DoFs by atomics
-  bool csr_combine = false;       // variant 48: per-DoF CSR combine kernel instead of the run-length one -- for the immediate AND a deferred pass
-  void set_variant(int v) { variant = v; atomic_scatter = v >= 100; shared_by_atomics = v % 100 == 54 || v % 100 == 55; csr_combine = v % 100 == 48; }
+  // the switches a variant implies (decode_variant), for every degree and operator; their only readers are the p = 4 block / team launches and
+  // the combine pass behind them (other degrees, Helmholtz and hanging-node meshes reject 48, 54, 55 before any launch).  csr_combine holds for
+  // the immediate AND a deferred pass
+  bool atomic_scatter = false, shared_by_atomics = false, csr_combine = false;
+  void set_variant(int v)
+  {
+    const VariantInfo d = decode_variant(v);
+    variant = v; atomic_scatter = d.atomic_scatter; shared_by_atomics = d.shared_by_atomics; csr_combine = d.csr_combine;
+  }
   // block kernel
   uint32_t b0 = 0, b1 = 0;     // block range of [c0, c1) (0,0 = all blocks; filled in by the dispatch)
   bool combine_later = false;  // cell ranges: partial slab now, ONE combine pass (per window) launched by the caller after the last range
@@ -277,19 +301,41 @@ inline void fill_shape(ShapeArg<n> &sh, const bp5_mf *mf)
   }
 }
 
+// What every operator launch takes from the handle (affine builds read ONE scalar plane, cells n^3 entries apart); the launcher adds range and team counts
+inline ApplyArgs apply_args(const bp5_mf *mf, bool affine, const double *coef, const double *src, double *dst)
+{
+  ApplyArgs a{};
+  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
+  a.plane_stride = mf->coef_plane_stride; a.cell_stride = affine ? (uint64_t)mf->n3 : mf->coef_cell_stride;
+  a.gcell = mf->d_gcell; a.n_cells_total = mf->n_cells;
+  a.hang_mask = mf->d_hang_mask; a.hang_I = mf->d_hang_I;
+  return a;
+}
+inline int zero_dst(bp5_mf *mf, double *dst) // ahead of a launch that accumulates (atomic scatter; owner stores that do not reach every entry)
+{
+  HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+  return BP5_OK;
+}
+
+// The degree's default pencil launch: p <= 3 four one-wave teams per workgroup, p >= 4 one four-wave team; n^2 lanes per cell, every plane prefetched.
+// Users: variant 0 of every operator class (interior stores at p >= 5; hanging + affine included) and the block-vector kernel
+template <int DEG>
+struct DefaultPencil {
+  static constexpr int TW = DEG <= 3 ? 1 : 4, LPC = (DEG + 1) * (DEG + 1), TPB = DEG <= 3 ? 4 : 1;
+  static constexpr bool PF = true;
+};
+
+// overwrite: the launch must leave dst = A src; the kernel accumulates with atomics, so dst is zeroed first
 template <int P, bool COLL, int TW, int LPC, int TPB, bool PF, int ABL = 0>
-inline int launch_apply_t(bp5_mf *mf, ApplyCall &, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1)
+inline int launch_apply_t(bp5_mf *mf, ApplyCall &, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite)
 {
   constexpr int n = P + 1;
   constexpr int CPT = 64 * TW / LPC;
   using L = LdsLayout<n, LPC>;
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
-  a.plane_stride = mf->coef_plane_stride; a.cell_stride = (ABL & 1024) ? (uint64_t)mf->n3 : mf->coef_cell_stride; // (affine builds read ONE scalar plane)
+  if ((ABL & BLK_HANG) && !mf->has_hanging) return fail(BP5_ERR_INVALID, "the hanging-node build needs constraint masks");
+  if (overwrite) BP5_TRY(zero_dst(mf, dst));
+  ApplyArgs a = apply_args(mf, (ABL & BLK_AFFINE) != 0, coef, src, dst);
   a.cell_begin = c0; a.cell_end = c1;
-  a.gcell = mf->d_gcell; a.n_cells_total = mf->n_cells;
-  a.hang_mask = mf->d_hang_mask; a.hang_I = mf->d_hang_I;
-  if ((ABL & 2097152) && !mf->has_hanging) return fail(BP5_ERR_INVALID, "the hanging-node build needs constraint masks");
   a.n_teams = (c1 - c0 + CPT - 1) / CPT;
   const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
   a.teams_per_xcd = (nblk + 7) / 8;
@@ -311,11 +357,8 @@ inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_compo
   constexpr int n = P + 1;
   constexpr int CPT = 64 * TW / LPC;
   using L = LdsLayout<n, LPC>;
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
-  a.plane_stride = mf->coef_plane_stride; a.cell_stride = mf->coef_cell_stride;
+  ApplyArgs a = apply_args(mf, false, coef, src, dst);
   a.cell_begin = 0; a.cell_end = mf->n_cells;
-  a.n_cells_total = mf->n_cells;
   a.n_teams = (mf->n_cells + CPT - 1) / CPT;
   const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
   a.teams_per_xcd = (nblk + 7) / 8;
@@ -328,15 +371,14 @@ inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_compo
   KERNEL_CHECK();
   return BP5_OK;
 }
-// the degree's default pencil shape (APPLY_CASE(P, 0, ...)), both quadratures
+// the degree's default pencil shape, both quadratures
 template <int DEG>
 int apply_components_degree_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
 {
-  constexpr int n2 = (DEG + 1) * (DEG + 1);
-  constexpr int TW = DEG <= 3 ? 1 : 4, TPB = DEG <= 3 ? 4 : 1;
+  using DP = DefaultPencil<DEG>;
   if (mf->n_cells == 0) return BP5_OK;
-  if (mf->quadrature == BP5_QUAD_GLL) return launch_apply_components_t<DEG, true, TW, n2, TPB>(mf, coef, n_components, ld, src, dst);
-  return launch_apply_components_t<DEG, false, TW, n2, TPB>(mf, coef, n_components, ld, src, dst);
+  if (mf->quadrature == BP5_QUAD_GLL) return launch_apply_components_t<DEG, true, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst);
+  return launch_apply_components_t<DEG, false, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst);
 }
 
 // LDS bytes of one block-kernel workgroup: transpose tiles of the cell slots (two per slot where the cells span waves: BlockPass::PP),
@@ -475,17 +517,13 @@ inline int launch_block_t(bp5_mf *mf, ApplyCall &call, const double *coef, const
     HIP_TRY(hipMemsetAsync(mf->d_stamps, 0, 4096 * 16 * sizeof(unsigned long long), mf->stream));
     bp.stamps = mf->d_stamps;
   }
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
-  a.plane_stride = mf->coef_plane_stride; a.cell_stride = (ABL & BLK_AFFINE) ? (uint64_t)mf->n3 : mf->coef_cell_stride; // (affine builds read ONE scalar plane)
+  ApplyArgs a = apply_args(mf, (ABL & BLK_AFFINE) != 0, coef, src, dst);
   a.cell_begin = 0; a.cell_end = mf->n_cells; a.n_teams = dp->n_groups; a.teams_per_xcd = 0;
-  a.gcell = mf->d_gcell; a.n_cells_total = mf->n_cells;
-  a.hang_mask = mf->d_hang_mask; a.hang_I = mf->d_hang_I;
   if ((ABL & BLK_HANG) && !mf->has_hanging) return fail(BP5_ERR_INVALID, "the hanging-node build needs constraint masks");
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const bool set = overwrite && dp->covers_all;
-  if (overwrite && !set) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+  if (overwrite && !set) BP5_TRY(zero_dst(mf, dst));
   if (bp.signal && atomic_shared) return fail(BP5_ERR_INVALID, "boundary-first signal: owner-store launches only");
   const dim3 grid(n_wg), block(256);
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_block_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", LPC,
@@ -553,11 +591,8 @@ inline int launch_team_t(bp5_mf *mf, ApplyCall &call, const double *coef, const 
   TeamPlan tp{};
   bp5_mf::DevPlan *dp = nullptr;
   BP5_TRY(get_plan(mf, CPT, tp, &dp));
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
-  a.plane_stride = mf->coef_plane_stride; a.cell_stride = (OPT & 1024) ? (uint64_t)mf->n3 : mf->coef_cell_stride; // (affine builds read ONE scalar plane)
+  ApplyArgs a = apply_args(mf, (OPT & BLK_AFFINE) != 0, coef, src, dst);
   a.cell_begin = c0; a.cell_end = c1;
-  a.gcell = mf->d_gcell; a.n_cells_total = mf->n_cells;
   a.n_teams = (c1 + CPT - 1) / CPT - c0 / CPT;
   a.teams_per_xcd = (a.n_teams + 7) / 8;
   ShapeArg<n> sh;
@@ -567,11 +602,11 @@ inline int launch_team_t(bp5_mf *mf, ApplyCall &call, const double *coef, const 
   const bool whole = (c0 == 0 && c1 == mf->n_cells);
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_team_kernel<%d,%s,%d,%d,%s,", P, COLL ? "true" : "false", TW, LPC, PF ? "true" : "false");
   if (!whole || call.atomic_scatter) {
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+    if (overwrite) BP5_TRY(zero_dst(mf, dst));
     hipLaunchKernelGGL((apply_team_kernel<P, COLL, TW, LPC, PF, SC_ATOMIC, OPT>), grid, block, lds, mf->stream, a, tp, sh);
   } else {
     const bool set = overwrite && dp->covers_all;
-    if (overwrite && !set) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+    if (overwrite && !set) BP5_TRY(zero_dst(mf, dst));
     if (set) hipLaunchKernelGGL((apply_team_kernel<P, COLL, TW, LPC, PF, SC_OWNER_SET, OPT>), grid, block, lds, mf->stream, a, tp, sh);
     else hipLaunchKernelGGL((apply_team_kernel<P, COLL, TW, LPC, PF, SC_OWNER_ADD, OPT>), grid, block, lds, mf->stream, a, tp, sh);
     KERNEL_CHECK();
@@ -589,9 +624,9 @@ inline int launch_team_t(bp5_mf *mf, ApplyCall &call, const double *coef, const 
   (coll ? FN<P, true, BP5_UNPAREN TARGS>(mf, call, __VA_ARGS__) : FN<P, false, BP5_UNPAREN TARGS>(mf, call, __VA_ARGS__))
 #define TEAM_CASE(P, V, TW, LPC, PF) BP5_CASE(P, V) return LAUNCH_COLL(launch_team_t, P, (TW, LPC, PF), coef, src, dst, c0, c1, overwrite)
 
-// z-marching kernel (whole cell range only; partial ranges take the plain pencil kernel)
+// z-marching kernel (whole cell range only; partial ranges take the plain pencil kernel); atomic scatter: overwrite zeroes dst first
 template <int P, bool COLL, int TW, int LPC, bool PF, int ABL = 0>
-inline int launch_march_t(bp5_mf *mf, ApplyCall &, const double *coef, const double *src, double *dst)
+inline int launch_march_t(bp5_mf *mf, ApplyCall &, const double *coef, const double *src, double *dst, bool overwrite)
 {
   constexpr int n = P + 1;
   constexpr int CPT = 64 * TW / LPC;
@@ -609,11 +644,9 @@ inline int launch_march_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
   MarchPlan mp{};
   mp.team_off = it->second.team_off; mp.entries = it->second.entries; mp.n_teams = it->second.n_teams;
   mp.teams_per_xcd = (mp.n_teams + 7) / 8;
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
-  a.plane_stride = mf->coef_plane_stride; a.cell_stride = (ABL & 1024) ? (uint64_t)mf->n3 : mf->coef_cell_stride; // (affine builds read ONE scalar plane)
+  if (overwrite) BP5_TRY(zero_dst(mf, dst));
+  ApplyArgs a = apply_args(mf, (ABL & BLK_AFFINE) != 0, coef, src, dst);
   a.cell_begin = 0; a.cell_end = mf->n_cells; a.n_teams = mp.n_teams; a.teams_per_xcd = mp.teams_per_xcd;
-  a.gcell = mf->d_gcell; a.n_cells_total = mf->n_cells;
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const size_t lds = (size_t)CPT * L::CS * sizeof(double);
@@ -623,76 +656,133 @@ inline int launch_march_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
   return BP5_OK;
 }
 
-// variant table: (degree, variant) -> (TW, LPC, TPB, PF); variant 0 = default for the degree
-#define APPLY_CASE(P, V, TW, LPC, TPB, PF)                                                                         \
-  BP5_CASE(P, V) {                                                                                                 \
-    if (overwrite && hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream) != hipSuccess)             \
-      return fail(BP5_ERR_HIP, "hipMemsetAsync");                                                                  \
-    return LAUNCH_COLL(launch_apply_t, P, (TW, LPC, TPB, PF), coef, src, dst, c0, c1);                              \
-  }
-
-// overwrite: the launch must leave dst = A src (no prior zeroing by the caller); otherwise dst += A src
-template <int P>
-inline int launch_affine(bp5_mf *mf, ApplyCall &call, const double *src, double *dst, uint32_t c0, uint32_t c1)
-{ // TW = 4 teams when n^2 lanes per cell pack well into 256 threads, as for the 6-plane default
-  constexpr int n2 = (P + 1) * (P + 1);
-  constexpr int LPC = n2;
-  constexpr bool PF = true;
+// ------------------------------------------------------------------------------------ variant 56: the default block kernel
+// The builds of the default block kernel that exist, per degree: a mask each, Gauss-only where marked (the others are compiled for both
+// quadratures).  The list IS the inventory: launch_block_default launches nothing else, every entry is instantiated.  Within an operator class
+// the builds with more optional features come first.  Every degree: Poisson on double planes, plain or fused, packed or lattice indices; on
+// float planes (never fused); Helmholtz and hanging nodes, plain or fused, packed indices only.  p = 4 alone: the face carry (in every lattice
+// build; BP5_TUNE_FACE_CARRY switches it per launch), non-temporal metric loads (Gauss only; with lattice blocks, or on hanging-node meshes; never
+// on float planes), the affine build, and two older shapes for plans without packed indices (run-length write-out with list loads; list write-out)
+template <int M, bool GAUSS_ONLY = false> struct Bld {};
+template <typename... B> struct BuildList {};
+template <int DEG>
+struct DefaultBlockBuilds {
+  static constexpr int D = BLK_DEFAULT, F = BLK_FUSE;
+  using list = BuildList<Bld<D | BLK_LATT>, Bld<D | F | BLK_LATT>, Bld<D>, Bld<D | F>, Bld<D | BLK_F32M | BLK_LATT>, Bld<D | BLK_F32M>, Bld<D | BLK_HELM>,
+                         Bld<D | F | BLK_HELM>, Bld<D | BLK_HANG>, Bld<D | F | BLK_HANG>>;
+};
+template <>
+struct DefaultBlockBuilds<4> {
+  static constexpr int D = BLK_DEFAULT, F = BLK_FUSE, LATC = BLK_LATT | BLK_CARRY;
+  using list = BuildList<Bld<D | LATC | BLK_NTM, true>, Bld<D | F | LATC | BLK_NTM, true>, Bld<D | LATC>, Bld<D | F | LATC>, Bld<D>, Bld<D | F>,
+#ifdef BP5_TIMING_BUILDS // variant 63: the rolling metric prefetch (BlockPass::ROLL) -- a measured loss (profiles/r4 d_*)
+                         Bld<D | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | F | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | BLK_LATT | BLK_ROLL, true>,
+                         Bld<D | F | BLK_LATT | BLK_ROLL, true>,
+#endif
+                         Bld<D | BLK_F32M | LATC>, Bld<D | BLK_F32M>, Bld<D | BLK_HELM>, Bld<D | F | BLK_HELM>, Bld<D | BLK_HANG | BLK_NTM, true>,
+                         Bld<D | F | BLK_HANG | BLK_NTM, true>, Bld<D | BLK_HANG>, Bld<D | F | BLK_HANG>, Bld<D | BLK_AFFINE>,
+                         Bld<BLK_SINGLE | BLK_SEQ | BLK_RUNS>, Bld<BLK_SINGLE | BLK_SEQ>>;
+};
+// Lattice indices, the face carry and non-temporal metric loads are OPTIONAL: they change the speed and no bit of the result.  A build serves a
+// request when everything else agrees and it has no optional feature that was not asked for; an optional feature asked for that the operator
+// class, the degree or the quadrature has no build with is thereby DROPPED, not refused (non-temporal loads under GLL quadrature, the carry
+// outside p = 4, lattice indices for the Helmholtz operator ...).  Everything else (operator class, fused dot products) is served or refused.
+constexpr int BLK_OPTIONAL = BLK_LATT | BLK_CARRY | BLK_NTM;
+constexpr bool build_serves(int m, bool gauss_only, int want, bool coll)
+{
+  return (m & ~BLK_OPTIONAL) == (want & ~BLK_OPTIONAL) && (m & BLK_OPTIONAL & ~want) == 0 && !(gauss_only && coll);
+}
+template <int DEG, int M, bool GAUSS_ONLY>
+inline bool launch_if_serves(Bld<M, GAUSS_ONLY>, int want, int *status, bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
   const bool coll = mf->quadrature == BP5_QUAD_GLL;
-  return LAUNCH_COLL(launch_apply_t, P, (4, LPC, 1, PF, BLK_AFFINE), mf->d_scalar_plane, src, dst, c0, c1);
+  if (!build_serves(M, GAUSS_ONLY, want, coll)) return false;
+  if constexpr (GAUSS_ONLY) *status = launch_block_t<DEG, false, block_lpc(DEG), M>(mf, call, coef, src, dst, call.overwrite);
+  else *status = LAUNCH_COLL(launch_block_t, DEG, (block_lpc(DEG), M), coef, src, dst, call.overwrite);
+  return true;
+}
+template <int DEG, typename... B>
+inline bool launch_first_that_serves(BuildList<B...>, int want, int *status, bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
+  return (launch_if_serves<DEG>(B{}, want, status, mf, call, coef, src, dst) || ...);
+}
+// Variant 56 of every operator class and degree (and three p = 4 siblings that differ in the request only: 48 never asks for lattice indices -- it
+// A/Bs the combine pass of the packed shape --, 49 takes the plan as one without packed indices, 63 adds the rolling prefetch): the block range,
+// the plan, what the handle and the solver ask for as a mask, then the first build of the degree's list that serves it.
+template <int DEG>
+inline int launch_block_default(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
+{
+  static_assert(block_lpc(DEG) != 0, "no block-kernel shape for this degree");
+  const int variant = call.variant % 100;
+  if (!block_aligned(mf, call.c0, call.c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
+  bp5_mf::DevPlan *dp = nullptr;
+  BP5_TRY(get_plan_raw(mf, -(256 / block_lpc(DEG)), &dp));
+  const int cls = // operator class (apply_degree_impl has refused the combinations of them, and returned on an empty range)
+      mf->f32_metric() ? BLK_F32M : mf->operator_kind == BP5_OP_HELMHOLTZ ? BLK_HELM : mf->has_hanging ? BLK_HANG : mf->geometry_mode == BP5_GEOM_AFFINE ? BLK_AFFINE : 0;
+  int want;
+  if (dp->packed && variant != 49) {
+    want = BLK_DEFAULT | cls | (call.fuse ? BLK_FUSE : 0);
+    if (dp->lattice && dp->n_lattice_blocks == dp->n_groups && variant != 48) want |= BLK_LATT | BLK_CARRY; // every block a lattice block: closed-form indices, no per-DoF index stream
+    if (streaming_accesses(mf)) want |= BLK_NTM;
+  } else { // more than 128 runs in some block: only the Poisson operator at p = 4 keeps kernels for such plans, none of them fused
+    if (DEG != 4 || cls != 0) return fail(BP5_ERR_UNSUPPORTED, "variant " + std::to_string(variant) + " needs packed indices (<= 128 runs per cell block)");
+    if (call.fuse) return fail(BP5_ERR_INVALID, "fused dot products need the packed block kernel");
+    want = dp->max_runs <= (uint32_t)BLOCK_MAX_RUNS ? BLK_SINGLE | BLK_SEQ | BLK_RUNS : BLK_SINGLE | BLK_SEQ; // write-out without list loads while the runs fit the LDS table
+  }
+#ifndef BP5_TIMING_BUILDS
+  if (variant == 63) return fail(BP5_ERR_INVALID, "variant 63 lives in libbp5_timing.so");
+#else
+  if (variant == 63) {
+    if (!(want & BLK_LATT) || mf->quadrature == BP5_QUAD_GLL) return fail(BP5_ERR_UNSUPPORTED, "variant 63 (rolling metric prefetch) needs lattice blocks and Gauss quadrature");
+    want = (want & ~BLK_CARRY) | BLK_ROLL;
+  }
+#endif
+  int status = BP5_OK;
+  if (!launch_first_that_serves<DEG>(typename DefaultBlockBuilds<DEG>::list{}, want, &status, mf, call, cls == BLK_AFFINE ? mf->d_scalar_plane : coef, src, dst))
+    return fail(BP5_ERR_UNSUPPORTED, "the block kernel has no build for this operator, plan and solver request");
+  return status;
 }
 
-// (degree, variant) -> kernel.  One instantiation per degree: only the cases of DEG are compiled into it.
+// ------------------------------------------------------------------------------------ (degree, variant) -> kernel
+// pencil variants: (degree, variant) -> (TW, LPC, TPB, PF); variant 0 is DefaultPencil
+#define APPLY_CASE(P, V, TW, LPC, TPB, PF) BP5_CASE(P, V) return LAUNCH_COLL(launch_apply_t, P, (TW, LPC, TPB, PF), coef, src, dst, c0, c1, overwrite)
+
+// The affine pencil kernel keeps a shape of its OWN, not DefaultPencil: one four-wave team per workgroup (TW = 4, TPB = 1) at every degree
+template <int P>
+inline int launch_affine(bp5_mf *mf, ApplyCall &call, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite)
+{
+  const bool coll = mf->quadrature == BP5_QUAD_GLL;
+  return LAUNCH_COLL(launch_apply_t, P, (4, (P + 1) * (P + 1), 1, true, BLK_AFFINE), mf->d_scalar_plane, src, dst, c0, c1, overwrite);
+}
+
+// One instantiation per degree: only the cases of DEG are compiled into it.
 #define BP5_CASE(P, V) if constexpr (DEG == (P)) if (variant == (V))
+#define LAUNCH_DEFAULT_PENCIL(ABL, COEF) LAUNCH_COLL(launch_apply_t, DEG, (DP::TW, DP::LPC, DP::TPB, DP::PF, ABL), COEF, src, dst, c0, c1, overwrite)
 template <int DEG>
 int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
 {
+  using DP = DefaultPencil<DEG>;
   const uint32_t c0 = call.c0, c1 = call.c1;
   const bool overwrite = call.overwrite;
   const bool coll = mf->quadrature == BP5_QUAD_GLL;
+  const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
+  if (c1 <= c0) return overwrite ? zero_dst(mf, dst) : BP5_OK; // the empty range, for every operator and variant
   if (mf->f32_metric()) {
     // FP32 metric planes (bp5_mf_set_metric_precision): the BLK_F32M builds of what the dispatch picks for an unfused application of the Poisson
-    // operator on six planes -- variant 56: the block kernel's default shape (packed indices; lattice blocks in closed form, with the face carry
-    // at p = 4), cell ranges and two-part launches included; variant 0: the degree's default pencil kernel.  Ordinary (not non-temporal) metric
-    // loads in every build: the results are the same bits either way
-    if (mf->operator_kind != BP5_OP_POISSON || mf->has_hanging || mf->geometry_mode != BP5_GEOM_MERGED6)
+    // operator on six planes -- variant 56: the default block kernel, cell ranges and two-part launches included; variant 0: the degree's default
+    // pencil kernel
+    if (mf->operator_kind != BP5_OP_POISSON || mf->has_hanging || affine)
       return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: Poisson operator on a conforming mesh with the six-plane geometry only");
     if (call.fuse) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: no fused dot products");
-    if (c1 <= c0) { if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); return BP5_OK; }
-    if (call.variant == 56) {
-      if constexpr (block_lpc(DEG) != 0) {
-        constexpr int LPCB = block_lpc(DEG);
-        if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
-        bp5_mf::DevPlan *dp_ = nullptr;
-        BP5_TRY(get_plan_raw(mf, -(256 / LPCB), &dp_));
-        if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: variant 56 needs packed indices (<= 128 runs per cell block)");
-        constexpr int LATF = DEG == 4 ? (BLK_LATT | BLK_CARRY) : BLK_LATT; // (the face carry exists at p = 4, as for double planes)
-        if (dp_->lattice && dp_->n_lattice_blocks == dp_->n_groups) return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | LATF | BLK_F32M), coef, src, dst, overwrite);
-        return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_F32M), coef, src, dst, overwrite);
-      }
-    }
+    if (call.variant == 56) return launch_block_default<DEG>(mf, call, coef, src, dst);
     if (call.variant != 0) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    constexpr int n2f = (DEG + 1) * (DEG + 1);
-    constexpr int TWF = DEG <= 3 ? 1 : 4, TPBF = DEG <= 3 ? 4 : 1; // the shapes of APPLY_CASE(P, 0, ...)
-    return LAUNCH_COLL(launch_apply_t, DEG, (TWF, n2f, TPBF, true, BLK_F32M), coef, src, dst, c0, c1);
+    return LAUNCH_DEFAULT_PENCIL(BLK_F32M, coef);
   }
   if (mf->operator_kind == BP5_OP_HELMHOLTZ) {
     // step-64's Helmholtz operator (step-64/step-64.cu:154-160,201-219) as a build of the same fused kernels: the degree's default pencil
     // shape (any mesh), or the deterministic block kernel on cell bricks (variant 56; with the CG dot products fused when the solver asks)
-    if (mf->has_hanging || mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs a conforming mesh and the six-plane geometry");
-    if (call.variant == 56) {
-      if constexpr (block_lpc(DEG) != 0) {
-        constexpr int LPCB = block_lpc(DEG);
-        if (c1 <= c0) { if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); return BP5_OK; }
-        if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
-        bp5_mf::DevPlan *dp_ = nullptr;
-        BP5_TRY(get_plan_raw(mf, -(256 / LPCB), &dp_));
-        if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 56 needs packed indices (<= 128 runs per cell block)");
-        if (call.fuse) return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_FUSE | BLK_HELM), coef, src, dst, overwrite);
-        return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_HELM), coef, src, dst, overwrite);
-      }
-    }
+    if (mf->has_hanging || affine) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs a conforming mesh and the six-plane geometry");
+    if (call.variant == 56) return launch_block_default<DEG>(mf, call, coef, src, dst);
 #ifdef BP5_TIMING_BUILDS
     // timing-only ablations of the Helmholtz block kernel at p = 3 (wrong results; profiles/r4 j_*): 91 no write-out (and no combine pass), 93 no plane loads, 95 no gather
     if constexpr (DEG == 3) if (call.variant == 91 || call.variant == 93 || call.variant == 95) {
@@ -703,149 +793,107 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
     }
 #endif
     if (call.variant != 0) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    if (c1 <= c0) return BP5_OK;
-    constexpr int n2e = (DEG + 1) * (DEG + 1);
-    constexpr int TWE = DEG <= 3 ? 1 : 4, TPBE = DEG <= 3 ? 4 : 1;
-    return LAUNCH_COLL(launch_apply_t, DEG, (TWE, n2e, TPBE, true, BLK_HELM), coef, src, dst, c0, c1);
+    return LAUNCH_DEFAULT_PENCIL(BLK_HELM, coef);
   }
   if (mf->has_hanging) {
     // 2:1 refined meshes (resolve_hanging_nodes, bp5/fe_evaluation_gl.h:150-151,167-168): the hanging-node fix-up after the gather and its
     // adjoint before the scatter.  Variant 56: the deterministic block kernel (cell blocks, packed indices; the CG dot products fused when
-    // the solver asks); variant 90: the degree's default pencil shape with atomics (any mesh; also the affine geometry mode)
-    if (call.variant == 56 && mf->geometry_mode != BP5_GEOM_AFFINE) {
-      if constexpr (block_lpc(DEG) != 0) {
-        constexpr int LPCB = block_lpc(DEG);
-        if (c1 <= c0) { if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); return BP5_OK; }
-        if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
-        bp5_mf::DevPlan *dp_ = nullptr;
-        BP5_TRY(get_plan_raw(mf, -(256 / LPCB), &dp_));
-        if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 56 needs packed indices (<= 128 runs per cell block)");
-        if constexpr (DEG == 4) if (!coll && streaming_accesses(mf)) { // streaming policy (non-temporal metric loads on small meshes), as for conforming meshes
-          if (call.fuse) return launch_block_t<4, false, LPCB, BLK_DEFAULT | BLK_FUSE | BLK_HANG | BLK_NTM>(mf, call, coef, src, dst, overwrite);
-          return launch_block_t<4, false, LPCB, BLK_DEFAULT | BLK_HANG | BLK_NTM>(mf, call, coef, src, dst, overwrite);
-        }
-        if (call.fuse) return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_FUSE | BLK_HANG), coef, src, dst, overwrite);
-        return LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_HANG), coef, src, dst, overwrite);
-      }
-    }
+    // the solver asks); variant 90: the degree's default pencil shape with atomics (any mesh; also the affine geometry mode: all cells affine on
+    // undeformed 2:1 meshes, per-cell K K^T + one scalar plane)
+    if (call.variant == 56 && !affine) return launch_block_default<DEG>(mf, call, coef, src, dst);
     if (call.variant != 90) return fail(BP5_ERR_UNSUPPORTED, "meshes with hanging nodes run apply variants 90 (pencil kernel) and 56 (block kernel)");
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    if (c1 <= c0) return BP5_OK;
-    constexpr int n2h = (DEG + 1) * (DEG + 1);
-    constexpr int TWH = DEG <= 3 ? 1 : 4, TPBH = DEG <= 3 ? 4 : 1;
-    if (mf->geometry_mode == BP5_GEOM_AFFINE) // all cells affine (undeformed 2:1 meshes): per-cell K K^T + one scalar plane
-      return LAUNCH_COLL(launch_apply_t, DEG, (TWH, n2h, TPBH, true, BLK_HANG | BLK_AFFINE), mf->d_scalar_plane, src, dst, c0, c1);
-    return LAUNCH_COLL(launch_apply_t, DEG, (TWH, n2h, TPBH, true, BLK_HANG), coef, src, dst, c0, c1);
+    if (affine) return LAUNCH_DEFAULT_PENCIL(BLK_HANG | BLK_AFFINE, mf->d_scalar_plane);
+    return LAUNCH_DEFAULT_PENCIL(BLK_HANG, coef);
   }
-  if (mf->geometry_mode == BP5_GEOM_AFFINE && c1 > c0) {
+  if (affine) { // per-cell K K^T + one scalar plane: the affine pencil kernel, whatever the variant; p = 4 also has team and block builds
     const bool whole = c0 == 0 && c1 == mf->n_cells;
     if constexpr (DEG == 4) {
     if (call.variant % 100 == 10) return LAUNCH_COLL(launch_team_t, 4, (4, 25, true, BLK_AFFINE), mf->d_scalar_plane, src, dst, c0, c1, overwrite);
-    if (call.variant == 56) { // the default block-kernel shape on the scalar plane + per-cell K K^T
-      if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
-      return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite);
-    }
-    if (whole && (call.variant == 54 || call.variant == 55)) // (brick-surface DoFs by atomics: ApplyCall::shared_by_atomics)
-      return call.variant == 54 ? LAUNCH_COLL(launch_block_t, 4, (32, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite)
-                                : LAUNCH_COLL(launch_block_t, 4, (25, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite);
-    if (whole && (call.variant == 50 || call.variant == 51))
-      return call.variant == 50 ? LAUNCH_COLL(launch_block_t, 4, (25, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite)
-                                : LAUNCH_COLL(launch_block_t, 4, (32, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite);
+    if (call.variant == 56) return launch_block_default<4>(mf, call, coef, src, dst);
+    // 50 / 51: 25 / 32 lanes per cell; 55 / 54: the same with the brick-surface DoFs by atomics (ApplyCall::shared_by_atomics)
+    if (whole && (call.variant == 51 || call.variant == 54)) return LAUNCH_COLL(launch_block_t, 4, (32, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite);
+    if (whole && (call.variant == 50 || call.variant == 55)) return LAUNCH_COLL(launch_block_t, 4, (25, BLK_AFFINE), mf->d_scalar_plane, src, dst, overwrite);
 #ifdef BP5_TIMING_BUILDS
     if (call.variant == 85) // timing only: affine, no scatter atomics -> compute/latency floor of the pencil kernel
-      return launch_apply_t<4, false, 4, 25, 1, true, 1025>(mf, call, mf->d_scalar_plane, src, dst, c0, c1);
+      return launch_apply_t<4, false, 4, 25, 1, true, 1025>(mf, call, mf->d_scalar_plane, src, dst, c0, c1, false);
 #endif
     }
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    return launch_affine<DEG>(mf, call, src, dst, c0, c1);
-  }
-  if (c1 <= c0) {
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    return BP5_OK;
+    return launch_affine<DEG>(mf, call, src, dst, c0, c1, overwrite);
   }
   // variants >= 100: the team kernel of (variant - 100) with the global-atomic scatter (A/B tests)
   int variant = call.variant % 100;
-  // cell-interior DoFs numbered ahead of all others (recognised by bp5_mf_create): the default pencil kernel of p >= 5 stores the entries a cell owns alone
-  // plainly -- (p-1)^3 of (p+1)^3 atomics less per cell (47 % at p = 8), and no store ever meets an atomic in one cache line
-  if constexpr (DEG >= 5) if (variant == 0 && !call.atomic_scatter && mf->cell_interiors_first && mf->tune[BP5_TUNE_INTERIOR_STORES]) {
-    if (overwrite) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
-    return LAUNCH_COLL(launch_apply_t, DEG, (4, (DEG + 1) * (DEG + 1), 1, true, 32), coef, src, dst, c0, c1);
+  if (variant == 0) {
+    // cell-interior DoFs numbered ahead of all others (recognised by bp5_mf_create): the default pencil kernel of p >= 5 stores the entries a cell owns alone
+    // plainly -- (p-1)^3 of (p+1)^3 atomics less per cell (47 % at p = 8), and no store ever meets an atomic in one cache line
+    if constexpr (DEG >= 5) if (!call.atomic_scatter && mf->cell_interiors_first && mf->tune[BP5_TUNE_INTERIOR_STORES])
+      return LAUNCH_DEFAULT_PENCIL(PEN_INTERIOR_STORES, coef);
+    return LAUNCH_DEFAULT_PENCIL(0, coef);
   }
+  if (variant == 56) return launch_block_default<DEG>(mf, call, coef, src, dst);
   {
-    APPLY_CASE(1, 0, 1, 4, 4, true);
     APPLY_CASE(1, 1, 1, 4, 4, true);
-    APPLY_CASE(2, 0, 1, 9, 4, true);
-    APPLY_CASE(3, 0, 1, 16, 4, true);
     APPLY_CASE(3, 1, 1, 16, 4, true);
-    APPLY_CASE(4, 0, 4, 25, 1, true);
     APPLY_CASE(4, 6, 1, 25, 4, true);
     APPLY_CASE(4, 1, 1, 32, 4, true);
     APPLY_CASE(4, 2, 2, 25, 1, true);
     APPLY_CASE(4, 3, 4, 25, 1, true);
     APPLY_CASE(4, 4, 1, 25, 1, true);
     APPLY_CASE(4, 5, 1, 25, 4, false);
-    APPLY_CASE(5, 0, 4, 36, 1, true);
     APPLY_CASE(5, 1, 1, 36, 4, true);
     APPLY_CASE(5, 2, 4, 36, 1, false);
     APPLY_CASE(5, 3, 2, 36, 1, true);
-    APPLY_CASE(6, 0, 4, 49, 1, true);   // defaults for p >= 6 from the high-degree sweep: prefetch all planes
-    APPLY_CASE(6, 5, 4, 49, 1, false);
+    APPLY_CASE(6, 5, 4, 49, 1, false);   // (the defaults for p >= 6 prefetch all planes: the high-degree sweep)
     APPLY_CASE(6, 1, 1, 49, 4, false);
     APPLY_CASE(6, 2, 4, 49, 1, true);
     APPLY_CASE(6, 3, 1, 49, 1, true);
     APPLY_CASE(6, 4, 2, 49, 1, false);
-    APPLY_CASE(7, 0, 4, 64, 1, true);
     APPLY_CASE(7, 5, 1, 64, 4, false);
     APPLY_CASE(7, 1, 4, 64, 1, false);
     APPLY_CASE(7, 2, 4, 64, 1, true);
     APPLY_CASE(7, 3, 1, 64, 1, true);
-    APPLY_CASE(8, 0, 4, 81, 1, true);
     APPLY_CASE(8, 5, 4, 81, 1, false);
     APPLY_CASE(8, 1, 2, 81, 1, false);
     APPLY_CASE(8, 2, 4, 81, 1, true);
     APPLY_CASE(8, 3, 2, 81, 1, true);
 #ifdef BP5_TIMING_BUILDS
     // timing-only ablations of variant 3 (results are wrong by construction): 20 + ABL mask
-#define ABL_CASE(M) BP5_CASE(4, 20 + (M)) return launch_apply_t<4, false, 4, 25, 1, true, M>(mf, call, coef, src, dst, c0, c1)
-#define ABL_CASE_HI(P, L, M) BP5_CASE(P, 20 + (M)) return launch_apply_t<P, false, 4, L, 1, true, M>(mf, call, coef, src, dst, c0, c1)
+#define ABL_CASE(M) BP5_CASE(4, 20 + (M)) return launch_apply_t<4, false, 4, 25, 1, true, M>(mf, call, coef, src, dst, c0, c1, false)
+#define ABL_CASE_HI(P, L, M) BP5_CASE(P, 20 + (M)) return launch_apply_t<P, false, 4, L, 1, true, M>(mf, call, coef, src, dst, c0, c1, false)
     ABL_CASE_HI(8, 81, 1); ABL_CASE_HI(8, 81, 2); ABL_CASE_HI(8, 81, 4); ABL_CASE_HI(8, 81, 8); ABL_CASE_HI(8, 81, 9); ABL_CASE_HI(8, 81, 11);
     ABL_CASE_HI(6, 49, 1); ABL_CASE_HI(6, 49, 2); ABL_CASE_HI(6, 49, 8); ABL_CASE_HI(6, 49, 9);
-    BP5_CASE(4, 7) return LAUNCH_COLL(launch_apply_t, 4, (4, 25, 1, true, 256), coef, src, dst, c0, c1);
-    BP5_CASE(4, 8) return LAUNCH_COLL(launch_apply_t, 4, (4, 25, 1, true, 512), coef, src, dst, c0, c1);
-    BP5_CASE(4, 9) return LAUNCH_COLL(launch_apply_t, 4, (2, 25, 1, true, 512), coef, src, dst, c0, c1);
-    BP5_CASE(4, 82) return launch_apply_t<4, false, 4, 25, 1, true, 257>(mf, call, coef, src, dst, c0, c1);
-    BP5_CASE(4, 83) return launch_apply_t<4, false, 4, 25, 1, true, 4096>(mf, call, coef, src, dst, c0, c1);
-    BP5_CASE(4, 84) return launch_apply_t<4, false, 4, 25, 1, true, 8192>(mf, call, coef, src, dst, c0, c1);
-    BP5_CASE(4, 80) return launch_apply_t<4, false, 4, 25, 1, true, 64>(mf, call, coef, src, dst, c0, c1);
+    BP5_CASE(4, 7) return LAUNCH_COLL(launch_apply_t, 4, (4, 25, 1, true, 256), coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 8) return LAUNCH_COLL(launch_apply_t, 4, (4, 25, 1, true, 512), coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 9) return LAUNCH_COLL(launch_apply_t, 4, (2, 25, 1, true, 512), coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 82) return launch_apply_t<4, false, 4, 25, 1, true, 257>(mf, call, coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 83) return launch_apply_t<4, false, 4, 25, 1, true, 4096>(mf, call, coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 84) return launch_apply_t<4, false, 4, 25, 1, true, 8192>(mf, call, coef, src, dst, c0, c1, false);
+    BP5_CASE(4, 80) return launch_apply_t<4, false, 4, 25, 1, true, 64>(mf, call, coef, src, dst, c0, c1, false);
     BP5_CASE(4, 81) { // E-vector stores need a big scratch target
       if (!mf->d_evec) HIP_TRY(hipMalloc((void **)&mf->d_evec, (size_t)mf->n_cells * mf->n3 * sizeof(double)));
-      return launch_apply_t<4, false, 4, 25, 1, true, 128>(mf, call, coef, src, mf->d_evec, c0, c1); }
+      return launch_apply_t<4, false, 4, 25, 1, true, 128>(mf, call, coef, src, mf->d_evec, c0, c1, false); }
     BP5_CASE(4, 90) {
       if (!mf->d_evec) HIP_TRY(hipMalloc((void **)&mf->d_evec, ((size_t)mf->n_cells * mf->n3 + 4096 * 5) * sizeof(double) * 2));
-      return launch_apply_t<4, false, 4, 25, 1, true, 262144>(mf, call, coef, src, mf->d_evec, c0, c1); }
+      return launch_apply_t<4, false, 4, 25, 1, true, 262144>(mf, call, coef, src, mf->d_evec, c0, c1, false); }
     BP5_CASE(4, 88) {
       if (!mf->d_evec) HIP_TRY(hipMalloc((void **)&mf->d_evec, (size_t)mf->n_cells * mf->n3 * sizeof(double)));
-      return launch_apply_t<4, false, 4, 25, 1, true, 128 + 65536>(mf, call, coef, src, mf->d_evec, c0, c1); }
+      return launch_apply_t<4, false, 4, 25, 1, true, 128 + 65536>(mf, call, coef, src, mf->d_evec, c0, c1, false); }
     BP5_CASE(4, 89) {
       if (!mf->d_evec) HIP_TRY(hipMalloc((void **)&mf->d_evec, (size_t)mf->n_cells * mf->n3 * sizeof(double)));
-      return launch_apply_t<4, false, 4, 25, 1, true, 1 + 131072>(mf, call, coef, src, mf->d_evec, c0, c1); }
+      return launch_apply_t<4, false, 4, 25, 1, true, 1 + 131072>(mf, call, coef, src, mf->d_evec, c0, c1, false); }
     BP5_CASE(4, 86) {
       if (!mf->d_evec) HIP_TRY(hipMalloc((void **)&mf->d_evec, (size_t)mf->n_cells * mf->n3 * sizeof(double)));
-      return launch_apply_t<4, false, 4, 25, 1, true, 128 + 16384>(mf, call, coef, src, mf->d_evec, c0, c1); }
+      return launch_apply_t<4, false, 4, 25, 1, true, 128 + 16384>(mf, call, coef, src, mf->d_evec, c0, c1, false); }
     ABL_CASE(1); ABL_CASE(2); ABL_CASE(3); ABL_CASE(4); ABL_CASE(5); ABL_CASE(7); ABL_CASE(8); ABL_CASE(9); ABL_CASE(15); ABL_CASE(14); ABL_CASE(13); ABL_CASE(11);
 #endif
-    // z-marching kernel, variants 70+ (atomic scatter: dst must be zero-filled like for the pencil kernel)
+    // z-marching kernel, variants 70+ (a partial cell range takes the pencil kernel of the same shape)
 #define MARCH_CASE(P, V, TW, LPC, PF)                                                                              \
   BP5_CASE(P, V) {                                                                                                 \
-    if (overwrite && hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream) != hipSuccess)             \
-      return fail(BP5_ERR_HIP, "hipMemsetAsync");                                                                  \
     if (c0 != 0 || c1 != mf->n_cells)                                                                              \
-      return LAUNCH_COLL(launch_apply_t, P, (TW, LPC, 1, PF), coef, src, dst, c0, c1);                              \
-    return LAUNCH_COLL(launch_march_t, P, (TW, LPC, PF), coef, src, dst); \
+      return LAUNCH_COLL(launch_apply_t, P, (TW, LPC, 1, PF), coef, src, dst, c0, c1, overwrite);                   \
+    return LAUNCH_COLL(launch_march_t, P, (TW, LPC, PF), coef, src, dst, overwrite);                                \
   }
 #ifdef BP5_TIMING_BUILDS
-    BP5_CASE(4, 73) return launch_march_t<4, false, 4, 25, true, 1>(mf, call, coef, src, dst); // timing only: march, no scatter
+    BP5_CASE(4, 73) return launch_march_t<4, false, 4, 25, true, 1>(mf, call, coef, src, dst, false); // timing only: march, no scatter
 #endif
     MARCH_CASE(1, 70, 4, 4, true);
     MARCH_CASE(2, 70, 4, 9, true);
@@ -875,8 +923,6 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
         return variant == 54 ? LAUNCH_COLL(launch_block_t, 4, (32), coef, src, dst, overwrite) : LAUNCH_COLL(launch_block_t, 4, (25), coef, src, dst, overwrite);
       return LAUNCH_COLL(launch_team_t, 4, (4, 25, true), coef, src, dst, c0, c1, overwrite);
     }
-    // 56 on the other degrees with a wave-local cell shape (p = 2, 3, 5, 6, 7): sequential tiles, run-length write-out, packed
-    // indices; p >= 5 keep two workgroups per CU (registers), fused CG dot products when the solver asks for them
 #ifdef BP5_TIMING_BUILDS
     if constexpr (DEG == 6 || DEG == 8 || DEG == 5) if (variant == 99 || variant == 91 || variant == 93) { // cycle stamps / no write-out / no metric loads
       constexpr int LPCB = block_lpc(DEG);
@@ -886,69 +932,20 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
       return launch_block_t<DEG, false, LPCB, BLK_DEFAULT | 2>(mf, call, coef, src, dst, true);
     }
 #endif
-    if constexpr (DEG != 4 && block_lpc(DEG) != 0) if (variant == 56) {
-      constexpr int LPCB = block_lpc(DEG);
-      if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
-      bp5_mf::DevPlan *dp_ = nullptr;
-      BP5_TRY(get_plan_raw(mf, -(256 / LPCB), &dp_));
-      if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 56 needs packed indices (<= 128 runs per cell block) at this degree");
-      const bool lattice = dp_->lattice && dp_->n_lattice_blocks == dp_->n_groups; // every block a lattice block: closed-form indices, no per-DoF index stream
-      if (call.fuse) return lattice ? LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_FUSE | BLK_LATT), coef, src, dst, overwrite)
-                                    : LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_FUSE), coef, src, dst, overwrite);
-      return lattice ? LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT | BLK_LATT), coef, src, dst, overwrite)
-                     : LAUNCH_COLL(launch_block_t, DEG, (LPCB, BLK_DEFAULT), coef, src, dst, overwrite);
-    }
-    // 48 = 56 with the per-DoF CSR combine kernel instead of the run-length one (A/B)
-    // 49 = 56 with run-length write-out but without packed indices (A/B)
-    // 60 = 56 with the brick's src staged once in LDS (cells gather from LDS; needs the packed indices)
-    // 61 = 56 with non-temporal metric loads (A/B: the once-read metric stream then evicts less of a brick's src from L2)
-    // 62 = 56 with ds_add_f64 for the accumulation into the LDS vector (A/B)
+    // p = 4 A/B siblings of 56.  Three differ in the request only and go through launch_block_default:
+    // 48 = 56 with the per-DoF CSR combine kernel instead of the run-length one
+    // 49 = 56 with run-length write-out but without packed indices
     // 63 = 56 with the rolling metric prefetch (BlockPass::ROLL; lattice blocks only) -- libbp5_timing.so only: a measured loss (profiles/r4 d_*)
-    if constexpr (DEG == 4) if (variant == 48 || variant == 49 || variant == 56 || variant == 60 || variant == 61 || variant == 62 || variant == 63) { if (block_aligned(mf, c0, c1, &call.b0, &call.b1)) {
-        bp5_mf::DevPlan *dp_ = nullptr;
-        BP5_TRY(get_plan_raw(mf, -8, &dp_)); // p = 4: 32 lanes per cell, 8 cells per pass
-        if (variant == 60) {
-          if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 60 needs packed indices (<= 128 runs per cell block)");
-          return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_STAGE), coef, src, dst, overwrite);
-        }
-        if (variant == 62) {
-          if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 62 needs packed indices (<= 128 runs per cell block)");
-          return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_LDSADD), coef, src, dst, overwrite);
-        }
-        if (variant == 61) {
-          if (!dp_->packed) return fail(BP5_ERR_UNSUPPORTED, "variant 61 needs packed indices (<= 128 runs per cell block)");
-          return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_NTM), coef, src, dst, overwrite);
-        }
-        // BLK_LATT: every block a lattice block -- closed-form indices, no per-DoF index stream; LATC: ... with the face carry compiled in (BP5_TUNE_FACE_CARRY switches it per launch)
-        constexpr int LATC = BLK_LATT | BLK_CARRY;
-        const bool lattice = (variant == 56 || variant == 63) && dp_->packed && dp_->lattice && dp_->n_lattice_blocks == dp_->n_groups;
-        const bool ntm = streaming_accesses(mf); // non-temporal metric loads
-#ifndef BP5_TIMING_BUILDS
-        if (variant == 63) return fail(BP5_ERR_INVALID, "variant 63 lives in libbp5_timing.so");
-#else
-        if (variant == 63) {
-          if (!lattice || coll) return fail(BP5_ERR_UNSUPPORTED, "variant 63 (rolling metric prefetch) needs lattice blocks and Gauss quadrature");
-          if (call.fuse) return ntm ? launch_block_t<4, false, 32, BLK_DEFAULT | BLK_FUSE | BLK_LATT | BLK_NTM | BLK_ROLL>(mf, call, coef, src, dst, overwrite)
-                                      : launch_block_t<4, false, 32, BLK_DEFAULT | BLK_FUSE | BLK_LATT | BLK_ROLL>(mf, call, coef, src, dst, overwrite);
-          return ntm ? launch_block_t<4, false, 32, BLK_DEFAULT | BLK_LATT | BLK_NTM | BLK_ROLL>(mf, call, coef, src, dst, overwrite)
-                     : launch_block_t<4, false, 32, BLK_DEFAULT | BLK_LATT | BLK_ROLL>(mf, call, coef, src, dst, overwrite);
-        }
-#endif
-        if (call.fuse) { // the solver asked for the fused dot products (only ever with the packed default shape)
-          if (!dp_->packed || variant != 56) return fail(BP5_ERR_INVALID, "fused dot products need the packed block kernel");
-          if (lattice && ntm && !coll) return launch_block_t<4, false, 32, BLK_DEFAULT | BLK_FUSE | LATC | BLK_NTM>(mf, call, coef, src, dst, overwrite);
-          return lattice ? LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_FUSE | LATC), coef, src, dst, overwrite)
-                         : LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_FUSE), coef, src, dst, overwrite);
-        }
-        if (lattice && ntm && !coll) return launch_block_t<4, false, 32, BLK_DEFAULT | LATC | BLK_NTM>(mf, call, coef, src, dst, overwrite);
-        if (lattice) return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | LATC), coef, src, dst, overwrite);
-        if (dp_->packed && variant != 49) // few long runs (block-major numbering): one packed u16 per cell-local DoF, no local_to_global stream
-          return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT), coef, src, dst, overwrite);
-        if (dp_->max_runs <= (uint32_t)BLOCK_MAX_RUNS) // write-out without list loads
-          return LAUNCH_COLL(launch_block_t, 4, (32, BLK_SINGLE | BLK_SEQ | BLK_RUNS), coef, src, dst, overwrite);
-        return LAUNCH_COLL(launch_block_t, 4, (32, BLK_SINGLE | BLK_SEQ), coef, src, dst, overwrite);
-      }
-      return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
+    if constexpr (DEG == 4) if (variant == 48 || variant == 49 || variant == 63) return launch_block_default<4>(mf, call, coef, src, dst);
+    // ... three are builds of their own on the packed shape:
+    // 60 = 56 with the brick's src staged once in LDS (cells gather from LDS)
+    // 61 = 56 with non-temporal metric loads on packed indices (A/B: the once-read metric stream then evicts less of a brick's src from L2)
+    // 62 = 56 with ds_add_f64 for the accumulation into the LDS vector
+    if constexpr (DEG == 4) if (variant == 60 || variant == 61 || variant == 62) {
+      if (!block_aligned(mf, c0, c1, &call.b0, &call.b1)) return fail(BP5_ERR_INVALID, "variant 56 needs a cell range aligned with the cell blocks");
+      if (variant == 60) return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_STAGE), coef, src, dst, overwrite);
+      if (variant == 61) return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_NTM), coef, src, dst, overwrite);
+      return LAUNCH_COLL(launch_block_t, 4, (32, BLK_DEFAULT | BLK_LDSADD), coef, src, dst, overwrite);
     }
     BP5_CASE(4, 59) { if (c0 == 0 && c1 == mf->n_cells) return LAUNCH_COLL(launch_block_t, 4, (32, BLK_SINGLE | BLK_SEQ), coef, src, dst, overwrite);
       return fail(BP5_ERR_INVALID, "variant 59 needs the whole cell range"); }
@@ -988,7 +985,7 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
   BP5_CASE(4, 40 + (M)) {                                                                                         \
     TeamPlan tp; bp5_mf::DevPlan *dp = nullptr;                                                                    \
     BP5_TRY(get_plan(mf, 10, tp, &dp));                                                                            \
-    ApplyArgs a; a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst; a.plane_stride = mf->coef_plane_stride; a.cell_stride = mf->coef_cell_stride; \
+    ApplyArgs a = apply_args(mf, false, coef, src, dst);                                                           \
     a.cell_begin = c0; a.cell_end = c1; a.n_teams = (c1 + 9) / 10 - c0 / 10; a.teams_per_xcd = (a.n_teams + 7) / 8;  \
     ShapeArg<5> sh; fill_shape(sh, mf);                  \
     hipLaunchKernelGGL((apply_team_kernel<4, false, 4, 25, true, SC_OWNER_SET, M>), dim3(a.teams_per_xcd * 8), dim3(256), \

@@ -33,6 +33,29 @@ struct ShapeArg { // passed by value as a kernel argument: uniform -> scalar loa
   double D[n * n];
 };
 
+// ------------------------------------------------------------------------------------ build bits
+// The fused operator kernels are templates over a mask of build bits (ABL; OPT in the team kernel).  The dispatch (bp5_device.hpp) composes a
+// mask from these names, the kernels test them by name, and the mask is printed as a number into the kernel name a solve reports.
+// Block kernel (BlockPass / apply_block_kernel; what each bit selects is described at the BlockPass member of the same name).  The pencil, march and
+// team kernels read the AFFINE, HANG, HELM and F32M bits of their own mask with the same meaning.  Bits below 1024 (and a few probes above, spelled as
+// numbers where they are used) are timing-only ablations: no write-out, no metric loads, no gather ...
+enum : int {
+  BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_PACK = 262144,
+  BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
+  BLK_ROLL = 67108864, BLK_CARRY = 268435456,
+  BLK_F32M = 536870912, // the metric planes are float (bp5_mf_set_metric_precision)
+  // the default shape: metric loaded in its own pass, sequential tiles, run-length write-out, packed indices
+  BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK
+};
+// Pencil kernel (and the march kernel, which shares its metric loads): the same VALUES mean other things in the block kernel
+enum : int {
+  PEN_INTERIOR_STORES = 32,  // plain stores for the entries a cell owns alone (cell-interior DoFs numbered first, p >= 5)
+  PEN_NT_LOADS = 256,        // non-temporal loads of local_to_global and the metric planes
+  PEN_FULL_OCCUPANCY = 512   // launch bounds ask for every wave slot the workgroup shape allows
+};
+// Team kernel
+enum : int { TEAM_DIRECT_GATHER = 32 }; // gather through local_to_global instead of the LDS-staged team vector
+
 // ---------------------------------------------------------------------------------- device layout of per-q-point data
 // A cell's n^3 values of one plane (merged metric, affine scalar plane) are consumed in the orientation where lane
 // ab = qj + n qk owns the x-pencil qi = 0..n-1.  "Pair layout": the pencil values are stored as pairs (qi, qi+1), lane
@@ -77,8 +100,6 @@ __device__ __forceinline__ void load_pencil(const float *base, int ab, float (&S
   }
   if constexpr (n & 1) S[n - 1] = NT ? __builtin_nontemporal_load(base + (n / 2) * (2 * n * n) + ab) : base[(n / 2) * (2 * n * n) + ab];
 }
-// build bit of the fused operator kernels (pencil and block kernel; the ABL template argument): the metric planes are float
-constexpr int BLK_F32M = 536870912;
 template <int ABL> using metric_t = typename std::conditional<(ABL & BLK_F32M) != 0, float, double>::type;
 
 // pieces of load_pencil: pair m (qi = 2m, 2m + 1) and the unpaired last qi of an odd n -- the rolling metric prefetch of the block kernel
@@ -109,7 +130,7 @@ struct ApplyArgs {
   uint32_t teams_per_xcd;
   const double *gcell;   // affine mode: [6][n_cells] per-cell K K^T (planes 00,11,22,01,02,12); coef = 1 scalar plane
   uint32_t n_cells_total;
-  // hanging nodes (builds with ABL & 2097152): per-cell constraint mask (bp5.h BP5_HANG_*) and the two 1-D interpolation
+  // hanging nodes (builds with ABL & BLK_HANG): per-cell constraint mask (bp5.h BP5_HANG_*) and the two 1-D interpolation
   // matrices I[h][a][b] = phi_b(xi_a / 2 + h / 2)
   const uint32_t *hang_mask;
   const double *hang_I;
@@ -319,7 +340,7 @@ __device__ __forceinline__ void pencil_hang_resolve(uint32_t m, const double *__
 // metric loads, bit2 skip the src gather, bit3 skip the contractions
 // ABL bit 512: ask the compiler for 4 waves per SIMD (<= 128 VGPRs)
 template <int P, bool COLL, int TW, int LPC, int TPB, bool PF, int ABL = 0>
-__global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) apply_pencil_kernel(ApplyArgs a, ShapeArg<P + 1> sh)
+__global__ void __launch_bounds__(64 * TW * TPB, (ABL & PEN_FULL_OCCUPANCY) ? (TW * TPB) : 1) apply_pencil_kernel(ApplyArgs a, ShapeArg<P + 1> sh)
 {
   constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
   constexpr int TEAM = 64 * TW;
@@ -352,11 +373,11 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
   double u[n];
   const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
 #pragma unroll
-  for (int k = 0; k < n; ++k) idx[k] = (ABL & 256) ? __builtin_nontemporal_load(l2g_c + k * n2) : l2g_c[k * n2];
+  for (int k = 0; k < n; ++k) idx[k] = (ABL & PEN_NT_LOADS) ? __builtin_nontemporal_load(l2g_c + k * n2) : l2g_c[k * n2];
 #pragma unroll
   for (int k = 0; k < n; ++k) u[k] = (ABL & 4) ? 1e-9 * idx[k] : a.src[idx[k]];
   uint32_t hmask = 0;
-  if constexpr ((ABL & 2097152) != 0) { // hanging nodes: coarse-face values -> this cell's own face nodes
+  if constexpr ((ABL & BLK_HANG) != 0) { // hanging nodes: coarse-face values -> this cell's own face nodes
     hmask = a.hang_mask[cell];
     pencil_hang_resolve<n, TW, false, L>(hmask, a.hang_I, u, T, a_, b_, active);
   }
@@ -370,11 +391,11 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
   // ---- metric planes (x-owner: a_ = j, b_ = k; registers hold i), layout [c][cell][i][j+n k]
   using MT = metric_t<ABL>; // plane entries: double, or float on an FP32-metric handle (BLK_F32M)
   const MT *cf = reinterpret_cast<const MT *>(a.coef) + cell * a.cell_stride; // cell base; lane offsets through coef_off / load_pencil
-  constexpr bool AFFINE = (ABL & 1024) != 0; // affine geometry: one scalar plane + six per-cell numbers
+  constexpr bool AFFINE = (ABL & BLK_AFFINE) != 0; // affine geometry: one scalar plane + six per-cell numbers
   // HELM: step-64's Helmholtz operator (grad v, grad u) + (v, a u) (step-64/step-64.cu:154-160,201-219): evaluate(true, true) /
   // integrate(true, true) cost ONE more 1-D contraction each way (the value path shares the y- and z-contractions with the x-derivative),
   // submit_value(a * get_value()) one more plane: a(x_q) JxW behind the six merged planes
-  constexpr bool HELM = (ABL & 8388608) != 0;
+  constexpr bool HELM = (ABL & BLK_HELM) != 0;
   static_assert(!HELM || (PF && !AFFINE), "Helmholtz build: prefetched planes, six-plane geometry");
   static_assert((ABL & BLK_F32M) == 0 || (!HELM && !AFFINE), "FP32 metric planes: Poisson operator, six-plane geometry");
   constexpr int NPL = HELM ? 7 : 6;
@@ -392,7 +413,7 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
 #pragma unroll
         for (int i = 0; i < n; ++i) S[pl][i] = 1.0 + pl + i + 1e-3 * abm;
       } else
-        load_pencil<n, (ABL & 256) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
+        load_pencil<n, (ABL & PEN_NT_LOADS) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
     }
   }
 
@@ -559,7 +580,7 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
     MV_DT_ADD(sh.D, z2, y);
   }
 
-  if constexpr ((ABL & 2097152) != 0) pencil_hang_resolve<n, TW, true, L>(hmask, a.hang_I, y, T, a_, b_, active); // adjoint, before the scatter
+  if constexpr ((ABL & BLK_HANG) != 0) pencil_hang_resolve<n, TW, true, L>(hmask, a.hang_I, y, T, a_, b_, active); // adjoint, before the scatter
   // ---- scatter-add (distribute_local_to_global, bp5/fe_evaluation_gl.h:170-180)
   if constexpr (ABL & 1) {
     double acc = 0.0;
@@ -597,7 +618,7 @@ __global__ void __launch_bounds__(64 * TW * TPB, (ABL & 512) ? (TW * TPB) : 1) a
         else a.dst[cell * n3 + k * n2 + abm] = y[k];
       }
     }
-  } else if constexpr ((ABL & 32) != 0) {
+  } else if constexpr ((ABL & PEN_INTERIOR_STORES) != 0) {
     // Cell-interior entries (1 <= i, j, k <= n - 2: (n - 2)^3 of n^3, 47 % at p = 8) belong to this cell alone: a plain store instead of a memory-side
     // atomic -- the kernel is bound by the COUNT of its atomics.  Correct on any mesh; it pays only where these DoFs do not share cache
     // lines with atomically updated ones ("an atomic to a line that is dirty in L2 forces its write-back": stores mixed into such lines cost 21 % at p = 4),
@@ -694,7 +715,7 @@ __global__ void __launch_bounds__(64 * TW) apply_march_kernel(ApplyArgs a, March
 
     // ---- metric planes (x-owner: a_ = j, b_ = k; registers hold i), layout [c][cell][i][j+n k]
     const double *cf = a.coef + cell * a.cell_stride; // cell base; lane offsets through coef_off / load_pencil
-    constexpr bool AFFINE = (ABL & 1024) != 0; // affine geometry: one scalar plane + six per-cell numbers
+    constexpr bool AFFINE = (ABL & BLK_AFFINE) != 0; // affine geometry: one scalar plane + six per-cell numbers
     double S[(PF && !AFFINE) ? 6 : 1][n];
     double Gc[6] = {0, 0, 0, 0, 0, 0};
     if constexpr (AFFINE) {
@@ -708,7 +729,7 @@ __global__ void __launch_bounds__(64 * TW) apply_march_kernel(ApplyArgs a, March
 #pragma unroll
           for (int i = 0; i < n; ++i) S[pl][i] = 1.0 + pl + i + 1e-3 * abm;
         } else
-          load_pencil<n, (ABL & 256) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
+          load_pencil<n, (ABL & PEN_NT_LOADS) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
       }
     }
 
@@ -962,7 +983,7 @@ __global__ void __launch_bounds__(64 * TW) apply_team_kernel(ApplyArgs a, TeamPl
   const int n_rounds = tp.team_rounds[team];
   // ---- metric planes (issued early; consumed after the evaluate phase)
   const double *cf = a.coef + cell * a.cell_stride; // cell base; lane offsets through coef_off / load_pencil
-  constexpr bool AFFINE = (ABL & 1024) != 0;
+  constexpr bool AFFINE = (ABL & BLK_AFFINE) != 0;
   double S[(PF && !AFFINE) ? 6 : 1][n];
   double Gc[6] = {0, 0, 0, 0, 0, 0};
   if constexpr (AFFINE) {
@@ -978,7 +999,7 @@ __global__ void __launch_bounds__(64 * TW) apply_team_kernel(ApplyArgs a, TeamPl
 #pragma unroll
   for (int k = 0; k < n; ++k) ps[k] = pos_c[k * n2];
   double u[n];
-  if constexpr (ABL & 32) { // direct gather through local_to_global (L2-served re-reads), no LDS staging
+  if constexpr (ABL & TEAM_DIRECT_GATHER) { // direct gather through local_to_global (L2-served re-reads), no LDS staging
     const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
     uint32_t idx[n];
 #pragma unroll
@@ -1175,12 +1196,12 @@ __global__ void __launch_bounds__(64 * TW) apply_team_kernel(ApplyArgs a, TeamPl
 // order: no global atomics, no zero-fill of dst, bitwise reproducible.
 // Build flags (ABL) select the shape.  First version: three transpose tiles per cell and a second register set
 // (double-buffered prefetch of the next pass: indices, gathered src values, all six metric planes), two workgroups per
-// CU.  Default at p = 4 (variant 56 = 2048 | 8192 | 16384 | 262144), all measured steps in profiles/r1/README.md:
-//   2048    single register set: 151-167 VGPRs -> three waves per SIMD
-//   8192    ONE transpose tile per cell, used field after field (32 lanes per cell: tile syncs are wave-local and
+// CU.  Default at p = 4 (variant 56 = BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK), all measured steps in profiles/r1/README.md:
+//   SINGLE  single register set: 151-167 VGPRs -> three waves per SIMD
+//   SEQ     ONE transpose tile per cell, used field after field (32 lanes per cell: tile syncs are wave-local and
 //           free) -> tiles + 17^3 accumulator + run tables = 49.5 KB -> three workgroups per CU
-//   16384   run-length write-out: the brick's sorted DoF list as <= 128 runs in LDS, 16-byte stores, no list loads
-//   262144  packed indices: one u16 (run << 9 | offset) per cell-local DoF gives both the accumulator slot and the
+//   RUNS    run-length write-out: the brick's sorted DoF list as <= 128 runs in LDS, 16-byte stores, no list loads
+//   PACK    packed indices: one u16 (run << 9 | offset) per cell-local DoF gives both the accumulator slot and the
 //           DoF to gather through that run table; local_to_global is not read
 // With the metric in the pair layout (coef_off) a lane issues 18 + 3 + 5 + 1 load instructions per cell.
 
@@ -1455,7 +1476,7 @@ constexpr int BLOCK_MAX_RUNS = 128;
 constexpr uint32_t BLOCK_DOF_MASK = 0x3fffffffu, BLOCK_DOF_CONSTRAINED = 0x40000000u;
 constexpr int PARTIAL_STRIDE = 8192;   // row length of the partial-sum array d_partials[8][PARTIAL_STRIDE] (all reducing kernels)
 constexpr int BLOCK_LATTICE_WORDS = 64; // per block: 27 entity slots, 27 entity DoFs, dims | flag, face-carry words, padding (bp5_device.hip: detect_lattice_blocks)
-// face carry (builds with ABL & 268435456): when block g + 1 of the plan is the neighbour of block g across a face whose interior DoFs the two
+// face carry (builds with ABL & BLK_CARRY): when block g + 1 of the plan is the neighbour of block g across a face whose interior DoFs the two
 // share with nobody else, and one workgroup walks both, the face's partial sums stay in LDS from the write-out of g to the write-out of
 // g + 1, which stores p(g + 1) + p(g) as an owner store -- the bits of the combine pass's p(g) + p(g + 1) without the slab round trip.
 // Lattice words of block g: [55] = face DoFs << 16 | first list slot of the face g can hand to g + 1 (0: none), [56] = the same for the face g
@@ -1471,7 +1492,7 @@ struct BlockPlan {
   const uint32_t *dofs;       // sorted distinct DoFs per block; bit 31: touched by this block only
   const uint16_t *pos;        // [n_cells*n^3] position of each local DoF in its block's list, pair layout (coef_off(k, i + n j))
   const uint32_t *gidx;       // [n_cells*n^3] local_to_global in the same pair layout
-  // packed form (builds with ABL & 262144): ONE u16 per cell-local DoF = run << 9 | offset in the run (runs are cut at
+  // packed form (builds with ABL & BLK_PACK): ONE u16 per cell-local DoF = run << 9 | offset in the run (runs are cut at
   // 512 entries and where the Dirichlet flag changes, at most 128 per block -- a boundary brick of a slab mesh with its ghost rows has ~70); list slot = run_slot[run] + offset, DoF = run_dof[run] + offset, both from the
   // block's run table in LDS -- the local_to_global stream is not read at all
   const uint16_t *packed;     // [n_cells*n^3], pair layout
@@ -1491,14 +1512,14 @@ struct BlockPlan {
   // (hipStreamWaitValue64), combines the ghost rows and sends them
   uint32_t n_parts;           // 1 or 2
   unsigned long long *signal; // NULL: nobody waits
-  // run-length form of dofs (builds with ABL & 16384): run r of block b covers the list slots [runs[2r], runs[2r+2]) and
+  // run-length form of dofs (builds with ABL & BLK_RUNS): run r of block b covers the list slots [runs[2r], runs[2r+2]) and
   // the consecutive DoFs starting at runs[2r+1] (bit 31 as in dofs); at most BLOCK_MAX_RUNS runs per block
   const uint32_t *run_off;    // [n_blocks+1]
   const uint32_t *runs;       // [2 * run_off[n_blocks]]
   uint32_t max_list;          // longest block list (the accumulator's size in LDS)
   uint32_t carry;             // face-carry builds: 1 = carry (the combine tables of this launch leave the carried faces out), 0 = every shared DoF to the slab
   unsigned long long *stamps; // diagnostic builds only: [n_wg][16] cycle sums per phase (never read by kernels)
-  // builds with ABL & 1048576 (fused CG dot products, SolverCGFullMerge's update_b, bp5/solver.h:142-311): src == p, dst == v
+  // builds with ABL & BLK_FUSE (fused CG dot products, SolverCGFullMerge's update_b, bp5/solver.h:142-311): src == p, dst == v
   const double *cg_r;         // residual vector r
   double *dot_partials;       // [7][PARTIAL_STRIDE] row k, column = dot_col0 + workgroup: p.v, v.v, r.v, r.r (rows 4-6 = rows 2, 1, 3: D == 1)
   uint32_t dot_col0;          // first column of this launch (the boundary-first schedule runs the bricks in two launches)
@@ -1545,7 +1566,7 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #endif
 #define BP5_PRIO_PHASE(k) if constexpr ((k) >= 0) __builtin_amdgcn_s_setprio((k) < 0 ? 0 : (k));
 #define BP5_STAMP(slot)                                                                                            \
-  if constexpr (ABL & 4096) {                                                                                      \
+  if constexpr (ABL & BLK_STAMPS) {                                                                                \
     const unsigned long long now_ = stamp_now();                                                                   \
     ph[slot] += now_ - tprev;                                                                                      \
     tprev = now_;                                                                                                  \
@@ -1554,46 +1575,36 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #ifndef BP5_WAVE_PACK
 #define BP5_WAVE_PACK 1
 #endif
-// Build bits of the block kernel (the ABL template argument of BlockPass / apply_block_kernel; what each selects is described at the
-// BlockPass member of the same name).  Bits below 1024 are timing-only ablations (no write-out, no metric loads, no gather ...).  The
-// pencil and team kernels read the AFFINE, HANG and HELM bits of their own mask with the same meaning.
-enum : int {
-  BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_PACK = 262144,
-  BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
-  BLK_ROLL = 67108864, BLK_CARRY = 268435456, // (BLK_F32M = 536870912: FP32 metric planes, defined next to load_pencil)
-  // the default shape: metric loaded in its own pass, sequential tiles, run-length write-out, packed indices
-  BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK
-};
 template <int P, bool COLL, int LPC, int SCATTER, int ABL>
 struct BlockPass {
   static constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
   static constexpr int TEAM = 256;
   static constexpr int CPT = TEAM / LPC;
-  static constexpr bool AFFINE = (ABL & 1024) != 0;
+  static constexpr bool AFFINE = (ABL & BLK_AFFINE) != 0;
   // SINGLE: the metric of a pass is loaded at the top of that pass (as in apply_pencil_kernel) and only the
   // indices / gathered values are prefetched one pass ahead: ~60 fewer VGPRs -> three workgroups per CU
-  static constexpr bool SINGLE = (ABL & 2048) != 0;
+  static constexpr bool SINGLE = (ABL & BLK_SINGLE) != 0;
   // HELM: step-64's Helmholtz operator, see apply_pencil_kernel (one more contraction each way, one more plane: a(x_q) JxW)
-  static constexpr bool HELM = (ABL & 8388608) != 0;
+  static constexpr bool HELM = (ABL & BLK_HELM) != 0;
   static constexpr int NPL = HELM ? 7 : 6;
-  static_assert(!HELM || (!AFFINE && (ABL & 8192) != 0), "Helmholtz build: six-plane geometry, sequential tiles");
+  static_assert(!HELM || (!AFFINE && (ABL & BLK_SEQ) != 0), "Helmholtz build: six-plane geometry, sequential tiles");
   // HANG: 2:1 refined meshes -- resolve_hanging_nodes after the gather and its adjoint before the accumulation into the brick vector
   // (bp5/fe_evaluation_gl.h:150-151,167-168), through the cell's transpose tile like apply_pencil_kernel; a pass without a flagged
   // cell skips both (one ballot / one barrier-with-or per pass)
-  static constexpr bool HANG = (ABL & 2097152) != 0;
-  static_assert(!HANG || (ABL & 8192) != 0, "hanging-node build: sequential tiles");
+  static constexpr bool HANG = (ABL & BLK_HANG) != 0;
+  static_assert(!HANG || (ABL & BLK_SEQ) != 0, "hanging-node build: sequential tiles");
   // ROLL: rolling metric prefetch.  The metric of pass q + 1 is loaded INTO THE REGISTERS OF PASS q's METRIC, piece by piece, each piece right
   // after the quadrature-point loop of pass q has consumed it: the six planes of the next pass are in flight during integrate, accumulation,
   // write-out and the next evaluate -- a whole pass ahead -- at the register cost of the single-buffered build (three workgroups per CU).
   // Without it a wave has loads in flight during evaluate only.  MEASURED, NOT ADOPTED (profiles/r4 d_*): held for a whole pass the six planes cost
   // 50 more VGPRs than the three-waves-per-SIMD budget has (210-221 against 168); at two workgroups per CU the kernel takes 2.72 against 2.40 ms, capped
   // at 168 registers it spills and takes 4.73 -- this kernel lives on its twelve waves per CU, not on its prefetch depth.  Kept for libbp5_timing.so
-  static constexpr bool ROLL = (ABL & 67108864) != 0;
-  static_assert(!ROLL || (((ABL & 2048) != 0) && ((ABL & 8192) != 0) && !AFFINE), "rolling prefetch: single-buffered build, sequential tiles, plane geometry");
+  static constexpr bool ROLL = (ABL & BLK_ROLL) != 0;
+  static_assert(!ROLL || (((ABL & BLK_SINGLE) != 0) && ((ABL & BLK_SEQ) != 0) && !AFFINE), "rolling prefetch: single-buffered build, sequential tiles, plane geometry");
   // F32M: the metric planes are float (bp5_mf_set_metric_precision): half the bytes of the stream this kernel lives on; the pencils stay float in
   // registers until the quadrature-point loop widens them, the arithmetic is double as in every other build
   using MT = metric_t<ABL>;
-  static_assert((ABL & BLK_F32M) == 0 || (!AFFINE && !HELM && !ROLL && (ABL & 1048576) == 0), "FP32 metric planes: Poisson operator, six-plane geometry, no fused dot products");
+  static_assert((ABL & BLK_F32M) == 0 || (!AFFINE && !HELM && !ROLL && (ABL & BLK_FUSE) == 0), "FP32 metric planes: Poisson operator, six-plane geometry, no fused dot products");
   using R = PassRegs<n, AFFINE, NPL, ROLL, MT>;
   // all lanes of a cell slot sit in one wave when LPC divides 64: the tile exchanges then need no block barrier
   // WPACK (round 4, p = 2): 9 lanes per cell do not divide a wave, but SEVEN whole cells fit one (63 lanes) and 4 x 7 = 28 = 256 / 9 cells fill the pass
@@ -1603,18 +1614,18 @@ struct BlockPass {
   static constexpr bool WAVE_LOCAL = (64 % LPC == 0) || WPACK;
   // SEQ: the transposes go through ONE field tile per cell, field after field (wave-local syncs are free), so a
   // workgroup needs a third of the tile memory: 4x4x4 accumulator + tiles = 47 KB -> three workgroups per CU
-  static constexpr bool PACK = (ABL & 262144) != 0; // packed (run, offset) indices, decoded through the LDS run table
+  static constexpr bool PACK = (ABL & BLK_PACK) != 0; // packed (run, offset) indices, decoded through the LDS run table
   // LATT: EVERY block of the plan is a lattice block (bp5_device.hip: detect_lattice_blocks) -- list slots and DoFs in closed form from the
   // cell's position in its block, no per-DoF index stream at all (a build of its own: the headline kernel sits at the register budget of
   // three waves per SIMD, and this path needs fewer registers than the packed one, both together more)
-  static constexpr bool LATT = (ABL & 16777216) != 0;
+  static constexpr bool LATT = (ABL & BLK_LATT) != 0;
   static_assert(!LATT || PACK, "lattice build: on top of the packed shape (run tables for the write-out)");
   // STAGE: the brick's src values are staged ONCE in an LDS array indexed like the accumulator (block start: coalesced loads
   // along the runs of the brick's sorted DoF list); the cells gather from LDS -- no global gather instructions, every src
   // entry of a brick crosses HBM/L2 once instead of once per cell that touches it
-  static constexpr bool STAGE = (ABL & 524288) != 0;
-  static_assert(!STAGE || (PACK && (ABL & 16384)), "LDS-staged src needs packed indices and the run table");
-  static constexpr bool SEQ = (ABL & 8192) != 0;
+  static constexpr bool STAGE = (ABL & BLK_STAGE) != 0;
+  static_assert(!STAGE || (PACK && (ABL & BLK_RUNS)), "LDS-staged src needs packed indices and the run table");
+  static constexpr bool SEQ = (ABL & BLK_SEQ) != 0;
   // (p = 8: 81 lanes per cell span two waves; the tile exchanges then use the workgroup barrier -- correct, every lane reaches every sync)
   // PP: cells that span waves exchange their tiles through the WORKGROUP barrier (20 barriers per pass with one tile: write, barrier, read,
   // barrier, field after field).  Two tiles used alternately need no barrier behind the reads -- the next field goes to the OTHER tile, and
@@ -1666,7 +1677,7 @@ struct BlockPass {
 #pragma unroll
         for (int i = 0; i < n; ++i) S[pl][i] = 1.0 + pl + i;
       } else
-        load_pencil<n, (ABL & 32768) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
+        load_pencil<n, (ABL & BLK_NTM) != 0>(cf + pl * a.plane_stride, abm, S[pl]);
     }
   }
   static __device__ __forceinline__ void issue_metric(const ApplyArgs &a, R &r, int abm)
@@ -1717,7 +1728,7 @@ struct BlockPass {
 #pragma unroll
           for (int i = 0; i < n; ++i) r.S[pl][i] = 1.0 + pl + i;
         } else
-          load_pencil<n, (ABL & 32768) != 0>(cf + pl * a.plane_stride, abm, r.S[pl]);
+          load_pencil<n, (ABL & BLK_NTM) != 0>(cf + pl * a.plane_stride, abm, r.S[pl]);
       }
     }
   }
@@ -1893,17 +1904,17 @@ struct BlockPass {
         }
         // fused CG: src . (A src) is the sum over cells and quadrature points of ghat^T S ghat -- everything is in
         // registers here, the dot product costs no memory traffic at all
-        if constexpr ((ABL & 1048576) != 0) { if (act) energy += x0 * q0[i] + x1 * q1[i] + x2 * q2[i]; }
+        if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += x0 * q0[i] + x1 * q1[i] + x2 * q2[i]; }
         if constexpr (HELM) {
           const double uq = um[i];
           um[i] = SM(6) * uq; // submit_value(coef * get_value(q)), JxW folded into the plane
-          if constexpr ((ABL & 1048576) != 0) { if (act) energy += uq * um[i]; }
+          if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += uq * um[i]; }
         }
       };
       if constexpr (ROLL) {
         // consume the metric pair by pair and refill each pair with the NEXT pass's values right away (same registers)
         const double *cfn = a.coef + (uint64_t)(nxt.ent & 0x7fffffffu) * a.cell_stride;
-        constexpr bool NTM = (ABL & 32768) != 0;
+        constexpr bool NTM = (ABL & BLK_NTM) != 0;
 #pragma unroll
         for (int m = 0; m < n / 2; ++m) {
           qpoint(2 * m, [&](int pl) { return Sr[pl][2 * m]; });
@@ -2033,7 +2044,7 @@ struct BlockPass {
         if (act && cur.round == rd) {
 #pragma unroll
           for (int k = 0; k < n; ++k) {
-            if constexpr ((ABL & 4194304) != 0) lds_add_f64(acc + cur.ps[k], yy[k]); // ds_add_f64, no return value: one LDS op per entry
+            if constexpr ((ABL & BLK_LDSADD) != 0) lds_add_f64(acc + cur.ps[k], yy[k]); // ds_add_f64, no return value: one LDS op per entry
             else acc[cur.ps[k]] += yy[k];
           }
         }
@@ -2211,7 +2222,7 @@ struct BlockPass {
 
 // the rolling-prefetch builds (BlockPass::ROLL; libbp5_timing.so only) take 210-221 VGPRs: two workgroups per CU (capped at three waves per SIMD they spill
 // 100-150 registers and run at half the speed)
-#define BP5_ROLL_TWO(ABL) (((ABL) & 67108864) != 0)
+#define BP5_ROLL_TWO(ABL) (((ABL) & BLK_ROLL) != 0)
 // workgroups per CU (= waves per SIMD: 256-thread workgroups) the block kernel is compiled for and launched with: three for the single-buffered builds
 // up to p = 4 (168 VGPRs), two otherwise (p >= 5: registers; Helmholtz; the rolling-prefetch probe).  p = 1 (round 4): FOUR -- the kernel needs 101 VGPRs
 // and 15 KB of LDS, and its waves wait two thirds of their life (profiles/r4 g_*): a pass is 64 cells with 6 loads per lane, all latency
@@ -2224,9 +2235,9 @@ struct BlockPass {
 template <int P, int ABL>
 constexpr int block_wg_per_cu()
 {
-  if (!(ABL & 2048) || (ABL & 8388608) || BP5_ROLL_TWO(ABL) || P > 4) return 2;
-  if (P == 1 && !(ABL & 2097152) && !(ABL & 1024)) return BP5_WG_PER_CU_P1;
-  if (P == 2 && BP5_WAVE_PACK != 0 && !(ABL & 2097152) && !(ABL & 1024)) return BP5_WG_PER_CU_P2; // (wave-packed cells: one tile per slot, 36 KB of LDS on 8x8x4 bricks, 126 VGPRs)
+  if (!(ABL & BLK_SINGLE) || (ABL & BLK_HELM) || BP5_ROLL_TWO(ABL) || P > 4) return 2;
+  if (P == 1 && !(ABL & BLK_HANG) && !(ABL & BLK_AFFINE)) return BP5_WG_PER_CU_P1;
+  if (P == 2 && BP5_WAVE_PACK != 0 && !(ABL & BLK_HANG) && !(ABL & BLK_AFFINE)) return BP5_WG_PER_CU_P2; // (wave-packed cells: one tile per slot, 36 KB of LDS on 8x8x4 bricks, 126 VGPRs)
   return 3;
 }
 // wave priority (round 4): the instructions that ISSUE a pass's loads (metric planes, indices, gather) and the write-out of a block run at s_setprio 3, the
@@ -2242,7 +2253,7 @@ constexpr int block_wg_per_cu()
 #define BP5_SETPRIO_WO 3
 #endif
 // (lattice and Helmholtz builds: measured there; the packed-index build of p = 4 sits at its 168 registers and would spill two)
-#define BP5_PRIO_ON (BP::LATT || (ABL & 8388608) != 0)
+#define BP5_PRIO_ON (BP::LATT || (ABL & BLK_HELM) != 0)
 #define BP5_PRIO_HI if constexpr (BP5_SETPRIO != 0 && BP5_PRIO_ON) __builtin_amdgcn_s_setprio(BP5_SETPRIO);
 #define BP5_PRIO_LO if constexpr (BP5_SETPRIO != 0 && BP5_PRIO_ON) __builtin_amdgcn_s_setprio(0);
 #define BP5_PRIO_WO_HI if constexpr (BP5_SETPRIO_WO != 0 && BP5_PRIO_ON) __builtin_amdgcn_s_setprio(BP5_SETPRIO_WO);
@@ -2268,8 +2279,8 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   const uint32_t w = (blockIdx.x & 7u) * (bp.n_wg >> 3) + (blockIdx.x >> 3);
   // DOTS: the write-out also accumulates the merged CG's v-dependent dot products over the DoFs it stores (and writes src
   // instead of the sum on Dirichlet DoFs); brick-surface DoFs are handled the same way by combine_runs_kernel<.., true>
-  constexpr bool DOTS = (ABL & 1048576) != 0;
-  static_assert(!DOTS || (((ABL & 16384) != 0) && ((ABL & 8192) != 0) && SCATTER == SC_OWNER_SET), "fused dot products: run-length write-out, sequential tiles, overwrite mode");
+  constexpr bool DOTS = (ABL & BLK_FUSE) != 0;
+  static_assert(!DOTS || (((ABL & BLK_RUNS) != 0) && ((ABL & BLK_SEQ) != 0) && SCATTER == SC_OWNER_SET), "fused dot products: run-length write-out, sequential tiles, overwrite mode");
   double ds[4] = {0.0, 0.0, 0.0, 0.0};
   // this workgroup is through with its ghost-touching bricks: release its stores (every wave's -- the barrier orders them before
   // thread 0's device-scope fence) and count it in
@@ -2313,7 +2324,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   // write-out by runs: the block's run table is fetched into registers at the top of its last pass, parked in one of
   // two LDS tables (block parity: a wave may still be writing out block b while another one enters b + 1) right
   // before the write-out barrier, and every thread walks it forward for its slots -- no list loads in the write-out
-  constexpr bool RUNS = (ABL & 16384) != 0;
+  constexpr bool RUNS = (ABL & BLK_RUNS) != 0;
   constexpr bool STAGE = BP::STAGE;
   double *const staged = acc + bp.max_list; // STAGE: src values of the current brick, indexed like acc
   uint32_t *const run_tab = reinterpret_cast<uint32_t *>(acc + (STAGE ? 2 : 1) * (size_t)bp.max_list);
@@ -2322,7 +2333,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   constexpr bool use_lattice = BP::LATT;
   uint32_t lat_word = 0;
   // face carry: two buffers (block parity: the write-out of block b reads the one block b - 1 filled and fills the other)
-  constexpr bool CARRY = (ABL & 268435456) != 0;
+  constexpr bool CARRY = (ABL & BLK_CARRY) != 0;
   static_assert(!CARRY || (BP::LATT && RUNS), "face carry: lattice blocks with run tables");
   double *const carry_buf = reinterpret_cast<double *>(lat_tab + 2 * BLOCK_LATTICE_WORDS);
   bool c_carried = false;             // the previous block of this workgroup handed its face on
@@ -2369,7 +2380,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   // two register sets, used alternately (loop unrolled by two): the loads of pass q+1 are issued
   // at the top of pass q and first waited for inside pass q+1
   unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-  if constexpr (ABL & 4096) tprev = stamp_now();
+  if constexpr (ABL & BLK_STAMPS) tprev = stamp_now();
   typename BP::R A, B;
   double Sroll[BP::ROLL ? BP::NPL : 1][BP::ROLL ? n : 1]; // ROLL: the one metric register set, refilled piece by piece (BlockPass::run)
   A.ent = entry(gp);
@@ -2396,7 +2407,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   // end-of-pass bookkeeping: when a block is finished, write it out and re-arm the accumulator.  The block's
   // DoF list is prefetched into registers at the top of its last pass (prefetch_list), so the write-out does
   // not wait on dependent loads; entries beyond MAXW per thread (very large blocks) take the slow path.
-  constexpr int MAXW = (ABL & 2048) ? 1 : 6; // registers are scarce (the single-buffered build is capped at 168)
+  constexpr int MAXW = (ABL & BLK_SINGLE) ? 1 : 6; // registers are scarce (the single-buffered build is capped at 168)
   uint32_t gl[MAXW];
   // bookkeeping scalars of the NEXT block, fetched at the top of this block's last pass so that the block switch
   // does not wait for them
@@ -2686,7 +2697,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
       bp.dot_partials[t * PARTIAL_STRIDE + bp.dot_col0 + blockIdx.x] = (red[k * 4] + red[k * 4 + 1]) + (red[k * 4 + 2] + red[k * 4 + 3]);
     }
   }
-  if constexpr (ABL & 4096) {
+  if constexpr (ABL & BLK_STAMPS) {
     if (t == 0) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) bp.stamps[(uint64_t)w * 16 + k] = ph[k];
