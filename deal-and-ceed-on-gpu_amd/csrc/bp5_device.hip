@@ -1712,8 +1712,13 @@ static int phases_begin(bp5_mf *mf, double *dst, bool overwrite, ApplyCall &call
     call.combine_later = true;
     call.set_variant(ev); // every range takes the block kernel, however few bricks it holds (and the combine passes the form the variant implies)
     call.keep_variant = true;
-  } else if (overwrite) // atomic kernels accumulate: one zero-fill, then every range adds
+  } else if (overwrite) { // atomic kernels accumulate: one zero-fill, then every range adds
     HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream));
+    // Known zero for EVERY range, not the first alone: the only launches that rely on it store the entries strictly inside a cell (interior stores
+    // of the pencil kernel).  Such an entry belongs to one cell, every cell is in exactly one range, and neither the other ranges' atomics nor the
+    // halo exchange (interface and ghost DoFs: on cell surfaces) ever touch it -- it still holds the zero of this fill when its one store arrives
+    call.dst_known_zero = true;
+  }
   return BP5_OK;
 }
 static int phases_range(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1)
@@ -2036,6 +2041,7 @@ static int solver_vmult(bp5_mf *mf, SolveState &ss, const double *coef, double *
   if (zero && !owner_scatter) {
     if (!ss.dst_prezeroed) HIP_TRY(hipMemsetAsync(dst, 0, mf->n_local() * sizeof(double), mf->stream)); // (else: the update kernel stored the zeros)
     zero = false;
+    call.dst_known_zero = true;
   }
   BP5_TRY(prof.mark(1));
   if (prof.on) call.mark_event = mf->ev_pool[prof.used + 2];

@@ -200,6 +200,9 @@ enum { EXCHANGE_NONE = 0, EXCHANGE_BOUNDARY_FIRST = 1, EXCHANGE_GHOST_ROWS_FIRST
 struct ApplyCall {
   uint32_t c0 = 0, c1 = 0;     // cell range
   bool overwrite = false;      // the launch must leave dst = A src (no prior zeroing by the caller); otherwise dst += A src
+  // dst is all zero where this launch starts although overwrite is false: the caller (or the solver's update kernel) has just zero-filled it.  Builds
+  // that STORE an entry instead of adding to it (PEN_INTERIOR_STORES) need overwrite or this; an accumulating call on the caller's dst has neither
+  bool dst_known_zero = false;
   int variant = 0;             // resolved apply variant: launch_apply takes it from effective_variant(handle, range) ...
   bool keep_variant = false;   // ... unless the caller fixed it (phased applications: ONE kernel family for every range)
   // the switches a variant implies (decode_variant), for every degree and operator; their only readers are the p = 4 block / team launches and
@@ -824,8 +827,10 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
   int variant = call.variant % 100;
   if (variant == 0) {
     // cell-interior DoFs numbered ahead of all others (recognised by bp5_mf_create): the default pencil kernel of p >= 5 stores the entries a cell owns alone
-    // plainly -- (p-1)^3 of (p+1)^3 atomics less per cell (47 % at p = 8), and no store ever meets an atomic in one cache line
-    if constexpr (DEG >= 5) if (!call.atomic_scatter && mf->cell_interiors_first && mf->tune[BP5_TUNE_INTERIOR_STORES])
+    // plainly -- (p-1)^3 of (p+1)^3 atomics less per cell (47 % at p = 8), and no store ever meets an atomic in one cache line.  A plain store REPLACES
+    // what dst held, so the build is taken only where that is known to be zero: the launch zero-fills itself (overwrite), or the caller has
+    // (ApplyCall::dst_known_zero).  dst += A src on the caller's own content (bp5_apply with zero_dst = 0, bp5_apply_cells) takes the atomics
+    if constexpr (DEG >= 5) if (!call.atomic_scatter && mf->cell_interiors_first && mf->tune[BP5_TUNE_INTERIOR_STORES] && (overwrite || call.dst_known_zero))
       return LAUNCH_DEFAULT_PENCIL(PEN_INTERIOR_STORES, coef);
     return LAUNCH_DEFAULT_PENCIL(0, coef);
   }

@@ -567,6 +567,16 @@ def test_face_carry_keeps_shared_faces_in_lds_and_changes_no_bit_of_v(cells, blo
             op.do_zero_out = True
             if ref is None:
                 ref = (v.clone(), w.clone())
+                # the first pair against the oracle on the slab's own cells (its coordinates and local_to_global): v = A u and w = w0 + A u, the Dirichlet copy on top
+                from types import SimpleNamespace
+                lm = SimpleNamespace(p=4, n=5, n_cells=mesh.n_cells, n_dofs=mesh.n_local, l2g=np.asarray(mesh.l2g), coords=np.asarray(mesh.coords))
+                _, _, wq, N, D = O.shape_tables(4, 0)
+                un, cst = u.cpu().numpy(), np.asarray(mesh.constrained).astype(np.int64)
+                Au = O.apply_cells(lm, O.merged_metric(lm, N, D, wq, O.kappa_step64), N, D, un)
+                v_want, w_want = Au.copy(), w0.cpu().numpy() + Au
+                v_want[cst] = w_want[cst] = un[cst]
+                assert np.abs(v.cpu().numpy() - v_want).max() <= TOL_OP * np.abs(v_want).max()
+                assert np.abs(w.cpu().numpy() - w_want).max() <= TOL_OP * np.abs(w_want).max()
             assert torch.equal(v, ref[0]) and torch.equal(w, ref[1]), (n_wg, carry)
     if kw:
         return      # (a slab without its neighbours: operator only)
