@@ -185,6 +185,11 @@ def lib():
         "bp5_halo_scatter_add": (i32, [vp, vp]),
         "bp5_halo_zero_ghosts": (i32, [vp, vp]),
         "bp5_apply_distributed": (i32, [vp, vp, vp, vp, i32]),
+        "bp5_halo_gather_components": (i32, [vp, i32, sz, vp]),
+        "bp5_halo_scatter_add_components": (i32, [vp, i32, sz, vp]),
+        "bp5_halo_zero_ghosts_components": (i32, [vp, i32, sz, vp]),
+        "bp5_apply_components_distributed": (i32, [vp, vp, i32, sz, vp, vp, i32]),
+        "bp5_cg_solve_components_distributed": (i32, [vp, vp, i32, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve": (i32, [vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_components": (i32, [vp, vp, i32, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_operator": (i32, [vp, VMULT_FN, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),

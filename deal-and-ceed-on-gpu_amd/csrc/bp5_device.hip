@@ -184,7 +184,7 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   hipStreamSynchronize(mf->stream);
   void *ptrs[] = {mf->d_constrained_bits, mf->d_l2g, mf->d_constrained, mf->d_send_idx, mf->d_coords, mf->d_tab, mf->d_tab_gauss, mf->d_l2g_padded,
                   mf->d_constraint_mask, mf->d_inv_jac, mf->d_JxW, mf->d_qpoints, mf->d_sendbuf, mf->d_recvbuf, mf->d_partials,
-                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base};
+                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->hc_base, mf->d_hc_off};
   for (void *p : ptrs) if (p) hipFree(p);
   if (mf->h_sc) hipHostFree(mf->h_sc);
   if (mf->h_st) hipHostFree(mf->h_st);
@@ -1162,15 +1162,22 @@ extern "C" int bp5_apply(bp5_mf *mf, const double *coef, const double *src, doub
 }
 
 // ------------------------------------------------------------------------------------ block vectors (n_components)
-// every refusal of bp5_apply_components / bp5_cg_solve_components, decided before any launch.  What needs no handle comes first, so that a bad
-// layout is named as such whatever the handle is.
+// every refusal of bp5_apply_components / bp5_cg_solve_components and of their *_distributed twins, decided before any launch.  What needs no
+// handle comes first, so that a bad layout is named as such whatever the handle is.
 static inline bool aligned16(const void *p);
-static int components_check(const bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
+// ... the part that needs no handle (all that the bp5_halo_*_components entries, which take ONE block vector, check besides the handle: v == w)
+static int components_layout_check(int n_components, size_t ld, const double *v, const double *w)
 {
-  if (!src || !dst) return fail(BP5_ERR_INVALID, "null argument");
+  if (!v || !w) return fail(BP5_ERR_INVALID, "null argument");
   if (n_components < 1 || n_components > BP5_MAX_COMPONENTS) return fail(BP5_ERR_INVALID, "n_components must be 1 .. BP5_MAX_COMPONENTS");
   if (ld & 1) return fail(BP5_ERR_INVALID, "block vectors: ld must be even (every block 16-byte aligned)");
-  if (!aligned16(src) || !aligned16(dst)) return fail(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  if (!aligned16(v) || !aligned16(w)) return fail(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  return BP5_OK;
+}
+// with_exchange: the *_distributed entries, which bring the halo exchange a handle with a communicator and neighbours needs
+static int components_check(const bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, bool with_exchange = false)
+{
+  BP5_TRY(components_layout_check(n_components, ld, src, dst));
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst overlap");
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
   if (ld < mf->n_local()) return fail(BP5_ERR_INVALID, "block vectors: ld < n_owned + n_ghost");
@@ -1180,7 +1187,7 @@ static int components_check(const bp5_mf *mf, const double *coef, int n_componen
   if (mf->operator_kind != BP5_OP_POISSON) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the Helmholtz operator is not supported");
   if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "block vectors: meshes with hanging nodes are not supported");
   if (mf->geometry_mode != BP5_GEOM_MERGED6) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the affine geometry mode is not supported");
-  if (mf->comm && !mf->neighbors.empty()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: no halo exchange (a handle with a communicator and neighbours)");
+  if (!with_exchange && mf->comm && !mf->neighbors.empty()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: no halo exchange (a handle with a communicator and neighbours)");
   if (!coef) return fail(BP5_ERR_INVALID, "null argument");
   return BP5_OK;
 }
@@ -1192,18 +1199,24 @@ static int components_zero(bp5_mf *mf, int n_components, size_t ld, double *dst)
   return BP5_OK;
 }
 // [dst = 0] ; dst_c += A src_c on validated arguments (the Dirichlet copy is the caller's next launch)
+static int components_apply_cells(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1);
 static int components_apply(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, bool zero)
 {
   if (zero) BP5_TRY(components_zero(mf, n_components, ld, dst));
+  return components_apply_cells(mf, coef, n_components, ld, src, dst, 0, mf->n_cells);
+}
+// dst_c += A src_c over the cells [c0, c1) (empty: nothing is launched)
+static int components_apply_cells(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1)
+{
   switch (mf->degree) {
-    case 1: BP5_TRY(apply_components_degree_impl<1>(mf, coef, n_components, ld, src, dst)); break;
-    case 2: BP5_TRY(apply_components_degree_impl<2>(mf, coef, n_components, ld, src, dst)); break;
-    case 3: BP5_TRY(apply_components_degree_impl<3>(mf, coef, n_components, ld, src, dst)); break;
-    case 4: BP5_TRY(apply_components_degree_impl<4>(mf, coef, n_components, ld, src, dst)); break;
-    case 5: BP5_TRY(apply_components_degree_impl<5>(mf, coef, n_components, ld, src, dst)); break;
-    case 6: BP5_TRY(apply_components_degree_impl<6>(mf, coef, n_components, ld, src, dst)); break;
-    case 7: BP5_TRY(apply_components_degree_impl<7>(mf, coef, n_components, ld, src, dst)); break;
-    case 8: BP5_TRY(apply_components_degree_impl<8>(mf, coef, n_components, ld, src, dst)); break;
+    case 1: BP5_TRY(apply_components_degree_impl<1>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 2: BP5_TRY(apply_components_degree_impl<2>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 3: BP5_TRY(apply_components_degree_impl<3>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 4: BP5_TRY(apply_components_degree_impl<4>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 5: BP5_TRY(apply_components_degree_impl<5>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 6: BP5_TRY(apply_components_degree_impl<6>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 7: BP5_TRY(apply_components_degree_impl<7>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
+    case 8: BP5_TRY(apply_components_degree_impl<8>(mf, coef, n_components, ld, src, dst, c0, c1)); break;
     default: return fail(BP5_ERR_INVALID, "unsupported degree");
   }
   return BP5_OK;
@@ -1789,6 +1802,200 @@ extern "C" int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src
   return bp5_copy_constrained(mf, src, dst);
 }
 
+// ------------------------------------------------------------------------------------ halo exchange of block vectors
+// The ghost ranges of a block vector are n_components strided pieces: they can neither be received in place nor sent from one buffer, and an
+// exchange per component would multiply the RCCL groups (the expensive part: profiles/r4 z_*).  So every exchange goes through staging buffers
+// in which a neighbour's message is contiguous and holds all components (bp5_kernels.hpp: halo_message_pos): ONE send and ONE receive per
+// neighbour and direction, launches and RCCL calls independent of n_components.  Streams, events and the one-in-flight rule are the scalar path's.
+struct HaloStaging { double *gather_send, *gather_recv, *scatter_send, *scatter_recv; const uint32_t *send_off, *recv_off; };
+static int halo_components_staging(bp5_mf *mf, int n_components, HaloStaging &st)
+{
+  const size_t ns = mf->send_off.back(), ng = mf->n_ghost, nb = mf->neighbors.size();
+  const size_t need = 2 * (size_t)n_components * (ns + ng);
+  if (!mf->d_hc_off) {
+    std::vector<uint32_t> off(mf->send_off);
+    off.insert(off.end(), mf->recv_off.begin(), mf->recv_off.end());
+    BP5_TRY(upload(&mf->d_hc_off, off.data(), off.size()));
+  }
+  if (mf->hc_cap < need) {
+    if (mf->hc_base) { // (send and receive staging are distinct: a rank may be its own neighbour)
+      HIP_TRY(hipStreamSynchronize(mf->stream));
+      if (mf->comm_stream) HIP_TRY(hipStreamSynchronize(mf->comm_stream));
+      HIP_TRY(hipFree(mf->hc_base));
+      mf->hc_base = nullptr; mf->hc_cap = 0;
+    }
+    HIP_TRY(hipMalloc((void **)&mf->hc_base, std::max<size_t>(need, 1) * sizeof(double)));
+    mf->hc_cap = need;
+  }
+  st.gather_send = mf->hc_base;
+  st.gather_recv = st.gather_send + (size_t)n_components * ns;
+  st.scatter_send = st.gather_recv + (size_t)n_components * ng;
+  st.scatter_recv = st.scatter_send + (size_t)n_components * ng;
+  st.send_off = mf->d_hc_off;
+  st.recv_off = mf->d_hc_off + nb + 1;
+  return BP5_OK;
+}
+// the RCCL group of one exchange: `out` travels to the neighbours in pieces out_off, `in` arrives in pieces in_off (offsets of ONE component)
+static int halo_components_group(bp5_mf *mf, int n_components, const double *out, const std::vector<uint32_t> &out_off, double *in,
+                                 const std::vector<uint32_t> &in_off, hipStream_t cs)
+{
+  const size_t nc = (size_t)n_components;
+  NCCL_TRY(ncclGroupStart());
+  for (size_t k = 0; k < mf->neighbors.size(); ++k) {
+    const size_t oc = out_off[k + 1] - out_off[k], ic = in_off[k + 1] - in_off[k];
+    if (oc) NCCL_TRY(ncclSend(out + nc * out_off[k], nc * oc, ncclDouble, mf->neighbors[k], mf->comm->comm, cs));
+    if (ic) NCCL_TRY(ncclRecv(in + nc * in_off[k], nc * ic, ncclDouble, mf->neighbors[k], mf->comm->comm, cs));
+  }
+  NCCL_TRY(ncclGroupEnd());
+  return BP5_OK;
+}
+static inline dim3 halo_components_grid(uint32_t n, int n_components) { return dim3((n + 255) / 256, n_components); }
+// update_ghost_values_start: pack on the compute stream, the group on the communication stream (on_comm_stream) or behind the pack
+static int gather_components_start(bp5_mf *mf, int n_components, size_t ld, double *v, bool on_comm_stream)
+{
+  BP5_TRY(halo_streams(mf));
+  HaloStaging st;
+  BP5_TRY(halo_components_staging(mf, n_components, st));
+  const uint32_t ns = mf->send_off.back(), nb = (uint32_t)mf->neighbors.size();
+  if (ns) {
+    hipLaunchKernelGGL(pack_components_kernel, halo_components_grid(ns, n_components), dim3(256), 0, mf->stream, mf->d_send_idx, st.send_off, nb, ns, v, ld,
+                       st.gather_send);
+    KERNEL_CHECK();
+  }
+  mf->overlap_now = on_comm_stream;
+  hipStream_t cs = on_comm_stream ? mf->comm_stream : mf->stream;
+  if (on_comm_stream) {
+    HIP_TRY(hipEventRecord(mf->ev_halo[0], mf->stream));
+    HIP_TRY(hipStreamWaitEvent(cs, mf->ev_halo[0], 0));
+  }
+  BP5_TRY(halo_components_group(mf, n_components, st.gather_send, mf->send_off, st.gather_recv, mf->recv_off, cs));
+  if (on_comm_stream) HIP_TRY(hipEventRecord(mf->ev_halo[1], cs));
+  return BP5_OK;
+}
+// update_ghost_values_finish: the compute stream waits for the transfer and unpacks the messages into the ghost ranges
+static int gather_components_finish(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  if (mf->overlap_now) HIP_TRY(hipStreamWaitEvent(mf->stream, mf->ev_halo[1], 0));
+  if (!mf->n_ghost) return BP5_OK;
+  HaloStaging st;
+  BP5_TRY(halo_components_staging(mf, n_components, st));
+  hipLaunchKernelGGL(unpack_ghosts_components_kernel, halo_components_grid(mf->n_ghost, n_components), dim3(256), 0, mf->stream, st.recv_off,
+                     (uint32_t)mf->neighbors.size(), mf->n_ghost, st.gather_recv, v + mf->n_owned, ld);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+// compress_start(add): the ghost ranges are packed (and zeroed: nothing reads them before the exchange is finished) on the compute stream
+static int scatter_components_start(bp5_mf *mf, int n_components, size_t ld, double *v, bool on_comm_stream)
+{
+  BP5_TRY(halo_streams(mf));
+  HaloStaging st;
+  BP5_TRY(halo_components_staging(mf, n_components, st));
+  if (mf->n_ghost) {
+    hipLaunchKernelGGL(pack_ghosts_components_kernel, halo_components_grid(mf->n_ghost, n_components), dim3(256), 0, mf->stream, st.recv_off,
+                       (uint32_t)mf->neighbors.size(), mf->n_ghost, v + mf->n_owned, ld, st.scatter_send);
+    KERNEL_CHECK();
+  }
+  mf->overlap_now = on_comm_stream;
+  hipStream_t cs = on_comm_stream ? mf->comm_stream : mf->stream;
+  if (on_comm_stream) {
+    HIP_TRY(hipEventRecord(mf->ev_halo[2], mf->stream));
+    HIP_TRY(hipStreamWaitEvent(cs, mf->ev_halo[2], 0));
+  }
+  BP5_TRY(halo_components_group(mf, n_components, st.scatter_send, mf->recv_off, st.scatter_recv, mf->send_off, cs));
+  if (on_comm_stream) HIP_TRY(hipEventRecord(mf->ev_halo[3], cs));
+  return BP5_OK;
+}
+// compress_finish(add): neighbour after neighbour on the compute stream (indices of one neighbour are distinct; the fixed order makes the
+// exchange bitwise reproducible)
+static int scatter_components_finish(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  if (mf->overlap_now) HIP_TRY(hipStreamWaitEvent(mf->stream, mf->ev_halo[3], 0));
+  HaloStaging st;
+  BP5_TRY(halo_components_staging(mf, n_components, st));
+  for (size_t k = 0; k < mf->neighbors.size(); ++k) {
+    const uint32_t sc = mf->send_off[k + 1] - mf->send_off[k];
+    if (!sc) continue;
+    hipLaunchKernelGGL(unpack_add_components_kernel, halo_components_grid(sc, n_components), dim3(256), 0, mf->stream, mf->d_send_idx + mf->send_off[k], sc,
+                       st.scatter_recv + (size_t)n_components * mf->send_off[k], v, ld);
+    KERNEL_CHECK();
+  }
+  return BP5_OK;
+}
+static int zero_ghosts_components(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  if (!mf->n_ghost) return BP5_OK;
+  hipLaunchKernelGGL(zero_ghosts_components_kernel, halo_components_grid(mf->n_ghost, n_components), dim3(256), 0, mf->stream, v + mf->n_owned, mf->n_ghost, ld);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+// what the three public exchanges check: the layout of one block vector, then the handle
+static int halo_components_check(const bp5_mf *mf, int n_components, size_t ld, const double *v)
+{
+  BP5_TRY(components_layout_check(n_components, ld, v, v));
+  if (!mf) return fail(BP5_ERR_INVALID, "null handle");
+  if (ld < mf->n_local()) return fail(BP5_ERR_INVALID, "block vectors: ld < n_owned + n_ghost");
+  if (!mf->neighbors.empty() && !mf->comm) return fail(BP5_ERR_INVALID, "halo exchange needs bp5_mf_set_comm");
+  return BP5_OK;
+}
+extern "C" int bp5_halo_gather_components(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  BP5_TRY(halo_components_check(mf, n_components, ld, v));
+  if (mf->neighbors.empty()) return BP5_OK;
+  HIP_TRY(hipSetDevice(mf->device));
+  BP5_TRY(gather_components_start(mf, n_components, ld, v, overlap_wanted(mf)));
+  return gather_components_finish(mf, n_components, ld, v);
+}
+extern "C" int bp5_halo_scatter_add_components(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  BP5_TRY(halo_components_check(mf, n_components, ld, v));
+  HIP_TRY(hipSetDevice(mf->device));
+  if (mf->neighbors.empty()) return zero_ghosts_components(mf, n_components, ld, v); // (as the scalar call: ghosts zeroed either way)
+  BP5_TRY(scatter_components_start(mf, n_components, ld, v, overlap_wanted(mf)));
+  return scatter_components_finish(mf, n_components, ld, v);
+}
+extern "C" int bp5_halo_zero_ghosts_components(bp5_mf *mf, int n_components, size_t ld, double *v)
+{
+  BP5_TRY(components_layout_check(n_components, ld, v, v));
+  if (!mf) return fail(BP5_ERR_INVALID, "null handle");
+  if (ld < mf->n_local()) return fail(BP5_ERR_INVALID, "block vectors: ld < n_owned + n_ghost");
+  HIP_TRY(hipSetDevice(mf->device));
+  return zero_ghosts_components(mf, n_components, ld, v);
+}
+
+// dst_c += A src_c with the exchange (dst zeroed first where asked), on a handle with a communicator and neighbours: the schedules of
+// apply_overlapped for an atomic kernel.  Unsplit (overlap off, or auto below the threshold of overlap_wanted): gather, all cells, scatter-add
+// on the handle's stream.  Three-phase: gather in flight under the cells [0, split), the ghost-touching cells, the ghost contributions on their
+// way under the cells [split, n_interior).  Ghosts of src are zeroed again; the Dirichlet copy is the caller's next launch.
+static int components_apply_exchanged(bp5_mf *mf, const double *coef, int n_components, size_t ld, double *src, double *dst, bool zero)
+{
+  const bool split = overlap_wanted(mf);
+  BP5_TRY(gather_components_start(mf, n_components, ld, src, split));
+  if (zero) BP5_TRY(components_zero(mf, n_components, ld, dst));
+  if (!split) {
+    BP5_TRY(gather_components_finish(mf, n_components, ld, src));
+    BP5_TRY(components_apply_cells(mf, coef, n_components, ld, src, dst, 0, mf->n_cells));
+    BP5_TRY(scatter_components_start(mf, n_components, ld, dst, false));
+  } else {
+    const uint32_t half = interior_split(mf);
+    BP5_TRY(components_apply_cells(mf, coef, n_components, ld, src, dst, 0, half));                       // under the gather
+    BP5_TRY(gather_components_finish(mf, n_components, ld, src));
+    BP5_TRY(components_apply_cells(mf, coef, n_components, ld, src, dst, mf->n_interior, mf->n_cells));   // cells that touch ghosts
+    BP5_TRY(scatter_components_start(mf, n_components, ld, dst, true));
+    BP5_TRY(components_apply_cells(mf, coef, n_components, ld, src, dst, half, mf->n_interior));          // under the scatter-add
+  }
+  BP5_TRY(scatter_components_finish(mf, n_components, ld, dst));
+  return zero_ghosts_components(mf, n_components, ld, src);
+}
+static bool components_exchange_needed(const bp5_mf *mf) { return mf->comm && !mf->neighbors.empty(); }
+extern "C" int bp5_apply_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, double *src, double *dst, int zero_dst)
+{
+  BP5_TRY(components_check(mf, coef, n_components, ld, src, dst, true));
+  HIP_TRY(hipSetDevice(mf->device));
+  if (components_exchange_needed(mf)) BP5_TRY(components_apply_exchanged(mf, coef, n_components, ld, src, dst, zero_dst != 0));
+  else BP5_TRY(components_apply(mf, coef, n_components, ld, src, dst, zero_dst != 0));
+  return components_copy_constrained(mf, n_components, ld, src, dst);
+}
+
 // ------------------------------------------------------------------------------------ events
 extern "C" int bp5_event_create(bp5_event **out)
 {
@@ -2350,17 +2557,20 @@ extern "C" int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, 
 
 // cg.solve(A, x, b, DiagonalMatrix) on a block vector: the BP5_CG_PLAIN recurrence of cg_solve_impl on the stacked system, one launch per
 // BLAS-1 step (component = second grid dimension), alpha / beta / the stop flag on the device
-extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
-                                       const bp5_cg_params *prm, bp5_cg_result *res)
+// with_exchange (bp5_cg_solve_components_distributed): a handle with a communicator and neighbours is taken, every operator application carries
+// the halo exchange (components_apply_exchanged) and d.h, g.g and g.z are all-reduced where the scalar plain solver all-reduces them
+static int cg_solve_components_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
+                                    const bp5_cg_params *prm, bp5_cg_result *res, bool with_exchange)
 {
   if (!b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
   if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return fail(BP5_ERR_INVALID, "unknown CG variant");
   if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
   if (diag && !aligned16(diag)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
-  BP5_TRY(components_check(mf, coef, n_components, ld, b, x));
+  BP5_TRY(components_check(mf, coef, n_components, ld, b, x, with_exchange));
   if (prm->variant == BP5_CG_MERGED) return fail(BP5_ERR_UNSUPPORTED, "block vectors: SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   HIP_TRY(hipSetDevice(mf->device));
   hipStream_t s = mf->stream;
+  const bool dist = with_exchange && components_exchange_needed(mf);
   const size_t need = 3 * (size_t)n_components * ld;
   if (mf->wsc_cap < need) {
     if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
@@ -2388,6 +2598,8 @@ extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_com
   // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381)
   hipLaunchKernelGGL(cgc_init_kernel, grid1, dim3(VB), 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
   hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, (const int *)nullptr);
+  KERNEL_CHECK();
+  if (with_exchange) BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
   hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
   KERNEL_CHECK();
   const int check = prm->check_every;
@@ -2395,15 +2607,18 @@ extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_com
     BP5_TRY(prof.mark(0));
     BP5_TRY(components_zero(mf, n_components, ld, h));
     BP5_TRY(prof.mark(1));
-    BP5_TRY(components_apply(mf, coef, n_components, ld, d, h, false));
+    if (dist) BP5_TRY(components_apply_exchanged(mf, coef, n_components, ld, d, h, false));
+    else BP5_TRY(components_apply(mf, coef, n_components, ld, d, h, false));
     BP5_TRY(prof.mark(2));
     BP5_TRY(components_copy_constrained(mf, n_components, ld, d, h));
     BP5_TRY(prof.mark(3));
     if (prof.on) prof.used += 4;
     hipLaunchKernelGGL(cgc_dot_kernel, grid2, dim3(VB), 0, s, d, h, n, ld, mf->d_partials, mf->d_st);
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, nblk2, mf->d_sc + SC_DH, mf->d_st);
+    if (with_exchange) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1)); }
     hipLaunchKernelGGL(cgc_update_kernel, grid2, dim3(VB), 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials);
     hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
+    if (with_exchange) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); }
     hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
     hipLaunchKernelGGL(cgc_direction_kernel, grid2, dim3(VB), 0, s, d, g, diag, n, ld, mf->d_sc, mf->d_st);
     KERNEL_CHECK();
@@ -2434,9 +2649,20 @@ extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_com
     res->apply_ms_avg = tot / (prof.used / 4);
     res->operator_ms_avg = tot_op / (prof.used / 4);
   }
+  res->exchange_schedule = !dist ? 0 : overlap_wanted(mf) ? 3 : 1;
   strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
   if (mf->h_st[ST_BREAKDOWN]) return fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
   return BP5_OK;
+}
+extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
+                                       const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  return cg_solve_components_impl(mf, coef, n_components, ld, diag, b, x, prm, res, false);
+}
+extern "C" int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b,
+                                                   double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  return cg_solve_components_impl(mf, coef, n_components, ld, diag, b, x, prm, res, true);
 }
 
 // ------------------------------------------------------------------------------------ CG with any preconditioner

@@ -114,6 +114,12 @@ struct bp5_mf {
   double *ws_z = nullptr;     // preconditioner output of bp5_cg_solve_preconditioned (allocated on first use)
   double *wsc_base = nullptr; // bp5_cg_solve_components: g, d, h as block vectors (3 n_components ld doubles), grown on demand
   size_t wsc_cap = 0;         // ... doubles allocated
+  // halo exchange of block vectors: four staging buffers in one allocation, grown on demand -- gather send / scatter receive (n_components
+  // send_off.back() doubles each), gather receive / scatter send (n_components n_ghost each); a neighbour's message is contiguous and holds
+  // all components, [neighbour][component][entry].  d_hc_off: send_off, then recv_off, for the kernels that place an entry in its message
+  double *hc_base = nullptr;
+  size_t hc_cap = 0;
+  uint32_t *d_hc_off = nullptr;
   // bp5_cg_solve_preconditioned with check_every = 0: the stop flag of iteration k copied to h_done[k % 3] behind ev_done[k % 3]
   int *h_done = nullptr; // pinned
   hipEvent_t ev_done[3] = {nullptr, nullptr, nullptr};
@@ -352,17 +358,17 @@ inline int launch_apply_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
   return BP5_OK;
 }
 
-// bp5_apply_components: all cells, every component through ONE pass over the metric planes and local_to_global (the caller has validated
-// the layout and zeroed dst where asked)
+// bp5_apply_components: cells [c0, c1) (non-empty), every component through ONE pass over the metric planes and local_to_global (the caller
+// has validated the layout and zeroed dst where asked; the phases of bp5_apply_components_distributed launch one range each)
 template <int P, bool COLL, int TW, int LPC, int TPB>
-inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
+inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1)
 {
   constexpr int n = P + 1;
   constexpr int CPT = 64 * TW / LPC;
   using L = LdsLayout<n, LPC>;
   ApplyArgs a = apply_args(mf, false, coef, src, dst);
-  a.cell_begin = 0; a.cell_end = mf->n_cells;
-  a.n_teams = (mf->n_cells + CPT - 1) / CPT;
+  a.cell_begin = c0; a.cell_end = c1;
+  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
   const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
   a.teams_per_xcd = (nblk + 7) / 8;
   ComponentArgs ca{(uint32_t)n_components, (uint64_t)ld};
@@ -376,12 +382,12 @@ inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_compo
 }
 // the degree's default pencil shape, both quadratures
 template <int DEG>
-int apply_components_degree_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst)
+int apply_components_degree_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1)
 {
   using DP = DefaultPencil<DEG>;
-  if (mf->n_cells == 0) return BP5_OK;
-  if (mf->quadrature == BP5_QUAD_GLL) return launch_apply_components_t<DEG, true, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst);
-  return launch_apply_components_t<DEG, false, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst);
+  if (c1 <= c0) return BP5_OK;
+  if (mf->quadrature == BP5_QUAD_GLL) return launch_apply_components_t<DEG, true, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst, c0, c1);
+  return launch_apply_components_t<DEG, false, DP::TW, DP::LPC, DP::TPB>(mf, coef, n_components, ld, src, dst, c0, c1);
 }
 
 // LDS bytes of one block-kernel workgroup: transpose tiles of the cell slots (two per slot where the cells span waves: BlockPass::PP),
@@ -1018,6 +1024,6 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
 #define BP5_EXTERN_DEGREE(N) extern template int apply_degree_impl<N>(bp5_mf *, ApplyCall &, const double *, const double *, double *);
 BP5_EXTERN_DEGREE(1) BP5_EXTERN_DEGREE(2) BP5_EXTERN_DEGREE(3) BP5_EXTERN_DEGREE(4) BP5_EXTERN_DEGREE(5) BP5_EXTERN_DEGREE(6) BP5_EXTERN_DEGREE(7) BP5_EXTERN_DEGREE(8)
 
-#define BP5_EXTERN_COMPONENTS_DEGREE(N) extern template int apply_components_degree_impl<N>(bp5_mf *, const double *, int, size_t, const double *, double *);
+#define BP5_EXTERN_COMPONENTS_DEGREE(N) extern template int apply_components_degree_impl<N>(bp5_mf *, const double *, int, size_t, const double *, double *, uint32_t, uint32_t);
 BP5_EXTERN_COMPONENTS_DEGREE(1) BP5_EXTERN_COMPONENTS_DEGREE(2) BP5_EXTERN_COMPONENTS_DEGREE(3) BP5_EXTERN_COMPONENTS_DEGREE(4)
 BP5_EXTERN_COMPONENTS_DEGREE(5) BP5_EXTERN_COMPONENTS_DEGREE(6) BP5_EXTERN_COMPONENTS_DEGREE(7) BP5_EXTERN_COMPONENTS_DEGREE(8)

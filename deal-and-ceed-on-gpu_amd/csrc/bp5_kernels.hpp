@@ -3371,6 +3371,50 @@ static __global__ void unpack_add_kernel(const uint32_t *idx, uint32_t n, const 
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) v[idx[i]] += buf[i]; // indices of one neighbour are distinct
 }
+// ---- the same for a block vector (component = blockIdx.y at + c ld): a neighbour's message holds ALL components, [neighbour][component][entry],
+// so one send and one receive per neighbour carry the block vector whatever n_components is, and both the staging buffer and the ghost ranges
+// are accessed with unit stride.  off: the n_nb + 1 message offsets of ONE component (send_off or recv_off); entry i of the flat range
+// [0, off[n_nb]) belongs to the neighbour k with off[k] <= i < off[k + 1] (zero-length neighbours are stepped over; n_nb is small)
+__device__ __forceinline__ size_t halo_message_pos(const uint32_t *off, uint32_t n_nb, uint32_t i, uint32_t c, uint32_t nc)
+{
+  uint32_t k = 0;
+  while (k + 1 < n_nb && i >= off[k + 1]) ++k;
+  const uint32_t o = off[k];
+  return (size_t)nc * o + (size_t)c * (off[k + 1] - o) + (i - o);
+}
+// gather direction, owner side: buf <- owned values through send_indices
+static __global__ void pack_components_kernel(const uint32_t *idx, const uint32_t *off, uint32_t n_nb, uint32_t n, const double *v, size_t ld, double *buf)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) buf[halo_message_pos(off, n_nb, i, blockIdx.y, gridDim.y)] = v[blockIdx.y * ld + idx[i]];
+}
+// gather direction, ghost side: ghost ranges <- the received messages (ghosts: v + n_owned)
+static __global__ void unpack_ghosts_components_kernel(const uint32_t *off, uint32_t n_nb, uint32_t n, const double *buf, double *ghosts, size_t ld)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ghosts[blockIdx.y * ld + i] = buf[halo_message_pos(off, n_nb, i, blockIdx.y, gridDim.y)];
+}
+// scatter direction, ghost side: buf <- ghost ranges, which are zeroed on the way (compress(add) leaves them zero; nothing reads them in between)
+static __global__ void pack_ghosts_components_kernel(const uint32_t *off, uint32_t n_nb, uint32_t n, double *ghosts, size_t ld, double *buf)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    double *g = ghosts + blockIdx.y * ld + i;
+    buf[halo_message_pos(off, n_nb, i, blockIdx.y, gridDim.y)] = *g;
+    *g = 0.0;
+  }
+}
+// scatter direction, owner side, ONE neighbour's message (n entries per component): its indices are distinct
+static __global__ void unpack_add_components_kernel(const uint32_t *idx, uint32_t n, const double *buf, double *v, size_t ld)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v[blockIdx.y * ld + idx[i]] += buf[(size_t)blockIdx.y * n + i];
+}
+static __global__ void zero_ghosts_components_kernel(double *ghosts, uint32_t n, size_t ld)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ghosts[blockIdx.y * ld + i] = 0.0;
+}
 
 // the same for a solve with fused dot products (SolverCGFullMerge on the block kernel): the operator's write-out has already
 // counted the LOCAL sums of these owner DoFs in v.v and r.v; adding the neighbour's contribution c changes them by

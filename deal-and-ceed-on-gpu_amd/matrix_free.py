@@ -18,7 +18,8 @@ device memory / streams / the process group only -- no torch op is on the hot pa
 
 Block vectors (deal.II BlockVector over one scalar DoFHandler; CEED BP6): a contiguous 2-D tensor of shape (n_components, ld), component c
 in row c laid out like a scalar vector, ld = n_local rounded up to even (initialize_block_vector).  PoissonOperator.vmult and
-SolverCG.solve take them (bp5_apply_components, bp5_cg_solve_components); everything else refuses them with status 5."""
+SolverCG.solve take them (bp5_apply_components, bp5_cg_solve_components; their *_distributed twins on more than one rank); everything else
+refuses them with status 5."""
 import ctypes as C
 
 import numpy as np
@@ -274,6 +275,22 @@ class MatrixFree:
     def set_constrained_values(self, value, dst):
         _lib.check(_lib.lib().bp5_set_constrained(self.handle, float(value), _ptr(dst, self.n_local)))
 
+    # -- halo exchange of a block vector (2-D tensor): one message per neighbour and direction, whatever n_components is
+    def update_ghost_values_block(self, v):
+        """== BlockVector::update_ghost_values()"""
+        nc, ld = _block_args(self, v)
+        _lib.check(_lib.lib().bp5_halo_gather_components(self.handle, nc, ld, _ptr(v)))
+
+    def compress_add_block(self, v):
+        """== BlockVector::compress(VectorOperation::add); ghosts zero afterwards"""
+        nc, ld = _block_args(self, v)
+        _lib.check(_lib.lib().bp5_halo_scatter_add_components(self.handle, nc, ld, _ptr(v)))
+
+    def zero_out_ghosts_block(self, v):
+        """== BlockVector::zero_out_ghosts()"""
+        nc, ld = _block_args(self, v)
+        _lib.check(_lib.lib().bp5_halo_zero_ghosts_components(self.handle, nc, ld, _ptr(v)))
+
     def get_data(self, color=0):
         d = _lib.MFData()
         _lib.check(_lib.lib().bp5_mf_get_data(self.handle, color, C.byref(d)))
@@ -308,12 +325,14 @@ class PoissonOperator:
 
     def vmult(self, dst, src):
         """dst = [0 +] A src; dst[c] = src[c] on Dirichlet DoFs (bp5/step-64.cu:263-276).  Block vectors (2-D tensors): the same on every
-        component with one pass over the metric (bp5_apply_components)."""
+        component with one pass over the metric (bp5_apply_components; on more than one rank bp5_apply_components_distributed, which
+        brings the halo exchange of the block vector)."""
         L, mf = _lib.lib(), self.mf_data
         dst, src = _vals(dst), _vals(src)
         if _is_block(dst) or _is_block(src):
             nc, ld = _block_args(mf, dst, src)
-            _lib.check(L.bp5_apply_components(mf.handle, _ptr(self.coef), nc, ld, _ptr(src), _ptr(dst), 1 if self.do_zero_out else 0))
+            fn = L.bp5_apply_components_distributed if self.distributed else L.bp5_apply_components
+            _lib.check(fn(mf.handle, _ptr(self.coef), nc, ld, _ptr(src), _ptr(dst), 1 if self.do_zero_out else 0))
             return
         fn = L.bp5_apply_distributed if self.distributed else L.bp5_apply
         _lib.check(fn(mf.handle, _ptr(self.coef), _ptr(src, mf.n_local), _ptr(dst, mf.n_local), 1 if self.do_zero_out else 0))
@@ -815,13 +834,13 @@ class _SolverBase:
         failure = []
         native = isinstance(A, PoissonOperator)
         if _is_block(x) or _is_block(b):
-            # the stacked system diag(A, ..., A) x = b: ONE Krylov space for all components (bp5_cg_solve_components)
+            # the stacked system diag(A, ..., A) x = b: ONE Krylov space for all components (bp5_cg_solve_components[_distributed])
             if self.variant != CG_PLAIN or general or not native:
                 raise BP5Error(5, "block vectors (2-D tensors): SolverCG on a PoissonOperator with None / DiagonalMatrix only")
             nc, ld = _block_args(mf, x, b)
             diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None
-            status = _lib.lib().bp5_cg_solve_components(mf.handle, _ptr(A.coef), nc, ld, _ptr(diag, mf.n_owned) if diag is not None else None,
-                                                        _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
+            fn = _lib.lib().bp5_cg_solve_components_distributed if A.distributed else _lib.lib().bp5_cg_solve_components
+            status = fn(mf.handle, _ptr(A.coef), nc, ld, _ptr(diag, mf.n_owned) if diag is not None else None, _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
         elif general:
             if isinstance(preconditioner, PreconditionChebyshev):
                 pfn, pctx = C.cast(_lib.lib().bp5_chebyshev_vmult, C.c_void_p), preconditioner.handle

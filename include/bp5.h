@@ -445,6 +445,31 @@ int bp5_mf_set_overlap(bp5_mf *mf, int mode);
  *    all cells, scatter-add on the handle's stream), which is what runs when the overlap policy says off. */
 int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src, double *dst, int zero_dst);
 
+/* The same on block vectors (layout as for bp5_apply_components: component c at v + c * ld, ld even and >= n_owned + n_ghost, base 16-byte
+ * aligned, entries [n_owned + n_ghost, ld) of a block never read, never written).  The ghost ranges of a block vector are n_components
+ * strided pieces, so every exchange goes through staging buffers of the handle (grown on demand) in which a neighbour's message is
+ * contiguous and holds all components, [neighbour][component][entry]: ONE send and ONE receive per neighbour and direction in one RCCL
+ * group, zero-length messages skipped; the number of launches and of RCCL calls does not depend on n_components.  Stream choice as for the
+ * scalar calls (bp5_mf_set_overlap).  Refused before any launch: the layout errors of bp5_apply_components (BP5_ERR_INVALID); a handle
+ * without neighbours is not an error (nothing to exchange).
+ * == BlockVector::update_ghost_values() (per block: src.update_ghost_values, bp5/step-64.cu:274): every block's ghost range receives
+ *    its owners' values */
+int bp5_halo_gather_components(bp5_mf *mf, int n_components, size_t ld, double *v);
+/* == BlockVector::compress(VectorOperation::add) (per block: dst.compress(add) inside cell_loop, bp5/step-64.cu:274): the ghost
+ *    contributions of every block are added to the owners' entries, neighbour after neighbour in the fixed order of bp5_halo_scatter_add
+ *    (bitwise reproducible); every block's ghost range is zero afterwards */
+int bp5_halo_scatter_add_components(bp5_mf *mf, int n_components, size_t ld, double *v);
+/* == BlockVector::zero_out_ghosts() [upstream; the reference's cell_loop leaves src without ghost values, bp5/step-64.cu:274] */
+int bp5_halo_zero_ghosts_components(bp5_mf *mf, int n_components, size_t ld, double *v);
+/* bp5_apply_distributed on every block == PoissonOperator::vmult on a BlockVector on more than one rank (bp5/step-64.cu:263-276; the
+ *    reference asserts n_components == 1: bp5/fe_evaluation_gl.h:137,165): ghosts of src gathered; apply_pencil_components_kernel over the
+ *    cells; dst scatter-added; ghosts of src zeroed again; Dirichlet copy on every block.  Overlap off, or auto below 1e6 interior cells:
+ *    unsplit, all on the handle's stream.  Overlap on: the three-phase schedule of bp5_apply_distributed for atomic kernels -- the gather
+ *    in flight under the first half of the interior cells, the cells that touch ghosts, the ghost contributions on their way under the
+ *    rest of the interior cells.  Refusals: those of bp5_apply_components except the communicator one; a handle without a communicator or
+ *    without neighbours does what bp5_apply_components does. */
+int bp5_apply_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, double *src, double *dst, int zero_dst);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Krylov solvers                                                                              */
 enum { BP5_CG_PLAIN = 0,  /* deal.II SolverCG (bp5/step-64.cu:446-453): the parity target      */
@@ -512,6 +537,14 @@ int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, const doubl
  * (known, not offered on block vectors) BP5_ERR_UNSUPPORTED.  The work vectors (3 n_components ld doubles) belong to the handle. */
 int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *inv_diag, const double *b, double *x,
                             const bp5_cg_params *params, bp5_cg_result *result_host);
+/* ... on more than one rank (cg.solve on a BlockVector with MPI, bp5/step-64.cu:446-453): the same recurrence, still ONE Krylov space,
+ * with the halo exchange inside every operator application (bp5_apply_components_distributed) and d.h, g.g and g.z all-reduced where
+ * bp5_cg_solve all-reduces them (replaces cudaMemcpy D2H + MPI_Allreduce, bp5/solver.h:488-494), the initial reduction included: every
+ * rank gets the same iteration count and residual.  Stop rule, check_every, breakdown status and result fields as on one rank;
+ * result->exchange_schedule is 1 (unsplit) or 3 (three-phase), 0 without neighbours.  Refusals as for bp5_cg_solve_components except the
+ * communicator one. */
+int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *inv_diag, const double *b,
+                                        double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
 
 /* BP5_CG_MERGED on the packed block kernel (cell bricks, one rank's cells, diag == NULL): by default the operator's
  * write-out and combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311: p.v, v.v, r.v, r.r)
