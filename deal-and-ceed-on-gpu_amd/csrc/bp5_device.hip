@@ -1096,6 +1096,8 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
   }
   return 56;
 }
+// the block kernel through launch_block_default: variant 56 at every degree that has one, at p = 4 also 63 (its sibling of the timing library)
+static bool is_default_block(const bp5_mf *mf, int ev) { return block_lpc(mf->degree) != 0 && (ev == 56 || (mf->degree == 4 && ev == 63)); }
 // kernels that define every entry of dst themselves (owner stores + combine pass) need no zero-fill
 static bool variant_overwrites(const bp5_mf *mf, int ev)
 {
@@ -1187,7 +1189,7 @@ static int components_check(const bp5_mf *mf, const double *coef, int n_componen
   if (mf->operator_kind != BP5_OP_POISSON) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the Helmholtz operator is not supported");
   if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "block vectors: meshes with hanging nodes are not supported");
   if (mf->geometry_mode != BP5_GEOM_MERGED6) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the affine geometry mode is not supported");
-  if (!with_exchange && mf->comm && !mf->neighbors.empty()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: no halo exchange (a handle with a communicator and neighbours)");
+  if (!with_exchange && mf->has_neighbors()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: no halo exchange (a handle with a communicator and neighbours)");
   if (!coef) return fail(BP5_ERR_INVALID, "null argument");
   return BP5_OK;
 }
@@ -1254,7 +1256,7 @@ extern "C" int bp5_assemble_rhs(bp5_mf *mf, double *b)
   HIP_TRY(hipSetDevice(mf->device));
   HIP_TRY(hipMemsetAsync(b, 0, mf->n_local() * sizeof(double), mf->stream));
   BP5_TRY(rhs_dispatch(mf, b));
-  if (mf->comm && !mf->neighbors.empty()) BP5_TRY(bp5_halo_scatter_add(mf, b));
+  if (mf->has_neighbors()) BP5_TRY(bp5_halo_scatter_add(mf, b));
   return bp5_set_constrained(mf, 0.0, b);
 }
 template <int n>
@@ -1285,7 +1287,7 @@ extern "C" int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag
   HIP_TRY(hipSetDevice(mf->device));
   HIP_TRY(hipMemsetAsync(diag, 0, mf->n_local() * sizeof(double), mf->stream));
   if (mf->n_cells) BP5_TRY(diagonal_dispatch(mf, coef, diag));
-  if (mf->comm && !mf->neighbors.empty()) { // ghost contributions to their owners
+  if (mf->has_neighbors()) { // ghost contributions to their owners
     BP5_TRY(bp5_halo_scatter_add(mf, diag));
     BP5_TRY(bp5_halo_zero_ghosts(mf, diag));
   }
@@ -1312,7 +1314,7 @@ extern "C" int bp5_l2_norm_solution(bp5_mf *mf, const double *u, double *result)
   HIP_TRY(hipSetDevice(mf->device));
   // the cell integrals read ghost DoFs through local_to_global: refresh them first, as the reference does on its ghosted copy
   // (ghost_solution_host, bp5/step-64.cu:602-616; deal.II's update_ghost_values() is const as well), and leave them zeroed
-  const bool ghosts = mf->comm && !mf->neighbors.empty();
+  const bool ghosts = mf->has_neighbors();
   if (ghosts) BP5_TRY(bp5_halo_gather(mf, const_cast<double *>(u)));
   HIP_TRY(hipMemsetAsync(mf->d_scalar, 0, sizeof(double), mf->stream));
   BP5_TRY(l2_dispatch(mf, u, mf->d_scalar));
@@ -1715,7 +1717,7 @@ struct ApplyPhases {
 static int phases_begin(bp5_mf *mf, double *dst, bool overwrite, ApplyCall &call, ApplyPhases &ph)
 {
   const int ev = effective_variant(mf, 0, mf->n_cells);
-  ph.block = ev < 100 && (ev % 100 == 56 || ev % 100 == 48 || ev % 100 == 49 || ev % 100 == 60 || ev % 100 == 61 || ev % 100 == 62 || ev % 100 == 63) && block_lpc(mf->degree) != 0 && (mf->degree == 4 || ev % 100 == 56);
+  ph.block = is_default_block(mf, ev) || (mf->degree == 4 && (ev == 48 || ev == 49 || (ev >= 60 && ev <= 62))); // (p = 4, which has a block kernel -- block_lpc(4) != 0 as is_default_block asks --: and the A/B siblings that run brick ranges)
   call.overwrite = false;
   if (ph.block) {
     BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &ph.dp));
@@ -1794,7 +1796,7 @@ extern "C" int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src
   if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst must differ");
   HIP_TRY(hipSetDevice(mf->device));
-  if (mf->comm && !mf->neighbors.empty()) {
+  if (mf->has_neighbors()) {
     ApplyCall call;
     BP5_TRY(apply_overlapped(mf, call, coef, src, dst, zero_dst != 0));
   } else BP5_TRY(launch_apply(mf, coef, src, dst, 0, mf->n_cells, zero_dst != 0));
@@ -1986,12 +1988,11 @@ static int components_apply_exchanged(bp5_mf *mf, const double *coef, int n_comp
   BP5_TRY(scatter_components_finish(mf, n_components, ld, dst));
   return zero_ghosts_components(mf, n_components, ld, src);
 }
-static bool components_exchange_needed(const bp5_mf *mf) { return mf->comm && !mf->neighbors.empty(); }
 extern "C" int bp5_apply_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, double *src, double *dst, int zero_dst)
 {
   BP5_TRY(components_check(mf, coef, n_components, ld, src, dst, true));
   HIP_TRY(hipSetDevice(mf->device));
-  if (components_exchange_needed(mf)) BP5_TRY(components_apply_exchanged(mf, coef, n_components, ld, src, dst, zero_dst != 0));
+  if (mf->has_neighbors()) BP5_TRY(components_apply_exchanged(mf, coef, n_components, ld, src, dst, zero_dst != 0));
   else BP5_TRY(components_apply(mf, coef, n_components, ld, src, dst, zero_dst != 0));
   return components_copy_constrained(mf, n_components, ld, src, dst);
 }
@@ -2226,7 +2227,7 @@ static int solver_vmult(bp5_mf *mf, SolveState &ss, const double *coef, double *
                         uint32_t *n_cols = nullptr)
 {
   ApplyProfile &prof = ss.prof;
-  const bool dist = mf->comm && !mf->neighbors.empty(); // halo exchange: whenever there are neighbours (tests: a self neighbour)
+  const bool dist = mf->has_neighbors(); // halo exchange: whenever there are neighbours (tests: a self neighbour)
   const bool fusing = n_cols != nullptr;
   if (dist && fusing) return fused_vmult_distributed(mf, ss, coef, src, dst, fuse_r, n_cols);
   ApplyCall call;
@@ -2273,230 +2274,38 @@ static int poll_state(bp5_mf *mf)
   return BP5_OK;
 }
 
-// cg.solve(A, x, b, preconditioner): the solvers need nothing of A but vmult (bp5/solver.h:25-30,377,475).  user == nullptr:
-// the built-in Poisson operator (coef); otherwise the caller's operator through its callback.
-// history != NULL (plain solve): alpha / beta of iteration k into history[2k], history[2k + 1] on the device, k < history_cap (Chebyshev estimate)
-static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void *user_ctx, const double *diag, const double *b, double *x,
-                         const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr, int history_cap = 0)
+// ---- what every solver shares: begin and finish (the refusals stay with the entry points: their order is part of each one's contract)
+// tolerance + iteration cap to the device, the bracketing events of a profiled solve, the start event
+static int solve_begin(bp5_mf *mf, const bp5_cg_params *prm, const ApplyProfile &prof)
 {
-  if (!mf || (!user && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
-  if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
-  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return fail(BP5_ERR_INVALID, "unknown CG variant");
-  if (!aligned16(b) || !aligned16(x) || (diag && !aligned16(diag))) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
-  HIP_TRY(hipSetDevice(mf->device));
-  BP5_TRY(ensure_ws(mf));
-  const size_t n = mf->n_owned;
-  const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1);
   hipStream_t s = mf->stream;
-  double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h;
-  SolveState ss{ApplyProfile{mf, prm->profile != 0}};
-  ApplyProfile &prof = ss.prof;
   if (prof.on) { // create the bracketing events before the timed region starts
     const size_t want = 4 * (size_t)std::min(prm->max_iter, ApplyProfile::MAX_PROFILED);
     while (mf->ev_pool.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->ev_pool.push_back(e); }
   }
-  ss.phase_on = prm->profile == 2 && prm->variant == BP5_CG_MERGED;
-  if (ss.phase_on) {
-    const size_t want = (size_t)bp5_mf::PhaseProfile::MAX_ITERS * bp5_mf::PhaseProfile::MARKS;
-    while (mf->phase.ev.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->phase.ev.push_back(e); }
-  }
-  const hipEvent_t ev0 = mf->ev_solve[0], ev1 = mf->ev_solve[1];
-  // h = A d.  dst is fully defined by the call (the reference zeroes it in update_a* for its atomic scatter)
-  auto vmult = [&](double *src, double *dst, const double *fuse_r, uint32_t *n_cols) -> int {
-    if (!user) return solver_vmult(mf, ss, coef, src, dst, true, fuse_r, n_cols);
-    BP5_TRY(prof.mark(0));
-    BP5_TRY(prof.mark(1));
-    const int st = user(user_ctx, dst, src);
-    if (st != BP5_OK) return fail(st, "the operator's vmult callback reported a failure");
-    BP5_TRY(prof.mark(2));
-    BP5_TRY(prof.mark(3));
-    if (prof.on) prof.used += 4;
-    return BP5_OK;
-  };
-  // scalars: tolerance + iteration cap
   mf->h_sc[SC_TOL] = prm->abs_tol;
   HIP_TRY(hipMemcpyAsync(mf->d_sc + SC_TOL, mf->h_sc + SC_TOL, sizeof(double), hipMemcpyHostToDevice, s));
   mf->h_st[ST_MAXIT] = prm->max_iter;
   HIP_TRY(hipMemcpyAsync(mf->d_st + ST_MAXIT, mf->h_st + ST_MAXIT, sizeof(int), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s)); // pinned staging words are reused below
-  HIP_TRY(hipEventRecord(ev0, s));
-  const bool plain = prm->variant == BP5_CG_PLAIN;
-  bool fused_dots = false;
-  const int check = prm->check_every;
-  int status = BP5_OK;
-  // fused dot products: whenever the operator resolves to the packed block kernel on all cells of one rank (merged solver: and D == 1;
-  // the plain solver takes only d.h = the quadrature-point energy from the kernel, which no preconditioner enters).
-  // Across ranks the fused iteration keeps its dot products in every exchange schedule (fused_vmult_distributed): unsplit (bp5_mf_set_overlap 0:
-  // gather, one launch, combine, scatter-add on the compute stream), boundary-first (1, the reference's setting: the ghost-touching
-  // bricks come first, their rows travel to the owners on the communication stream under the interior bricks), and the automatic
-  // choice (2): one launch, ghost rows combined first, the exchange under the owned-row combine.
-  const bool dist_solve = mf->comm && !mf->neighbors.empty();
-  bool split = false, split_possible = false, late = false;
-  if (!user && mf->cg_fusion && !mf->f32_metric() /* no fused build reads float planes */ && (plain || !diag) && block_lpc(mf->degree) != 0 && mf->geometry_mode == BP5_GEOM_MERGED6 &&
-      (effective_variant(mf, 0, mf->n_cells) == 56 || (mf->degree == 4 && effective_variant(mf, 0, mf->n_cells) == 63))) {
-    bp5_mf::DevPlan *dp = nullptr;
-    BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));
-    fused_dots = dp->packed && dp->covers_all && (dp->n_shared == 0 || dp->cr_tile);
-    if (fused_dots && dist_solve) {
-      uint32_t b0_, b1_;
-      const bool possible = !mf->h_block_off.empty() && (mf->n_interior == 0 || mf->n_interior == mf->n_cells || block_aligned(mf, 0, mf->n_interior, &b0_, &b1_));
-      split_possible = possible;
-      split = possible && mf->overlap == 1;
-      if (mf->overlap == 1 && !split) fused_dots = false; // explicit overlap on a mesh that cannot run boundary-first: 3-phase schedule, separate dot products
-      // automatic: one launch, ghost rows combined first, exchange under the owned-row combine (needs the run-length combine windows)
-      late = fused_dots && mf->overlap == 2 && (dp->n_shared == 0 || dp->cr_tile); // (variant 56 / 63: the run-length pass wherever its tables exist)
-    }
-  }
-  ss.exchange = split ? EXCHANGE_BOUNDARY_FIRST : late ? EXCHANGE_GHOST_ROWS_FIRST : EXCHANGE_NONE;
-  // whole-range launches of a distributed fused solve walk the ghost-touching bricks first in EITHER exchange schedule: same workgroup
-  // ranges, same dot-product columns -- the two schedules then differ only in where the exchange is enqueued and give the same bits
-  ss.two_parts = fused_dots && dist_solve && split_possible;
-  // one rank, separate dot-product kernel: the two small launches around an operator that scatters with atomics fold into their
-  // neighbours -- the update kernel stores the zeros the operator needs in h / v (it holds the values in registers for the last time),
-  // the dot-product kernel applies the Dirichlet copy while it reads both vectors (bitmap of the Dirichlet DoFs)
-  const bool fold_enabled = mf->tune[BP5_TUNE_FOLD_SMALL] != 0; // A/B knob of the handle
-  const bool fold_small = fold_enabled && !fused_dots && !user && !dist_solve;
-  const bool prezero = fold_small && mf->n_ghost == 0 && !variant_overwrites(mf, effective_variant(mf, 0, mf->n_cells)); // (the update kernels cover owned entries)
-  // (the operator then sits between a zero-storing update and a copying dot-product kernel; neither holds for a fused application)
-  ss.dst_prezeroed = prezero;
-  ss.copies_dirichlet = fold_small;
-
-  if (plain) {
-    // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381)
-    hipLaunchKernelGGL(cg_init_kernel, dim3(grid1), dim3(VB), 0, s, b, diag, x, g, d, n, mf->d_partials);
-    hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
-    KERNEL_CHECK();
-    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-    hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-    KERNEL_CHECK();
-    if (prezero) HIP_TRY(hipMemsetAsync(h, 0, mf->n_local() * sizeof(double), s)); // once: every later zero-fill is stored by cg_update_kernel
-    for (int it = 1; it <= prm->max_iter; ++it) {
-      if (fused_dots) { // d.h = sum over the cells of the quadrature-point energy (+ d^2 on Dirichlet rows, where h = d): row 0 of the fused sums
-        uint32_t n_cols = 0;
-        BP5_TRY(vmult(d, h, nullptr, &n_cols)); // (no residual vector: the write-out does not read g)
-        hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, (int)n_cols, mf->d_sc + SC_DH, mf->d_st);
-      } else {
-        BP5_TRY(vmult(d, h, nullptr, nullptr));
-        if (fold_small) hipLaunchKernelGGL(cg_dh_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_partials, (const uint32_t *)mf->d_constrained_bits);
-        else hipLaunchKernelGGL(dot_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_partials);
-        hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_DH, mf->d_st);
-      }
-      KERNEL_CHECK();
-      BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1));
-      hipLaunchKernelGGL(cg_update_kernel, dim3(grid2), dim3(VB), 0, s, x, g, d, h, diag, n, mf->d_sc, mf->d_st, mf->d_partials, prezero);
-      hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GG, mf->d_st);
-      KERNEL_CHECK();
-      BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-      hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-      if (history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, history, history_cap);
-      hipLaunchKernelGGL(cg_direction_kernel, dim3(stream_grid_flat(mf, n, 2)), dim3(VB), 0, s, d, g, diag, n, mf->d_sc, mf->d_st);
-      KERNEL_CHECK();
-      if (check > 0 && it % check == 0 && it < prm->max_iter) {
-        BP5_TRY(poll_state(mf));
-        if (mf->h_st[ST_DONE]) break;
-      }
-    }
-  } else {
-    // SolverCGFullMerge: g == r, d == p, h == v
-    // (v: the fused block kernel of a one-rank solve overwrites every entry before anything reads it; every other path keeps the zero-fill)
-    hipLaunchKernelGGL(cgm_init_kernel, dim3(grid1), dim3(VB), 0, s, b, x, g, d, h, diag, n, mf->d_partials, !(fused_dots && !dist_solve));
-    hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
-    KERNEL_CHECK();
-    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-    hipLaunchKernelGGL(cgm_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-    KERNEL_CHECK();
-    // update kernels: U chunks of 256 pairs per workgroup (flat launch: one trip per workgroup), all loads ahead of the first store.
-    // profiles/r4 hbm_sweep: U = 1 flat 5.5-5.9 TB/s, the capped grid-stride grid of rounds 1-3 (U = 4, 2048 workgroups) 4.8-4.9
-    const int unroll = mf->tune[BP5_TUNE_UPDATE_UNROLL];
-    const int gridu = stream_grid_flat(mf, n, 2 * unroll);
-    // v and x non-temporally: at every size since round 4 (-1 = on; profiles/r4 ab_update_*: 3.741 -> 3.707 ms per iteration at 1e8 DoFs with the flat
-    // launch, 0.4075 -> 0.4025 at 1e7; rounds 1-3 followed the streaming policy of the metric loads, which is off at 1e8 DoFs)
-    const bool streaming = mf->tune[BP5_TUNE_UPDATE_NT] != 0;
-    auto launch_update = [&](int mode) {
-#define BP5_UPD(M, U, ZV, NT) hipLaunchKernelGGL((cgm_update_kernel<M, U, ZV, NT>), dim3(gridu), dim3(VB), 0, s, d, g, h, x, diag, n, mf->d_sc, mf->d_st)
-#define BP5_UPD_U(M, ZV, NT) do { if (unroll == 1) BP5_UPD(M, 1, ZV, NT); else if (unroll == 2) BP5_UPD(M, 2, ZV, NT); else BP5_UPD(M, 4, ZV, NT); } while (0)
-      if (mode == 0) { BP5_UPD_U(0, false, false); return; }
-      if (prezero) { if (mode == 1) BP5_UPD_U(1, true, false); else BP5_UPD_U(2, true, false); return; }
-      if (streaming) { if (mode == 1) BP5_UPD_U(1, false, true); else BP5_UPD_U(2, false, true); return; }
-      if (mode == 1) BP5_UPD_U(1, false, false); else BP5_UPD_U(2, false, false);
-#undef BP5_UPD_U
-#undef BP5_UPD
-    };
-    const bool fused = fused_dots;
-    // fused iteration across ranks: the values of the NEW p at the DoFs this rank sends are computed into the send buffer first, so the
-    // ghost gather of p runs on the communication stream underneath the update kernel (which touches owned entries only); the operator
-    // then just waits for the event
-    const bool early_gather_enabled = mf->tune[BP5_TUNE_EARLY_GATHER] != 0; // A/B knob of the handle
-    const bool early_gather = fused && dist_solve && early_gather_enabled;
-    auto gather_under_update = [&](int mode) -> int {
-      BP5_TRY(halo_streams(mf));
-      const uint32_t ns = mf->send_off.back();
-      if (ns) {
-        const dim3 gr((ns + 255) / 256), bl(256);
-        if (mode == 0) hipLaunchKernelGGL(cgm_pack_updated_kernel<0>, gr, bl, 0, s, mf->d_send_idx, ns, d, g, h, diag, mf->d_sc, mf->d_st, mf->d_sendbuf);
-        else hipLaunchKernelGGL(cgm_pack_updated_kernel<1>, gr, bl, 0, s, mf->d_send_idx, ns, d, g, h, diag, mf->d_sc, mf->d_st, mf->d_sendbuf);
-        KERNEL_CHECK();
-      }
-      return gather_exchange(mf, d, true);
-    };
-    int it = 1;
-    for (; it <= prm->max_iter; ++it) {
-      const int mode = it == 1 ? 0 : it % 2 == 0 ? 1 : 2;
-      BP5_TRY(phase_mark(mf, ss, 0));
-      if (early_gather) { BP5_TRY(gather_under_update(mode)); ss.gather_in_flight = true; }
-      if (mode != 0) launch_update(mode); // (mode 0, p = -D r: written by cgm_init_kernel already)
-      KERNEL_CHECK();
-      BP5_TRY(phase_mark(mf, ss, 1));
-      const bool one_launch = fused && !mf->comm; // no all-reduce between the local sums and the scalar step
-      if (fused) {
-        uint32_t n_cols = 0;
-        BP5_TRY(vmult(d, h, g, &n_cols));
-        BP5_TRY(phase_mark(mf, ss, 4));
-        if (one_launch) hipLaunchKernelGGL(cgm_finalize4_kernel<true>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
-        else hipLaunchKernelGGL(cgm_finalize4_kernel<false>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
-      } else {
-        BP5_TRY(vmult(d, h, nullptr, nullptr)); // (h: zeroed by cgm_init_kernel before the first, by the update kernel before every later application)
-        BP5_TRY(phase_mark(mf, ss, 4));
-        hipLaunchKernelGGL(cgm_dots_kernel, dim3(grid2), dim3(VB), 0, s, d, g, h, diag, n, mf->d_st, mf->d_partials,
-                           fold_small ? (const uint32_t *)mf->d_constrained_bits : (const uint32_t *)nullptr);
-        hipLaunchKernelGGL(finalize_kernel<7>, dim3(7), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_R0, mf->d_st);
-      }
-      KERNEL_CHECK();
-      BP5_TRY(phase_mark(mf, ss, 5));
-      if (!one_launch) {
-        BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_R0, 7));
-        BP5_TRY(phase_mark(mf, ss, 6));
-        hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-        KERNEL_CHECK();
-      } else
-        BP5_TRY(phase_mark(mf, ss, 6));
-      BP5_TRY(phase_mark(mf, ss, 7));
-      if (ss.phase_on) ++ss.phase_it;
-      if (check > 0 && it % check == 0 && it < prm->max_iter) {
-        BP5_TRY(poll_state(mf));
-        if (mf->h_st[ST_DONE]) break;
-      }
-    }
-    // epilogue x update (solver.h:510-526) runs inside the next update kernel; with max_iter == 0 no
-    // iteration has been done and nothing is pending
-    if (prm->max_iter > 0) {
-      launch_update(1);
-      hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-      KERNEL_CHECK();
-    }
-  }
-  HIP_TRY(hipEventRecord(ev1, s));
+  HIP_TRY(hipEventRecord(mf->ev_solve[0], s));
+  return BP5_OK;
+}
+// end event, the device's state to the host, the result (phase_ms: zero, the merged solver fills it in); returns the breakdown status
+static int solve_finish(bp5_mf *mf, const ApplyProfile &prof, bool fused_dots, int exchange_schedule, bool own_operator, bp5_cg_result *res)
+{
+  HIP_TRY(hipEventRecord(mf->ev_solve[1], mf->stream));
   BP5_TRY(poll_state(mf));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, mf->ev_solve[0], mf->ev_solve[1]));
+  memset(res, 0, sizeof(*res));
   res->iterations = mf->h_st[ST_ITER];
   res->residual = mf->h_sc[SC_RES];
   res->initial_residual = mf->h_sc[SC_RES0];
   res->solve_ms = ms;
-  res->apply_ms_avg = res->operator_ms_avg = 0.0;
   res->apply_launches = prof.used / 4;
   res->dot_products_fused = fused_dots ? 1 : 0;
-  res->exchange_schedule = !dist_solve ? 0 : split ? 2 : late ? 4 : fused_dots ? 1 : overlap_wanted(mf) ? 3 : 1;
+  res->exchange_schedule = exchange_schedule;
   if (prof.on && prof.used) {
     double tot = 0.0, tot_op = 0.0;
     for (int k = 0; k < prof.used; k += 4) {
@@ -2509,38 +2318,370 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
     res->apply_ms_avg = tot / (prof.used / 4);
     res->operator_ms_avg = tot_op / (prof.used / 4);
   }
-  memset(res->apply_kernel, 0, sizeof(res->apply_kernel));
-  if (!user) strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
-  for (double &v : res->phase_ms) v = 0.0;
-  if (ss.phase_on) { // averages over the stamped iterations after the first (whose update kernel is the cheap update_a0)
-    using PP = bp5_mf::PhaseProfile;
-    const int n_it = std::min(ss.phase_it, (int)PP::MAX_ITERS);
-    int counted = 0;
-    for (int i = n_it > 1 ? 1 : 0; i < n_it; ++i) {
-      const uint8_t rec = ss.phase_recorded[i];
-      const uint8_t need = (1u << 0) | (1u << 1) | (1u << 4) | (1u << 5) | (1u << 6) | (1u << 7);
-      if ((rec & need) != need) continue;
-      auto ms = [&](int a, int b, double &out) -> int {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, mf->phase.ev[(size_t)i * PP::MARKS + a], mf->phase.ev[(size_t)i * PP::MARKS + b]));
-        out += t;
-        return BP5_OK;
-      };
-      const bool g = rec & (1u << 2), x = rec & (1u << 3);
-      BP5_TRY(ms(0, 1, res->phase_ms[BP5_PHASE_UPDATE]));
-      if (g) BP5_TRY(ms(1, 2, res->phase_ms[BP5_PHASE_GATHER_WAIT]));
-      BP5_TRY(ms(g ? 2 : 1, x ? 3 : 4, res->phase_ms[BP5_PHASE_OPERATOR]));
-      if (x) BP5_TRY(ms(3, 4, res->phase_ms[BP5_PHASE_EXCHANGE]));
-      BP5_TRY(ms(4, 5, res->phase_ms[BP5_PHASE_REDUCE]));
-      BP5_TRY(ms(5, 6, res->phase_ms[BP5_PHASE_ALLREDUCE]));
-      BP5_TRY(ms(6, 7, res->phase_ms[BP5_PHASE_CONTROL]));
-      BP5_TRY(ms(0, 7, res->phase_ms[BP5_PHASE_ITERATION]));
-      ++counted;
+  if (own_operator) strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
+  if (mf->h_st[ST_BREAKDOWN]) return fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
+  return BP5_OK;
+}
+
+// dst = A src through the caller's callback, bracketed like an operator launch
+static int user_vmult(ApplyProfile &prof, bp5_vmult_fn user, void *user_ctx, double *src, double *dst)
+{
+  BP5_TRY(prof.mark(0));
+  BP5_TRY(prof.mark(1));
+  const int st = user(user_ctx, dst, src);
+  if (st != BP5_OK) return fail(st, "the operator's vmult callback reported a failure");
+  BP5_TRY(prof.mark(2));
+  BP5_TRY(prof.mark(3));
+  if (prof.on) prof.used += 4;
+  return BP5_OK;
+}
+
+// What a solve on scalar vectors decides once about its operator applications (the defaults: what a solve takes that asks for none of it)
+struct OperatorPlan {
+  bool dist = false;       // halo exchange inside every application
+  bool fused_dots = false; // the operator kernels form the dot products with its result
+  bool fold_small = false; // the dot-product kernel applies the Dirichlet copy ...
+  bool prezero = false;    // ... and the update kernel stores the zeros an atomic scatter needs
+  int schedule = 0;        // bp5_cg_result.exchange_schedule
+};
+// own_operator: the library's operator, not a callback.  fusable: no preconditioner enters the dot products the kernel would form
+static int plan_operator(bp5_mf *mf, bool own_operator, bool fusable, SolveState &ss, OperatorPlan &op)
+{
+  // fused dot products: whenever the operator resolves to the packed block kernel on all cells of one rank (merged solver: and D == 1;
+  // the plain solver takes only d.h = the quadrature-point energy from the kernel, which no preconditioner enters).
+  // Across ranks the fused iteration keeps its dot products in every exchange schedule (fused_vmult_distributed): unsplit (bp5_mf_set_overlap 0:
+  // gather, one launch, combine, scatter-add on the compute stream), boundary-first (1, the reference's setting: the ghost-touching
+  // bricks come first, their rows travel to the owners on the communication stream under the interior bricks), and the automatic
+  // choice (2): one launch, ghost rows combined first, the exchange under the owned-row combine.
+  op.dist = mf->has_neighbors();
+  bool split = false, split_possible = false, late = false;
+  if (own_operator && mf->cg_fusion && !mf->f32_metric() /* no fused build reads float planes */ && fusable && mf->geometry_mode == BP5_GEOM_MERGED6 &&
+      is_default_block(mf, effective_variant(mf, 0, mf->n_cells))) {
+    bp5_mf::DevPlan *dp = nullptr;
+    BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));
+    op.fused_dots = dp->packed && dp->covers_all && (dp->n_shared == 0 || dp->cr_tile);
+    if (op.fused_dots && op.dist) {
+      uint32_t b0_, b1_;
+      split_possible = !mf->h_block_off.empty() && (mf->n_interior == 0 || mf->n_interior == mf->n_cells || block_aligned(mf, 0, mf->n_interior, &b0_, &b1_));
+      split = split_possible && mf->overlap == 1;
+      if (mf->overlap == 1 && !split) op.fused_dots = false; // explicit overlap on a mesh that cannot run boundary-first: 3-phase schedule, separate dot products
+      // automatic: one launch, ghost rows combined first, exchange under the owned-row combine (needs the run-length combine windows)
+      late = op.fused_dots && mf->overlap == 2 && (dp->n_shared == 0 || dp->cr_tile); // (variant 56 / 63: the run-length pass wherever its tables exist)
     }
-    if (counted) for (double &v : res->phase_ms) v /= counted;
   }
-  if (mf->h_st[ST_BREAKDOWN]) status = fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
+  ss.exchange = split ? EXCHANGE_BOUNDARY_FIRST : late ? EXCHANGE_GHOST_ROWS_FIRST : EXCHANGE_NONE;
+  // whole-range launches of a distributed fused solve walk the ghost-touching bricks first in EITHER exchange schedule: same workgroup
+  // ranges, same dot-product columns -- the two schedules then differ only in where the exchange is enqueued and give the same bits
+  ss.two_parts = op.fused_dots && op.dist && split_possible;
+  // one rank, separate dot-product kernel: the two small launches around an operator that scatters with atomics fold into their
+  // neighbours -- the update kernel stores the zeros the operator needs in h / v (it holds the values in registers for the last time),
+  // the dot-product kernel applies the Dirichlet copy while it reads both vectors (bitmap of the Dirichlet DoFs)
+  const bool fold_enabled = mf->tune[BP5_TUNE_FOLD_SMALL] != 0; // A/B knob of the handle
+  op.fold_small = fold_enabled && !op.fused_dots && own_operator && !op.dist;
+  op.prezero = op.fold_small && mf->n_ghost == 0 && !variant_overwrites(mf, effective_variant(mf, 0, mf->n_cells)); // (the update kernels cover owned entries)
+  // (the operator then sits between a zero-storing update and a copying dot-product kernel; neither holds for a fused application)
+  ss.dst_prezeroed = op.prezero;
+  ss.copies_dirichlet = op.fold_small;
+  op.schedule = !op.dist ? 0 : split ? 2 : late ? 4 : op.fused_dots ? 1 : overlap_wanted(mf) ? 3 : 1;
+  return BP5_OK;
+}
+
+// ---- the plain recurrence (deal.II SolverCG): ONE driver for scalar vectors, block vectors and any preconditioner.  Its entry points have
+// checked their arguments and made the work vectors; they describe the solve by this struct
+struct PlainCG {
+  // vectors: n_components blocks ld apart (a scalar vector: one block) and the workspace triple g, d, h
+  int n_components = 1;
+  size_t ld = 0;
+  double *g = nullptr, *d = nullptr, *h = nullptr;
+  // operator: the library's (coef) or the caller's callback (scalar vectors); block: the block-vector application, with the halo exchange or without
+  const double *coef = nullptr;
+  bp5_vmult_fn user = nullptr;
+  void *user_ctx = nullptr;
+  bool block = false, exchange = false;
+  // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g (scalar vectors)
+  const double *diag = nullptr;
+  bp5_vmult_fn precond = nullptr;
+  void *precond_ctx = nullptr;
+  double *z = nullptr;
+  bool allreduce = true; // d.h, g.g and g.z summed over the ranks (block vectors without exchange: no)
+  // alpha / beta of iteration k into history[2k], history[2k + 1] on the device, k < history_cap (Chebyshev estimate)
+  double *history = nullptr;
+  int history_cap = 0;
+};
+// Per iteration: h = A d, d.h, x += alpha d, g += alpha h, [z = P g,] g.g and g.Dg (g.z) in ONE all-reduce, the scalar step, d = beta d - D g (z).
+// Every kernel is gated on the device-side stop flag.  A callback preconditioner is not (the host does not know the flag before it looks), it
+// writes only z and its own work vectors, and z is not read once the solve has stopped: the same bits for every check_every.
+static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  hipStream_t s = mf->stream;
+  const size_t n = mf->n_owned, ld = cg.ld;
+  const int nc = cg.n_components;
+  double *g = cg.g, *d = cg.d, *h = cg.h, *z = cg.z;
+  const double *diag = cg.diag;
+  // launch geometry: the component is the second grid dimension and owns PARTIAL_STRIDE / n_components columns of a partial-sum row (a scalar
+  // vector: all of them, stream_grid never asks for more).  Scalar vectors launch the direction kernel, which reduces nothing, flat
+  const int cols = PARTIAL_STRIDE / nc;
+  const dim3 grid1(std::min(stream_grid(n, 1), cols), nc), grid2(std::min(stream_grid(n, 2), cols), nc), block(VB);
+  const dim3 gridd = cg.block ? grid2 : dim3(stream_grid_flat(mf, n, 2));
+  const int nblk1 = (int)grid1.x * nc, nblk2 = (int)grid2.x * nc;
+  const int *no_flag = nullptr; // (the stop flag is the last solve's until the control step of the initialisation)
+  SolveState ss{ApplyProfile{mf, prm->profile != 0 && !cg.precond}}; // (a callback preconditioner: the applications are not bracketed)
+  ApplyProfile &prof = ss.prof;
+  BP5_TRY(solve_begin(mf, prm, prof)); // (the plan below may build the block kernel's tables on a handle's first solve: inside solve_ms)
+  OperatorPlan op;
+  if (!cg.block && !cg.precond) BP5_TRY(plan_operator(mf, !cg.user, true, ss, op));
+  else op.schedule = cg.user || !mf->has_neighbors() ? 0 : overlap_wanted(mf) ? 3 : 1;
+  // h = A d, Dirichlet rows included (unless the dot-product kernel copies them).  Fused dot products: d.h lies in *n_cols columns of d_partials
+  auto apply_A = [&](uint32_t *n_cols) -> int {
+    if (cg.user) return user_vmult(prof, cg.user, cg.user_ctx, d, h);
+    if (!cg.block) return solver_vmult(mf, ss, cg.coef, d, h, true, nullptr, op.fused_dots ? n_cols : nullptr); // (no residual vector: the write-out does not read g)
+    BP5_TRY(prof.mark(0));
+    BP5_TRY(components_zero(mf, nc, ld, h));
+    BP5_TRY(prof.mark(1));
+    if (cg.exchange) BP5_TRY(components_apply_exchanged(mf, cg.coef, nc, ld, d, h, false));
+    else BP5_TRY(components_apply(mf, cg.coef, nc, ld, d, h, false));
+    BP5_TRY(prof.mark(2));
+    BP5_TRY(components_copy_constrained(mf, nc, ld, d, h));
+    BP5_TRY(prof.mark(3));
+    if (prof.on) prof.used += 4;
+    return BP5_OK;
+  };
+  auto apply_P = [&]() -> int {
+    const int st = cg.precond(cg.precond_ctx, z, g);
+    return st == BP5_OK ? BP5_OK : fail(st, "the preconditioner's vmult callback reported a failure");
+  };
+  // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381); a callback: z = P g and d = -z behind the control step
+  if (cg.precond) {
+    hipLaunchKernelGGL(cg_init_kernel<false>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
+    KERNEL_CHECK();
+    BP5_TRY(apply_P());
+    hipLaunchKernelGGL(dot_kernel, grid2, block, 0, s, g, z, n, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, no_flag);
+  } else {
+    hipLaunchKernelGGL(cg_init_kernel<true>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
+    hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
+  }
+  KERNEL_CHECK();
+  if (cg.allreduce) BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
+  hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res0, gh = g.Dg (g.z), stop test
+  if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, true>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st);
+  KERNEL_CHECK();
+  if (op.prezero) HIP_TRY(hipMemsetAsync(h, 0, mf->n_local() * sizeof(double), s)); // once: every later zero-fill is stored by cg_update_kernel
+  const int check = prm->check_every;
+  // check_every = 0 with a callback preconditioner: the operator and the preconditioner are not gated on the stop flag (a preconditioner is any
+  // callback), so the host looks at the flag itself -- with a lag of DONE_LAG iterations (the copy of iteration k's flag is waited for after iteration
+  // k + DONE_LAG has been enqueued): the queue never drains, and at most DONE_LAG iterations run on a stopped solve, whose kernels leave x, g, d alone
+  constexpr int DONE_LAG = 2;
+  const bool lagged_look = cg.precond && check <= 0;
+  if (lagged_look) {
+    if (!mf->h_done) HIP_TRY(hipHostMalloc((void **)&mf->h_done, (DONE_LAG + 1) * sizeof(int)));
+    for (hipEvent_t &e : mf->ev_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  for (int it = 1; it <= prm->max_iter; ++it) {
+    uint32_t n_cols = 0;
+    BP5_TRY(apply_A(&n_cols));
+    if (op.fused_dots) // d.h = sum over the cells of the quadrature-point energy (+ d^2 on Dirichlet rows, where h = d): row 0 of the fused sums
+      hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, (int)n_cols, mf->d_sc + SC_DH, mf->d_st);
+    else {
+      if (op.fold_small) hipLaunchKernelGGL(cg_dh_kernel<true>, grid2, block, 0, s, d, h, n, ld, mf->d_partials, mf->d_st, (const uint32_t *)mf->d_constrained_bits);
+      else hipLaunchKernelGGL(cg_dh_kernel<false>, grid2, block, 0, s, d, h, n, ld, mf->d_partials, mf->d_st, (const uint32_t *)nullptr);
+      hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_DH, mf->d_st);
+    }
+    if (cg.allreduce) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1)); }
+    if (cg.precond) {
+      hipLaunchKernelGGL(cg_update_kernel<false>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, false);
+      hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
+      KERNEL_CHECK();
+      BP5_TRY(apply_P()); // (the sum g.g is in SC_GG already: the preconditioner may run reductions of its own)
+      hipLaunchKernelGGL(cg_dh_kernel<false>, grid2, block, 0, s, g, z, n, ld, mf->d_partials, mf->d_st, (const uint32_t *)nullptr);
+      hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, mf->d_st);
+    } else {
+      hipLaunchKernelGGL(cg_update_kernel<true>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, op.prezero);
+      hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
+    }
+    if (cg.allreduce) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); } // g.g, g.Dg (g.z)
+    hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res, ++it, stop test, beta
+    if (cg.history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, cg.history, cg.history_cap);
+    if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, false>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st);
+    else hipLaunchKernelGGL((cg_direction_kernel<false, false>), gridd, block, 0, s, d, g, diag, n, ld, mf->d_sc, mf->d_st);
+    KERNEL_CHECK();
+    if (check > 0 && it % check == 0 && it < prm->max_iter) {
+      BP5_TRY(poll_state(mf));
+      if (mf->h_st[ST_DONE]) break;
+    } else if (lagged_look && it < prm->max_iter) {
+      const int slot = it % (DONE_LAG + 1);
+      HIP_TRY(hipMemcpyAsync(mf->h_done + slot, mf->d_st + ST_DONE, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipEventRecord(mf->ev_done[slot], s));
+      if (it > DONE_LAG) {
+        const int seen = (it - DONE_LAG) % (DONE_LAG + 1);
+        HIP_TRY(hipEventSynchronize(mf->ev_done[seen]));
+        if (mf->h_done[seen]) break;
+      }
+    }
+  }
+  return solve_finish(mf, prof, op.fused_dots, op.schedule, !cg.user, res);
+}
+
+// ---- SolverCGFullMerge on scalar vectors (bp5/solver.h:343-542): g == r, d == p, h == v
+static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void *user_ctx, const double *diag, const double *b, double *x,
+                           const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  const size_t n = mf->n_owned;
+  const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1);
+  hipStream_t s = mf->stream;
+  double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h;
+  SolveState ss{ApplyProfile{mf, prm->profile != 0}};
+  ss.phase_on = prm->profile == 2;
+  if (ss.phase_on) {
+    const size_t want = (size_t)bp5_mf::PhaseProfile::MAX_ITERS * bp5_mf::PhaseProfile::MARKS;
+    while (mf->phase.ev.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->phase.ev.push_back(e); }
+  }
+  BP5_TRY(solve_begin(mf, prm, ss.prof)); // (the plan below may build the block kernel's tables on a handle's first solve: inside solve_ms)
+  OperatorPlan op;
+  BP5_TRY(plan_operator(mf, !user, !diag, ss, op));
+  const bool fused = op.fused_dots, dist_solve = op.dist, fold_small = op.fold_small, prezero = op.prezero;
+  // h = A d.  dst is fully defined by the call (the reference zeroes it in update_a* for its atomic scatter)
+  auto vmult = [&](double *src, double *dst, const double *fuse_r, uint32_t *n_cols) -> int {
+    if (!user) return solver_vmult(mf, ss, coef, src, dst, true, fuse_r, n_cols);
+    return user_vmult(ss.prof, user, user_ctx, src, dst);
+  };
+  const int check = prm->check_every;
+  // (v: the fused block kernel of a one-rank solve overwrites every entry before anything reads it; every other path keeps the zero-fill)
+  hipLaunchKernelGGL(cgm_init_kernel, dim3(grid1), dim3(VB), 0, s, b, x, g, d, h, diag, n, mf->d_partials, !(fused && !dist_solve));
+  hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
+  KERNEL_CHECK();
+  BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
+  hipLaunchKernelGGL(cgm_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+  KERNEL_CHECK();
+  // update kernels: U chunks of 256 pairs per workgroup (flat launch: one trip per workgroup), all loads ahead of the first store.
+  // profiles/r4 hbm_sweep: U = 1 flat 5.5-5.9 TB/s, the capped grid-stride grid of rounds 1-3 (U = 4, 2048 workgroups) 4.8-4.9
+  const int unroll = mf->tune[BP5_TUNE_UPDATE_UNROLL];
+  const int gridu = stream_grid_flat(mf, n, 2 * unroll);
+  // v and x non-temporally: at every size since round 4 (-1 = on; profiles/r4 ab_update_*: 3.741 -> 3.707 ms per iteration at 1e8 DoFs with the flat
+  // launch, 0.4075 -> 0.4025 at 1e7; rounds 1-3 followed the streaming policy of the metric loads, which is off at 1e8 DoFs)
+  const bool streaming = mf->tune[BP5_TUNE_UPDATE_NT] != 0;
+  auto launch_update = [&](int mode) {
+#define BP5_UPD(M, U, ZV, NT) hipLaunchKernelGGL((cgm_update_kernel<M, U, ZV, NT>), dim3(gridu), dim3(VB), 0, s, d, g, h, x, diag, n, mf->d_sc, mf->d_st)
+#define BP5_UPD_U(M, ZV, NT) do { if (unroll == 1) BP5_UPD(M, 1, ZV, NT); else if (unroll == 2) BP5_UPD(M, 2, ZV, NT); else BP5_UPD(M, 4, ZV, NT); } while (0)
+    if (mode == 0) { BP5_UPD_U(0, false, false); return; }
+    if (prezero) { if (mode == 1) BP5_UPD_U(1, true, false); else BP5_UPD_U(2, true, false); return; }
+    if (streaming) { if (mode == 1) BP5_UPD_U(1, false, true); else BP5_UPD_U(2, false, true); return; }
+    if (mode == 1) BP5_UPD_U(1, false, false); else BP5_UPD_U(2, false, false);
+#undef BP5_UPD_U
+#undef BP5_UPD
+  };
+  // fused iteration across ranks: the values of the NEW p at the DoFs this rank sends are computed into the send buffer first, so the
+  // ghost gather of p runs on the communication stream underneath the update kernel (which touches owned entries only); the operator
+  // then just waits for the event
+  const bool early_gather_enabled = mf->tune[BP5_TUNE_EARLY_GATHER] != 0; // A/B knob of the handle
+  const bool early_gather = fused && dist_solve && early_gather_enabled;
+  auto gather_under_update = [&](int mode) -> int {
+    BP5_TRY(halo_streams(mf));
+    const uint32_t ns = mf->send_off.back();
+    if (ns) {
+      const dim3 gr((ns + 255) / 256), bl(256);
+      if (mode == 0) hipLaunchKernelGGL(cgm_pack_updated_kernel<0>, gr, bl, 0, s, mf->d_send_idx, ns, d, g, h, diag, mf->d_sc, mf->d_st, mf->d_sendbuf);
+      else hipLaunchKernelGGL(cgm_pack_updated_kernel<1>, gr, bl, 0, s, mf->d_send_idx, ns, d, g, h, diag, mf->d_sc, mf->d_st, mf->d_sendbuf);
+      KERNEL_CHECK();
+    }
+    return gather_exchange(mf, d, true);
+  };
+  int it = 1;
+  for (; it <= prm->max_iter; ++it) {
+    const int mode = it == 1 ? 0 : it % 2 == 0 ? 1 : 2;
+    BP5_TRY(phase_mark(mf, ss, 0));
+    if (early_gather) { BP5_TRY(gather_under_update(mode)); ss.gather_in_flight = true; }
+    if (mode != 0) launch_update(mode); // (mode 0, p = -D r: written by cgm_init_kernel already)
+    KERNEL_CHECK();
+    BP5_TRY(phase_mark(mf, ss, 1));
+    const bool one_launch = fused && !mf->comm; // no all-reduce between the local sums and the scalar step
+    if (fused) {
+      uint32_t n_cols = 0;
+      BP5_TRY(vmult(d, h, g, &n_cols));
+      BP5_TRY(phase_mark(mf, ss, 4));
+      if (one_launch) hipLaunchKernelGGL(cgm_finalize4_kernel<true>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
+      else hipLaunchKernelGGL(cgm_finalize4_kernel<false>, dim3(1), dim3(FIN4_THREADS), 0, s, mf->d_partials, (int)n_cols, mf->d_sc, mf->d_st);
+    } else {
+      BP5_TRY(vmult(d, h, nullptr, nullptr)); // (h: zeroed by cgm_init_kernel before the first, by the update kernel before every later application)
+      BP5_TRY(phase_mark(mf, ss, 4));
+      hipLaunchKernelGGL(cgm_dots_kernel, dim3(grid2), dim3(VB), 0, s, d, g, h, diag, n, mf->d_st, mf->d_partials,
+                         fold_small ? (const uint32_t *)mf->d_constrained_bits : (const uint32_t *)nullptr);
+      hipLaunchKernelGGL(finalize_kernel<7>, dim3(7), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_R0, mf->d_st);
+    }
+    KERNEL_CHECK();
+    BP5_TRY(phase_mark(mf, ss, 5));
+    if (!one_launch) {
+      BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_R0, 7));
+      BP5_TRY(phase_mark(mf, ss, 6));
+      hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+      KERNEL_CHECK();
+    } else
+      BP5_TRY(phase_mark(mf, ss, 6));
+    BP5_TRY(phase_mark(mf, ss, 7));
+    if (ss.phase_on) ++ss.phase_it;
+    if (check > 0 && it % check == 0 && it < prm->max_iter) {
+      BP5_TRY(poll_state(mf));
+      if (mf->h_st[ST_DONE]) break;
+    }
+  }
+  // epilogue x update (solver.h:510-526) runs inside the next update kernel; with max_iter == 0 no
+  // iteration has been done and nothing is pending
+  if (prm->max_iter > 0) {
+    launch_update(1);
+    hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+    KERNEL_CHECK();
+  }
+  const int status = solve_finish(mf, ss.prof, fused, op.schedule, !user, res);
+  if (!ss.phase_on || (status != BP5_OK && status != BP5_ERR_BREAKDOWN)) return status;
+  // averages over the stamped iterations after the first (whose update kernel is the cheap update_a0)
+  using PP = bp5_mf::PhaseProfile;
+  const int n_it = std::min(ss.phase_it, (int)PP::MAX_ITERS);
+  int counted = 0;
+  for (int i = n_it > 1 ? 1 : 0; i < n_it; ++i) {
+    const uint8_t rec = ss.phase_recorded[i];
+    const uint8_t need = (1u << 0) | (1u << 1) | (1u << 4) | (1u << 5) | (1u << 6) | (1u << 7);
+    if ((rec & need) != need) continue;
+    auto ms = [&](int a, int b, double &out) -> int {
+      float t = 0.f;
+      HIP_TRY(hipEventElapsedTime(&t, mf->phase.ev[(size_t)i * PP::MARKS + a], mf->phase.ev[(size_t)i * PP::MARKS + b]));
+      out += t;
+      return BP5_OK;
+    };
+    const bool g = rec & (1u << 2), x = rec & (1u << 3);
+    BP5_TRY(ms(0, 1, res->phase_ms[BP5_PHASE_UPDATE]));
+    if (g) BP5_TRY(ms(1, 2, res->phase_ms[BP5_PHASE_GATHER_WAIT]));
+    BP5_TRY(ms(g ? 2 : 1, x ? 3 : 4, res->phase_ms[BP5_PHASE_OPERATOR]));
+    if (x) BP5_TRY(ms(3, 4, res->phase_ms[BP5_PHASE_EXCHANGE]));
+    BP5_TRY(ms(4, 5, res->phase_ms[BP5_PHASE_REDUCE]));
+    BP5_TRY(ms(5, 6, res->phase_ms[BP5_PHASE_ALLREDUCE]));
+    BP5_TRY(ms(6, 7, res->phase_ms[BP5_PHASE_CONTROL]));
+    BP5_TRY(ms(0, 7, res->phase_ms[BP5_PHASE_ITERATION]));
+    ++counted;
+  }
+  if (counted) for (double &v : res->phase_ms) v /= counted;
   return status;
+}
+
+// cg.solve(A, x, b, preconditioner) on scalar vectors with a diagonal: the solvers need nothing of A but vmult (bp5/solver.h:25-30,377,475).
+// user == nullptr: the built-in Poisson operator (coef); otherwise the caller's operator through its callback.
+// history != NULL (plain solve): the Lanczos coefficients for the Chebyshev estimate (PlainCG::history)
+static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void *user_ctx, const double *diag, const double *b, double *x,
+                         const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr, int history_cap = 0)
+{
+  if (!mf || (!user && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
+  if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
+  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return fail(BP5_ERR_INVALID, "unknown CG variant");
+  if (!aligned16(b) || !aligned16(x) || (diag && !aligned16(diag))) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(mf->device));
+  BP5_TRY(ensure_ws(mf));
+  if (prm->variant == BP5_CG_MERGED) return cg_solve_merged(mf, coef, user, user_ctx, diag, b, x, prm, res);
+  PlainCG cg;
+  cg.g = mf->ws_g; cg.d = mf->ws_d; cg.h = mf->ws_h;
+  cg.coef = coef; cg.user = user; cg.user_ctx = user_ctx;
+  cg.diag = diag;
+  cg.history = history; cg.history_cap = history_cap;
+  return cg_solve_plain(mf, cg, b, x, prm, res);
 }
 
 extern "C" int bp5_cg_solve(bp5_mf *mf, const double *coef, const double *diag, const double *b, double *x, const bp5_cg_params *prm,
@@ -2555,8 +2696,7 @@ extern "C" int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, 
   return cg_solve_impl(mf, nullptr, vmult, ctx, diag, b, x, prm, res);
 }
 
-// cg.solve(A, x, b, DiagonalMatrix) on a block vector: the BP5_CG_PLAIN recurrence of cg_solve_impl on the stacked system, one launch per
-// BLAS-1 step (component = second grid dimension), alpha / beta / the stop flag on the device
+// cg.solve(A, x, b, DiagonalMatrix) on a block vector: the plain recurrence on the stacked system, one launch per BLAS-1 step
 // with_exchange (bp5_cg_solve_components_distributed): a handle with a communicator and neighbours is taken, every operator application carries
 // the halo exchange (components_apply_exchanged) and d.h, g.g and g.z are all-reduced where the scalar plain solver all-reduces them
 static int cg_solve_components_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
@@ -2569,90 +2709,20 @@ static int cg_solve_components_impl(bp5_mf *mf, const double *coef, int n_compon
   BP5_TRY(components_check(mf, coef, n_components, ld, b, x, with_exchange));
   if (prm->variant == BP5_CG_MERGED) return fail(BP5_ERR_UNSUPPORTED, "block vectors: SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   HIP_TRY(hipSetDevice(mf->device));
-  hipStream_t s = mf->stream;
-  const bool dist = with_exchange && components_exchange_needed(mf);
   const size_t need = 3 * (size_t)n_components * ld;
   if (mf->wsc_cap < need) {
-    if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(s)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
+    if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
     HIP_TRY(hipMalloc((void **)&mf->wsc_base, need * sizeof(double)));
     mf->wsc_cap = need;
   }
-  HIP_TRY(hipMemsetAsync(mf->wsc_base, 0, need * sizeof(double), s)); // ghost entries of d are read by the operator: defined, zero
-  double *g = mf->wsc_base, *d = g + (size_t)n_components * ld, *h = d + (size_t)n_components * ld;
-  const size_t n = mf->n_owned;
-  const int cols = PARTIAL_STRIDE / n_components; // the component's columns of a partial-sum row
-  const dim3 grid2(std::min(stream_grid(n, 2), cols), n_components), grid1(std::min(stream_grid(n, 1), cols), n_components);
-  const int nblk2 = (int)grid2.x * n_components, nblk1 = (int)grid1.x * n_components;
-  ApplyProfile prof{mf, prm->profile != 0};
-  if (prof.on) {
-    const size_t want = 4 * (size_t)std::min(prm->max_iter, ApplyProfile::MAX_PROFILED);
-    while (mf->ev_pool.size() < want) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); mf->ev_pool.push_back(e); }
-  }
-  const hipEvent_t ev0 = mf->ev_solve[0], ev1 = mf->ev_solve[1];
-  mf->h_sc[SC_TOL] = prm->abs_tol;
-  HIP_TRY(hipMemcpyAsync(mf->d_sc + SC_TOL, mf->h_sc + SC_TOL, sizeof(double), hipMemcpyHostToDevice, s));
-  mf->h_st[ST_MAXIT] = prm->max_iter;
-  HIP_TRY(hipMemcpyAsync(mf->d_st + ST_MAXIT, mf->h_st + ST_MAXIT, sizeof(int), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s)); // pinned staging words are reused below
-  HIP_TRY(hipEventRecord(ev0, s));
-  // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381)
-  hipLaunchKernelGGL(cgc_init_kernel, grid1, dim3(VB), 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
-  hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, (const int *)nullptr);
-  KERNEL_CHECK();
-  if (with_exchange) BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-  hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-  KERNEL_CHECK();
-  const int check = prm->check_every;
-  for (int it = 1; it <= prm->max_iter; ++it) {
-    BP5_TRY(prof.mark(0));
-    BP5_TRY(components_zero(mf, n_components, ld, h));
-    BP5_TRY(prof.mark(1));
-    if (dist) BP5_TRY(components_apply_exchanged(mf, coef, n_components, ld, d, h, false));
-    else BP5_TRY(components_apply(mf, coef, n_components, ld, d, h, false));
-    BP5_TRY(prof.mark(2));
-    BP5_TRY(components_copy_constrained(mf, n_components, ld, d, h));
-    BP5_TRY(prof.mark(3));
-    if (prof.on) prof.used += 4;
-    hipLaunchKernelGGL(cgc_dot_kernel, grid2, dim3(VB), 0, s, d, h, n, ld, mf->d_partials, mf->d_st);
-    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, nblk2, mf->d_sc + SC_DH, mf->d_st);
-    if (with_exchange) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1)); }
-    hipLaunchKernelGGL(cgc_update_kernel, grid2, dim3(VB), 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials);
-    hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
-    if (with_exchange) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); }
-    hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-    hipLaunchKernelGGL(cgc_direction_kernel, grid2, dim3(VB), 0, s, d, g, diag, n, ld, mf->d_sc, mf->d_st);
-    KERNEL_CHECK();
-    if (check > 0 && it % check == 0 && it < prm->max_iter) {
-      BP5_TRY(poll_state(mf));
-      if (mf->h_st[ST_DONE]) break;
-    }
-  }
-  HIP_TRY(hipEventRecord(ev1, s));
-  BP5_TRY(poll_state(mf));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-  memset(res, 0, sizeof(*res));
-  res->iterations = mf->h_st[ST_ITER];
-  res->residual = mf->h_sc[SC_RES];
-  res->initial_residual = mf->h_sc[SC_RES0];
-  res->solve_ms = ms;
-  res->apply_launches = prof.used / 4;
-  if (prof.on && prof.used) {
-    double tot = 0.0, tot_op = 0.0;
-    for (int k = 0; k < prof.used; k += 4) {
-      float t = 0.f;
-      HIP_TRY(hipEventElapsedTime(&t, mf->ev_pool[k + 1], mf->ev_pool[k + 2]));
-      tot += t;
-      HIP_TRY(hipEventElapsedTime(&t, mf->ev_pool[k], mf->ev_pool[k + 3]));
-      tot_op += t;
-    }
-    res->apply_ms_avg = tot / (prof.used / 4);
-    res->operator_ms_avg = tot_op / (prof.used / 4);
-  }
-  res->exchange_schedule = !dist ? 0 : overlap_wanted(mf) ? 3 : 1;
-  strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
-  if (mf->h_st[ST_BREAKDOWN]) return fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
-  return BP5_OK;
+  HIP_TRY(hipMemsetAsync(mf->wsc_base, 0, need * sizeof(double), mf->stream)); // ghost entries of d are read by the operator: defined, zero
+  PlainCG cg;
+  cg.n_components = n_components; cg.ld = ld;
+  cg.g = mf->wsc_base; cg.d = cg.g + (size_t)n_components * ld; cg.h = cg.d + (size_t)n_components * ld;
+  cg.coef = coef; cg.block = true; cg.exchange = with_exchange && mf->has_neighbors();
+  cg.diag = diag;
+  cg.allreduce = with_exchange;
+  return cg_solve_plain(mf, cg, b, x, prm, res);
 }
 extern "C" int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
                                        const bp5_cg_params *prm, bp5_cg_result *res)
@@ -2665,10 +2735,7 @@ extern "C" int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coe
   return cg_solve_components_impl(mf, coef, n_components, ld, diag, b, x, prm, res, true);
 }
 
-// ------------------------------------------------------------------------------------ CG with any preconditioner
-// cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of
-// D g.  Every kernel is gated on the device-side stop flag; the preconditioner itself is not (the host does not know the flag before it
-// looks), it writes only z and its own work vectors, and z is not read once the solve has stopped: the same bits for every check_every.
+// cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of D g
 extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, bp5_vmult_fn precond, void *precond_ctx,
                                            const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
@@ -2682,93 +2749,11 @@ extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_v
     HIP_TRY(hipMalloc((void **)&mf->ws_z, std::max<size_t>(mf->n_local(), 2) * sizeof(double)));
     HIP_TRY(hipMemsetAsync(mf->ws_z, 0, std::max<size_t>(mf->n_local(), 2) * sizeof(double), mf->stream));
   }
-  const size_t n = mf->n_owned;
-  const int grid2 = stream_grid(n, 2), grid1 = stream_grid(n, 1), gridf = stream_grid_flat(mf, n, 2);
-  hipStream_t s = mf->stream;
-  double *g = mf->ws_g, *d = mf->ws_d, *h = mf->ws_h, *z = mf->ws_z;
-  SolveState ss{ApplyProfile{mf, false}};
-  auto apply_A = [&](double *src, double *dst) -> int {
-    if (!vmult) return solver_vmult(mf, ss, coef, src, dst, true);
-    const int st = vmult(ctx, dst, src);
-    return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
-  };
-  auto apply_P = [&](double *src, double *dst) -> int {
-    const int st = precond(precond_ctx, dst, src);
-    return st == BP5_OK ? BP5_OK : fail(st, "the preconditioner's vmult callback reported a failure");
-  };
-  mf->h_sc[SC_TOL] = prm->abs_tol;
-  HIP_TRY(hipMemcpyAsync(mf->d_sc + SC_TOL, mf->h_sc + SC_TOL, sizeof(double), hipMemcpyHostToDevice, s));
-  mf->h_st[ST_MAXIT] = prm->max_iter;
-  HIP_TRY(hipMemcpyAsync(mf->d_st + ST_MAXIT, mf->h_st + ST_MAXIT, sizeof(int), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s)); // pinned staging words are reused below
-  const hipEvent_t ev0 = mf->ev_solve[0], ev1 = mf->ev_solve[1];
-  HIP_TRY(hipEventRecord(ev0, s));
-  // g = -b, x = 0; z = P g; g.g and g.z in one all-reduce; res0, gh = g.z, stop test; d = -z
-  hipLaunchKernelGGL(pcg_init_kernel, dim3(grid1), dim3(VB), 0, s, b, x, g, n, mf->d_partials);
-  hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
-  KERNEL_CHECK();
-  BP5_TRY(apply_P(g, z));
-  hipLaunchKernelGGL(dot_kernel, dim3(grid2), dim3(VB), 0, s, g, z, n, mf->d_partials);
-  hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GDG, (const int *)nullptr);
-  KERNEL_CHECK();
-  BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-  hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
-  hipLaunchKernelGGL(pcg_direction_kernel<true>, dim3(gridf), dim3(VB), 0, s, d, z, n, mf->d_sc, mf->d_st);
-  KERNEL_CHECK();
-  const int check = prm->check_every;
-  // check_every = 0: the operator and the preconditioner are not gated on the stop flag (a preconditioner is any callback), so the host
-  // looks at the flag itself -- with a lag of DONE_LAG iterations (the copy of iteration k's flag is waited for after iteration k + DONE_LAG
-  // has been enqueued): the queue never drains, and at most DONE_LAG iterations run on a stopped solve, whose kernels leave x, g, d alone
-  constexpr int DONE_LAG = 2;
-  if (check <= 0) {
-    if (!mf->h_done) HIP_TRY(hipHostMalloc((void **)&mf->h_done, (DONE_LAG + 1) * sizeof(int)));
-    for (hipEvent_t &e : mf->ev_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  for (int it = 1; it <= prm->max_iter; ++it) {
-    BP5_TRY(apply_A(d, h));
-    hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid2), dim3(VB), 0, s, d, h, n, mf->d_st, mf->d_partials);
-    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_DH, mf->d_st);
-    KERNEL_CHECK();
-    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1));
-    hipLaunchKernelGGL(pcg_update_kernel, dim3(grid2), dim3(VB), 0, s, x, g, d, h, n, mf->d_sc, mf->d_st, mf->d_partials);
-    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GG, mf->d_st);
-    KERNEL_CHECK();
-    BP5_TRY(apply_P(g, z)); // (the partial sums of g.g are in SC_GG already: the preconditioner may run reductions of its own)
-    hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid2), dim3(VB), 0, s, g, z, n, mf->d_st, mf->d_partials);
-    hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), dim3(VB), 0, s, mf->d_partials, grid2, mf->d_sc + SC_GDG, mf->d_st);
-    KERNEL_CHECK();
-    BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); // g.g, g.z
-    hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res, ++it, stop test, beta = g.z / gh
-    hipLaunchKernelGGL(pcg_direction_kernel<false>, dim3(gridf), dim3(VB), 0, s, d, z, n, mf->d_sc, mf->d_st);
-    KERNEL_CHECK();
-    if (check > 0 && it % check == 0 && it < prm->max_iter) {
-      BP5_TRY(poll_state(mf));
-      if (mf->h_st[ST_DONE]) break;
-    } else if (check <= 0 && it < prm->max_iter) {
-      const int slot = it % (DONE_LAG + 1);
-      HIP_TRY(hipMemcpyAsync(mf->h_done + slot, mf->d_st + ST_DONE, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipEventRecord(mf->ev_done[slot], s));
-      if (it > DONE_LAG) {
-        const int seen = (it - DONE_LAG) % (DONE_LAG + 1);
-        HIP_TRY(hipEventSynchronize(mf->ev_done[seen]));
-        if (mf->h_done[seen]) break;
-      }
-    }
-  }
-  HIP_TRY(hipEventRecord(ev1, s));
-  BP5_TRY(poll_state(mf));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-  memset(res, 0, sizeof(*res));
-  res->iterations = mf->h_st[ST_ITER];
-  res->residual = mf->h_sc[SC_RES];
-  res->initial_residual = mf->h_sc[SC_RES0];
-  res->solve_ms = ms;
-  const bool dist_solve = mf->comm && !mf->neighbors.empty();
-  res->exchange_schedule = !dist_solve || vmult ? 0 : overlap_wanted(mf) ? 3 : 1;
-  if (!vmult) strncpy(res->apply_kernel, mf->last_apply_kernel, sizeof(res->apply_kernel) - 1);
-  if (mf->h_st[ST_BREAKDOWN]) return fail(BP5_ERR_BREAKDOWN, "CG breakdown: p.Ap is zero or NaN");
-  return BP5_OK;
+  PlainCG cg;
+  cg.g = mf->ws_g; cg.d = mf->ws_d; cg.h = mf->ws_h;
+  cg.coef = coef; cg.user = vmult; cg.user_ctx = ctx;
+  cg.precond = precond; cg.precond_ctx = precond_ctx; cg.z = mf->ws_z;
+  return cg_solve_plain(mf, cg, b, x, prm, res);
 }
 
 // ------------------------------------------------------------------------------------ PreconditionChebyshev
@@ -2793,7 +2778,7 @@ static int cheb_apply(bp5_chebyshev *c, double *x, double *t)
     return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
   }
   bp5_mf *mf = c->mf;
-  if (mf->comm && !mf->neighbors.empty()) return bp5_apply_distributed(mf, c->coef, x, t, 1);
+  if (mf->has_neighbors()) return bp5_apply_distributed(mf, c->coef, x, t, 1);
   return bp5_apply(mf, c->coef, x, t, 1);
 }
 
@@ -3055,7 +3040,6 @@ static int mg_combine(bp5_mg_transfer *t, double *dst, bool add)
   KERNEL_CHECK();
   return BP5_OK;
 }
-static bool mg_distributed(const bp5_mf *mf) { return mf->comm && !mf->neighbors.empty(); }
 
 // the CSR of each coarse local DoF's slots, ascending (= cell order): slot_dof[s] the coarse DoF slot s adds to (MG_NO_DOF: none)
 static int mg_upload_slot_csr(bp5_mg_transfer *t, const std::vector<uint32_t> &slot_dof)
@@ -3098,7 +3082,7 @@ static int mg_setup_fine_side(bp5_mg_transfer *t)
     if (!written[g]) return fail(BP5_ERR_INVALID, "multigrid transfer: an owned fine DoF lies in none of the rank's cells");
   BP5_TRY(upload(&t->d_wmask, wmask.data(), wmask.size()));
   BP5_TRY(upload(&t->d_w, count.data(), count.size()));
-  if (mg_distributed(fine)) { // the counts of all ranks: ghost counts to their owners, the totals back to the ghosts
+  if (fine->has_neighbors()) { // the counts of all ranks: ghost counts to their owners, the totals back to the ghosts
     BP5_TRY(bp5_halo_scatter_add(fine, t->d_w));
     BP5_TRY(bp5_halo_gather(fine, t->d_w));
   }
@@ -3266,7 +3250,7 @@ extern "C" int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst, d
 {
   if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(t->fine->device));
-  if (mg_distributed(t->coarse)) BP5_TRY(bp5_halo_gather(t->coarse, src));
+  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_gather(t->coarse, src));
   return mg_prolongate_dispatch(t, dst, src);
 }
 
@@ -3275,13 +3259,13 @@ extern "C" int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst, d
 static int mg_restrict(bp5_mg_transfer *t, double *dst, double *b, double *tv, bool add)
 {
   HIP_TRY(hipSetDevice(t->fine->device));
-  if (mg_distributed(t->fine)) {
+  if (t->fine->has_neighbors()) {
     BP5_TRY(bp5_halo_gather(t->fine, b));
     if (tv) BP5_TRY(bp5_halo_gather(t->fine, tv));
   }
   BP5_TRY(mg_restrict_dispatch(t, b, tv));
   BP5_TRY(mg_combine(t, dst, add));
-  if (mg_distributed(t->coarse)) BP5_TRY(bp5_halo_scatter_add(t->coarse, dst));
+  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_scatter_add(t->coarse, dst));
   return BP5_OK;
 }
 extern "C" int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst, double *src)
@@ -3393,7 +3377,7 @@ static int mg_level(bp5_mg *mg, int l, double *x, double *b)
   if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
   bp5_mf *mf = mg->mf[l];
   BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                      // pre-smoothing from zero
-  if (mg_distributed(mf)) BP5_TRY(bp5_apply_distributed(mf, mg->coef[l], x, mg->t[l], 1));
+  if (mf->has_neighbors()) BP5_TRY(bp5_apply_distributed(mf, mg->coef[l], x, mg->t[l], 1));
   else BP5_TRY(bp5_apply(mf, mg->coef[l], x, mg->t[l], 1));             // t = A x
   BP5_TRY(mg_restrict(mg->tr[l], mg->b[l + 1], b, mg->t[l], false));   // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
   BP5_TRY(mg_level(mg, l + 1, mg->x[l + 1], mg->b[l + 1]));

@@ -173,6 +173,7 @@ struct bp5_mf {
   std::map<int, DevMarch> march_plans; // keyed by cells per team
   std::map<int, DevPlan> plans;
   size_t n_local() const { return (size_t)n_owned + n_ghost; }
+  bool has_neighbors() const { return comm && !neighbors.empty(); } // operator applications carry the halo exchange (tests: a self neighbour)
 };
 
 // Fused CG dot products (SolverCGFullMerge on the block kernel) of ONE operator application: the solver owns it, the launches advance it

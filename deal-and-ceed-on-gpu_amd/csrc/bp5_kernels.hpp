@@ -3534,31 +3534,6 @@ static __global__ void __launch_bounds__(VB) dot_kernel(const double *x, const d
   block_reduce_store<1>(acc, partials);
 }
 
-// d.h of the standard solver with copy_constrained_values applied on the fly (h = d on the Dirichlet DoFs of the bitmap, stored)
-static __global__ void __launch_bounds__(VB) cg_dh_kernel(const double *d, double *h, size_t n, double *partials, const uint32_t *cbits)
-{
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    const uint32_t cb = (cbits[i >> 5] >> (i & 31)) & 3u;
-    if (i + 1 < n) {
-      const double2 a = *reinterpret_cast<const double2 *>(d + i);
-      double2 b = *reinterpret_cast<const double2 *>(h + i);
-      if (cb) {
-        if (cb & 1u) b.x = a.x;
-        if (cb & 2u) b.y = a.y;
-        *reinterpret_cast<double2 *>(h + i) = b;
-      }
-      acc[0] += a.x * b.x + a.y * b.y;
-    } else {
-      double b = h[i];
-      if (cb & 1u) { b = d[i]; h[i] = b; }
-      acc[0] += d[i] * b;
-    }
-  }
-  block_reduce_store<1>(acc, partials);
-}
-
 // number of nonzero (or NaN) entries, as a double so that it travels through the same reduction / all-reduce
 static __global__ void __launch_bounds__(VB) count_nonzero_kernel(const double *x, size_t n, double *partials)
 {
@@ -3574,19 +3549,39 @@ enum { SC_GH = 0, SC_DH, SC_GG, SC_GDG, SC_ALPHA, SC_BETA, SC_ALPHA_OLD, SC_BETA
        SC_COUNT = SC_R0 + 7 };
 enum { ST_DONE = 0, ST_ITER, ST_PENDING, ST_MAXIT, ST_BREAKDOWN, ST_COUNT };
 
-// ---- plain CG (deal.II SolverCG, Appendix A.5)
-// init: g = -b ; d = b (= -D g with D = 1) ; x = 0 ; partial sums of g.g and g.Dg
-static __global__ void __launch_bounds__(VB) cg_init_kernel(const double *b, const double *diag, double *x, double *g, double *d,
-                                                    size_t n, double *partials)
+// Dirichlet copy of a block vector: dst = src on the constrained DoFs of every block (component = blockIdx.y, blocks ld apart)
+static __global__ void copy_constrained_components_kernel(const uint32_t *cdofs, uint32_t n, const double *src, double *dst, size_t ld)
 {
-  double acc[2] = {0.0, 0.0};
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { const size_t c = cdofs[i] + blockIdx.y * ld; dst[c] = src[c]; }
+}
+
+// ---- plain CG (deal.II SolverCG, Appendix A.5): ONE kernel set for scalar vectors, block vectors and any preconditioner.
+// Component c = blockIdx.y works on the block at + c ld; its partial sums land in columns [c gridDim.x, (c + 1) gridDim.x) of the rows, so the
+// finalize pass sums block-wise partials, components in order (fixed order).  A scalar solve is one component: gridDim.y == 1, column 0.
+// diag is per scalar DoF, shared by the components.
+// GDG: the preconditioner is the diagonal (NULL == 1) and the kernel also forms g.Dg; false: z = P g comes from a callback, g.g alone
+// init: g = -b ; x = 0 ; partial sums of g.g   GDG: and d = b (= -D g with D = 1), partial sums of g.Dg
+template <bool GDG>
+__global__ void __launch_bounds__(VB) cg_init_kernel(const double *b, const double *diag, double *x, double *g, double *d, size_t n, size_t ld,
+                                                     double *partials)
+{
+  const size_t o = blockIdx.y * ld;
+  b += o; x += o; g += o; d += o;
+  double acc[GDG ? 2 : 1] = {};
   const size_t stride = (size_t)gridDim.x * VB;
   for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
-    const double gi = -b[i], hi = diag ? diag[i] * gi : gi;
-    x[i] = 0.0; g[i] = gi; d[i] = -hi;
-    acc[0] += gi * gi; acc[1] += gi * hi;
+    if constexpr (GDG) {
+      const double gi = -b[i], hi = diag ? diag[i] * gi : gi;
+      x[i] = 0.0; g[i] = gi; d[i] = -hi;
+      acc[0] += gi * gi; acc[1] += gi * hi;
+    } else {
+      const double gi = -b[i];
+      x[i] = 0.0; g[i] = gi;
+      acc[0] += gi * gi;
+    }
   }
-  block_reduce_store<2>(acc, partials);
+  block_reduce_store<GDG ? 2 : 1>(acc, partials + blockIdx.y * gridDim.x);
 }
 // after init: res0 = sqrt(gg); gh = gDg; done if res0 <= tol
 static __global__ void cg_init_control_kernel(double *sc, int *st)
@@ -3596,15 +3591,54 @@ static __global__ void cg_init_control_kernel(double *sc, int *st)
   st[ST_ITER] = 0; st[ST_PENDING] = 0; st[ST_BREAKDOWN] = 0;
   st[ST_DONE] = (sc[SC_RES] <= sc[SC_TOL]) ? 1 : 0;
 }
-// x += alpha d ; g += alpha h ; partial sums g.g, g.Dg   with alpha = gh / dh
-// zero_h: h is consumed here for the last time before the next operator application; an operator that scatters with atomics needs
-// it zeroed, so this kernel stores the zeros (see cgm_update_kernel<.., ZV>)
-static __global__ void __launch_bounds__(VB) cg_update_kernel(double *x, double *g, const double *d, double *h, const double *diag,
-                                                      size_t n, const double *sc, const int *st, double *partials, bool zero_h)
+// partial sums of d.h; a stopped solve leaves the partials alone (finalize_kernel is gated on the same flag)
+// COPY: copy_constrained_values applied on the fly (h = d on the Dirichlet DoFs of the bitmap, stored; scalar vectors)
+template <bool COPY>
+__global__ void __launch_bounds__(VB) cg_dh_kernel(const double *d, double *h, size_t n, size_t ld, double *partials, const int *st, const uint32_t *cbits)
 {
   if (st[ST_DONE]) return;
+  d += blockIdx.y * ld; h += blockIdx.y * ld;
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if constexpr (COPY) {
+      const uint32_t cb = (cbits[i >> 5] >> (i & 31)) & 3u;
+      if (i + 1 < n) {
+        const double2 a = *reinterpret_cast<const double2 *>(d + i);
+        double2 b = *reinterpret_cast<double2 *>(h + i);
+        if (cb) {
+          if (cb & 1u) b.x = a.x;
+          if (cb & 2u) b.y = a.y;
+          *reinterpret_cast<double2 *>(h + i) = b;
+        }
+        acc[0] += a.x * b.x + a.y * b.y;
+      } else {
+        double b = h[i];
+        if (cb & 1u) { b = d[i]; h[i] = b; }
+        acc[0] += d[i] * b;
+      }
+    } else {
+      if (i + 1 < n) {
+        const double2 a = *reinterpret_cast<const double2 *>(d + i), b = *reinterpret_cast<const double2 *>(h + i);
+        acc[0] += a.x * b.x + a.y * b.y;
+      } else
+        acc[0] += d[i] * h[i];
+    }
+  }
+  block_reduce_store<1>(acc, partials + blockIdx.y * gridDim.x);
+}
+// x += alpha d ; g += alpha h ; partial sums g.g (GDG: and g.Dg)   with alpha = gh / dh
+// zero_h: h is consumed here for the last time before the next operator application; an operator that scatters with atomics needs
+// it zeroed, so this kernel stores the zeros (see cgm_update_kernel<.., ZV>)
+template <bool GDG>
+__global__ void __launch_bounds__(VB) cg_update_kernel(double *x, double *g, const double *d, double *h, const double *diag, size_t n, size_t ld,
+                                                       const double *sc, const int *st, double *partials, bool zero_h)
+{
+  if (st[ST_DONE]) return;
+  const size_t o = blockIdx.y * ld;
+  x += o; g += o; d += o; h += o;
   const double alpha = sc[SC_GH] / sc[SC_DH];
-  double acc[2] = {0.0, 0.0};
+  double acc[GDG ? 2 : 1] = {};
   const size_t stride = (size_t)gridDim.x * VB * 2;
   for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
     if (i + 1 < n) {
@@ -3615,17 +3649,20 @@ static __global__ void __launch_bounds__(VB) cg_update_kernel(double *x, double 
       *reinterpret_cast<double2 *>(x + i) = xv;
       *reinterpret_cast<double2 *>(g + i) = gv;
       if (zero_h) *reinterpret_cast<double2 *>(h + i) = double2{0.0, 0.0};
-      const double z0 = diag ? diag[i] * gv.x : gv.x, z1 = diag ? diag[i + 1] * gv.y : gv.y;
       acc[0] += gv.x * gv.x + gv.y * gv.y;
-      acc[1] += gv.x * z0 + gv.y * z1;
+      if constexpr (GDG) {
+        const double z0 = diag ? diag[i] * gv.x : gv.x, z1 = diag ? diag[i + 1] * gv.y : gv.y;
+        acc[1] += gv.x * z0 + gv.y * z1;
+      }
     } else {
       const double xi = x[i] + alpha * d[i], gi = g[i] + alpha * h[i];
       x[i] = xi; g[i] = gi;
       if (zero_h) h[i] = 0.0;
-      acc[0] += gi * gi; acc[1] += gi * (diag ? diag[i] * gi : gi);
+      acc[0] += gi * gi;
+      if constexpr (GDG) acc[1] += gi * (diag ? diag[i] * gi : gi);
     }
   }
-  block_reduce_store<2>(acc, partials);
+  block_reduce_store<GDG ? 2 : 1>(acc, partials + blockIdx.y * gridDim.x);
 }
 // res = sqrt(gg); ++it; stop test; beta = gDg / gh ; gh = gDg
 static __global__ void cg_control_kernel(double *sc, int *st)
@@ -3641,106 +3678,24 @@ static __global__ void cg_control_kernel(double *sc, int *st)
   sc[SC_BETA] = sc[SC_GDG] / sc[SC_GH];
   sc[SC_GH] = sc[SC_GDG];
 }
-// d = beta d - D g
-static __global__ void __launch_bounds__(VB) cg_direction_kernel(double *d, const double *g, const double *diag, size_t n, const double *sc,
-                                                         const int *st)
-{
-  if (st[ST_DONE]) return;
-  const double beta = sc[SC_BETA];
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      double2 dv = *reinterpret_cast<double2 *>(d + i);
-      const double2 gv = *reinterpret_cast<const double2 *>(g + i);
-      dv.x = beta * dv.x - (diag ? diag[i] * gv.x : gv.x);
-      dv.y = beta * dv.y - (diag ? diag[i + 1] * gv.y : gv.y);
-      *reinterpret_cast<double2 *>(d + i) = dv;
-    } else
-      d[i] = beta * d[i] - (diag ? diag[i] * g[i] : g[i]);
-  }
-}
-
-// ---- plain CG on a block vector (bp5_cg_solve_components): the kernels above with the component as the second grid dimension.
-// Component c = blockIdx.y works on the block at + c ld; its partial sums land in columns [c gridDim.x, (c + 1) gridDim.x) of the rows, so the
-// finalize pass sums block-wise partials, components in order (fixed order).  diag is per scalar DoF, shared by the components.
-static __global__ void copy_constrained_components_kernel(const uint32_t *cdofs, uint32_t n, const double *src, double *dst, size_t ld)
-{
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const size_t c = cdofs[i] + blockIdx.y * ld; dst[c] = src[c]; }
-}
-static __global__ void __launch_bounds__(VB) cgc_init_kernel(const double *b, const double *diag, double *x, double *g, double *d, size_t n, size_t ld,
-                                                             double *partials)
-{
-  const size_t o = blockIdx.y * ld;
-  b += o; x += o; g += o; d += o;
-  double acc[2] = {0.0, 0.0};
-  const size_t stride = (size_t)gridDim.x * VB;
-  for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
-    const double gi = -b[i], hi = diag ? diag[i] * gi : gi;
-    x[i] = 0.0; g[i] = gi; d[i] = -hi;
-    acc[0] += gi * gi; acc[1] += gi * hi;
-  }
-  block_reduce_store<2>(acc, partials + blockIdx.y * gridDim.x);
-}
-static __global__ void __launch_bounds__(VB) cgc_dot_kernel(const double *x, const double *y, size_t n, size_t ld, double *partials, const int *st)
-{
-  if (st[ST_DONE]) return;
-  x += blockIdx.y * ld; y += blockIdx.y * ld;
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
-      acc[0] += a.x * b.x + a.y * b.y;
-    } else
-      acc[0] += x[i] * y[i];
-  }
-  block_reduce_store<1>(acc, partials + blockIdx.y * gridDim.x);
-}
-static __global__ void __launch_bounds__(VB) cgc_update_kernel(double *x, double *g, const double *d, const double *h, const double *diag, size_t n, size_t ld,
-                                                               const double *sc, const int *st, double *partials)
-{
-  if (st[ST_DONE]) return;
-  const size_t o = blockIdx.y * ld;
-  x += o; g += o; d += o; h += o;
-  const double alpha = sc[SC_GH] / sc[SC_DH];
-  double acc[2] = {0.0, 0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      double2 xv = *reinterpret_cast<double2 *>(x + i), gv = *reinterpret_cast<double2 *>(g + i);
-      const double2 dv = *reinterpret_cast<const double2 *>(d + i), hv = *reinterpret_cast<const double2 *>(h + i);
-      xv.x += alpha * dv.x; xv.y += alpha * dv.y;
-      gv.x += alpha * hv.x; gv.y += alpha * hv.y;
-      *reinterpret_cast<double2 *>(x + i) = xv;
-      *reinterpret_cast<double2 *>(g + i) = gv;
-      const double z0 = diag ? diag[i] * gv.x : gv.x, z1 = diag ? diag[i + 1] * gv.y : gv.y;
-      acc[0] += gv.x * gv.x + gv.y * gv.y;
-      acc[1] += gv.x * z0 + gv.y * z1;
-    } else {
-      const double xi = x[i] + alpha * d[i], gi = g[i] + alpha * h[i];
-      x[i] = xi; g[i] = gi;
-      acc[0] += gi * gi; acc[1] += gi * (diag ? diag[i] * gi : gi);
-    }
-  }
-  block_reduce_store<2>(acc, partials + blockIdx.y * gridDim.x);
-}
-static __global__ void __launch_bounds__(VB) cgc_direction_kernel(double *d, const double *g, const double *diag, size_t n, size_t ld, const double *sc,
-                                                                  const int *st)
+// d = beta d - D g   Z: g is the preconditioner's z = P g (diag not read): d = beta d - z   FIRST (with Z): d = -z, d not read
+template <bool Z, bool FIRST>
+__global__ void __launch_bounds__(VB) cg_direction_kernel(double *d, const double *g, const double *diag, size_t n, size_t ld, const double *sc,
+                                                          const int *st)
 {
   if (st[ST_DONE]) return;
   d += blockIdx.y * ld; g += blockIdx.y * ld;
-  const double beta = sc[SC_BETA];
+  const double beta = FIRST ? 0.0 : sc[SC_BETA];
   const size_t stride = (size_t)gridDim.x * VB * 2;
   for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
     if (i + 1 < n) {
-      double2 dv = *reinterpret_cast<double2 *>(d + i);
+      double2 dv = FIRST ? double2{0.0, 0.0} : *reinterpret_cast<double2 *>(d + i);
       const double2 gv = *reinterpret_cast<const double2 *>(g + i);
-      dv.x = beta * dv.x - (diag ? diag[i] * gv.x : gv.x);
-      dv.y = beta * dv.y - (diag ? diag[i + 1] * gv.y : gv.y);
+      dv.x = FIRST ? -gv.x : beta * dv.x - (!Z && diag ? diag[i] * gv.x : gv.x);
+      dv.y = FIRST ? -gv.y : beta * dv.y - (!Z && diag ? diag[i + 1] * gv.y : gv.y);
       *reinterpret_cast<double2 *>(d + i) = dv;
     } else
-      d[i] = beta * d[i] - (diag ? diag[i] * g[i] : g[i]);
+      d[i] = FIRST ? -g[i] : beta * d[i] - (!Z && diag ? diag[i] * g[i] : g[i]);
   }
 }
 
@@ -3976,78 +3931,6 @@ static __global__ void cgm_init_control_kernel(double *sc, int *st)
   st[ST_DONE] = (sc[SC_RES] <= sc[SC_TOL]) ? 1 : 0;
 }
 
-// ---- CG with a general preconditioner z = P g (bp5_cg_solve_preconditioned).  g, d, h as in the plain solver; z is the
-// preconditioner's output.  Scalars: SC_GG = g.g, SC_GDG = g.z (the slot of g.Dg), the control step is cg_control_kernel's.
-// init: x = 0, g = -b, partial sums of g.g
-static __global__ void __launch_bounds__(VB) pcg_init_kernel(const double *b, double *x, double *g, size_t n, double *partials)
-{
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB;
-  for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
-    const double gi = -b[i];
-    x[i] = 0.0; g[i] = gi;
-    acc[0] += gi * gi;
-  }
-  block_reduce_store<1>(acc, partials);
-}
-// x += alpha d ; g += alpha h ; partial sums of g.g   with alpha = gh / dh
-static __global__ void __launch_bounds__(VB) pcg_update_kernel(double *x, double *g, const double *d, const double *h, size_t n, const double *sc,
-                                                       const int *st, double *partials)
-{
-  if (st[ST_DONE]) return;
-  const double alpha = sc[SC_GH] / sc[SC_DH];
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      double2 xv = *reinterpret_cast<double2 *>(x + i), gv = *reinterpret_cast<double2 *>(g + i);
-      const double2 dv = *reinterpret_cast<const double2 *>(d + i), hv = *reinterpret_cast<const double2 *>(h + i);
-      xv.x += alpha * dv.x; xv.y += alpha * dv.y;
-      gv.x += alpha * hv.x; gv.y += alpha * hv.y;
-      *reinterpret_cast<double2 *>(x + i) = xv;
-      *reinterpret_cast<double2 *>(g + i) = gv;
-      acc[0] += gv.x * gv.x + gv.y * gv.y;
-    } else {
-      const double xi = x[i] + alpha * d[i], gi = g[i] + alpha * h[i];
-      x[i] = xi; g[i] = gi;
-      acc[0] += gi * gi;
-    }
-  }
-  block_reduce_store<1>(acc, partials);
-}
-// partial sums of x.y; a stopped solve leaves the partials alone (finalize_kernel is gated on the same flag)
-static __global__ void __launch_bounds__(VB) pcg_dot_kernel(const double *x, const double *y, size_t n, const int *st, double *partials)
-{
-  if (st[ST_DONE]) return;
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
-      acc[0] += a.x * b.x + a.y * b.y;
-    } else
-      acc[0] += x[i] * y[i];
-  }
-  block_reduce_store<1>(acc, partials);
-}
-// d = beta d - z   (FIRST: d = -z, d not read)
-template <bool FIRST>
-__global__ void __launch_bounds__(VB) pcg_direction_kernel(double *d, const double *z, size_t n, const double *sc, const int *st)
-{
-  if (st[ST_DONE]) return;
-  const double beta = FIRST ? 0.0 : sc[SC_BETA];
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      const double2 zv = *reinterpret_cast<const double2 *>(z + i);
-      double2 dv = FIRST ? double2{0.0, 0.0} : *reinterpret_cast<const double2 *>(d + i);
-      dv.x = FIRST ? -zv.x : beta * dv.x - zv.x;
-      dv.y = FIRST ? -zv.y : beta * dv.y - zv.y;
-      *reinterpret_cast<double2 *>(d + i) = dv;
-    } else
-      d[i] = FIRST ? -z[i] : beta * d[i] - z[i];
-  }
-}
 // Lanczos history of a plain solve (the eigenvalue estimate of PreconditionChebyshev): after the control step of iteration k
 // (1-based), hist[2k-2] = alpha_{k-1}, hist[2k-1] = beta_{k-1} (0 when the solve stopped there: no beta was formed)
 static __global__ void cg_record_kernel(const double *sc, const int *st, double *hist, int cap)
