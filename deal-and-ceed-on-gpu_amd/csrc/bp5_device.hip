@@ -241,6 +241,7 @@ extern "C" int bp5_mf_set_metric_precision(bp5_mf *mf, int precision)
   if (precision == BP5_METRIC_F32) {
     if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: meshes with hanging nodes keep double planes");
     if (mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the Helmholtz operator keeps double planes");
+    if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the mass operator keeps its double plane");
     if (mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the affine geometry mode has no six-plane stream to shrink");
     if (mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
   }
@@ -256,12 +257,19 @@ extern "C" int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision)
 }
 extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
 {
-  if (!mf || (op != BP5_OP_POISSON && op != BP5_OP_HELMHOLTZ)) return fail(BP5_ERR_INVALID, "unknown operator");
+  if (!mf || (op != BP5_OP_POISSON && op != BP5_OP_HELMHOLTZ && op != BP5_OP_MASS)) return fail(BP5_ERR_INVALID, "unknown operator");
   if (op == BP5_OP_HELMHOLTZ && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator keeps double metric planes (bp5_mf_set_metric_precision)");
   if (op == BP5_OP_HELMHOLTZ && (mf->has_hanging || mf->geometry_mode == BP5_GEOM_AFFINE))
     return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs a conforming mesh and the six-plane geometry (hanging nodes: the facade's FEEvaluation)");
   if (op == BP5_OP_HELMHOLTZ && mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 and 56");
-  if (mf->coef_planes_committed && mf->coef_planes_committed != (op == BP5_OP_HELMHOLTZ ? 7 : 6))
+  if (op == BP5_OP_MASS) {
+    if (mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "the mass operator keeps a double metric plane (bp5_mf_set_metric_precision: FP32 planes are not supported)");
+    if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs a conforming mesh (hanging nodes: the facade's FEEvaluation)");
+    if (mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "the mass operator has no build for the affine geometry mode");
+    if (mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "the mass operator runs apply variants 0 and 56");
+    if (mf->coef_cell_stride != (uint64_t)mf->n3) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs the plane-major metric layout");
+  }
+  if (mf->coef_planes_committed && mf->coef_planes_committed != bp5_mf::planes_of(op))
     return fail(BP5_ERR_INVALID, "the metric array of this handle has been sized or filled for another plane count: set the operator before bp5_mf_coef_size / bp5_mf_compute_merged_metric");
   mf->operator_kind = op;
   mf->auto_block = -1; // (decided per operator: the Helmholtz build of the block kernel runs two workgroups per CU)
@@ -297,6 +305,7 @@ extern "C" int bp5_mf_set_apply_variant(bp5_mf *mf, int v)
   }
   if (v == 90) return fail(BP5_ERR_INVALID, "apply variant 90 is the hanging-node kernel: the mesh has no constraint masks");
   if (mf->f32_metric() && v != 0 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
+  if (mf->operator_kind == BP5_OP_MASS && v != 0 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "the mass operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
 #ifndef BP5_TIMING_BUILDS
   if (mf->operator_kind == BP5_OP_HELMHOLTZ && v != 0 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
 #endif
@@ -403,6 +412,7 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
   HIP_TRY(hipSetDevice(mf->device));
   if (mode == BP5_GEOM_AFFINE && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes need the six-plane geometry (the affine mode has no six-plane stream to shrink)");
   if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs the six-plane geometry");
+  if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "the mass operator has no build for the affine geometry mode");
   if (mode == BP5_GEOM_AFFINE && mf->has_hanging && mf->apply_variant == 56) return fail(BP5_ERR_UNSUPPORTED, "hanging nodes in the affine geometry mode run the pencil kernel: set apply variant 0 or 90 first");
   if (mode == BP5_GEOM_AFFINE && !mf->d_scalar_plane) {
     double *sp = nullptr, *gc = nullptr, *dev = nullptr;
@@ -430,10 +440,24 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
   return BP5_OK;
 }
 
+template <int n>
+static int launch_mass_plane(bp5_mf *mf, double *coef)
+{
+  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
+  hipLaunchKernelGGL(mass_plane_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient, mf->n_cells, coef,
+                     mf->coef_cell_stride);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
+static int mass_plane_dispatch(bp5_mf *mf, double *coef) { DISPATCH_N(launch_mass_plane, mf, coef); }
 extern "C" int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef)
 {
   if (!mf || !coef) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mf->operator_kind == BP5_OP_MASS) { // one plane rho JxW (plane-major layout, conforming mesh: bp5_mf_set_operator has seen to both)
+    mf->coef_planes_committed = mf->n_planes();
+    return mass_plane_dispatch(mf, coef);
+  }
   GeomOut o{};
   o.coef = coef;
   o.plane_stride = mf->coef_plane_stride; o.cell_stride = mf->coef_cell_stride;
@@ -1066,9 +1090,12 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
   if (v != 0) return v;
   if (mf->has_hanging && mf->geometry_mode == BP5_GEOM_AFFINE) return 90;
   uint32_t b0, b1;
-  if (mf->f32_metric()) { // FP32 planes: the degree's pencil kernel, or the block kernel under the conditions of the double planes (packed indices at every degree)
+  if (mf->f32_metric() || mf->operator_kind == BP5_OP_MASS) {
+    // FP32 planes, the mass operator: the degree's (mass) pencil kernel, or the block kernel where it pays, with packed indices at every degree and
+    // the workgroups per CU of the build: FP32 planes three up to p = 4 and two beyond, the mass build what block_wg_per_cu launches it with
     if (!block_lpc(mf->degree) || mf->h_block_off.empty() || !block_aligned(mf, c0, c1, &b0, &b1)) return 0;
-    return block_kernel_pays(mf, c0, c1, b0, b1, mf->degree <= 4 ? 3 : 2, true) ? 56 : 0;
+    const int wg = mf->f32_metric() ? (mf->degree <= 4 ? 3 : 2) : mass_block_wg_per_cu(mf->degree);
+    return block_kernel_pays(mf, c0, c1, b0, b1, wg, true) ? 56 : 0;
   }
   if (mf->operator_kind == BP5_OP_HELMHOLTZ || mf->has_hanging) { // pencil kernel, or the block kernel (two workgroups per CU, packed indices)
     const int pencil = mf->has_hanging ? 90 : 0;
@@ -1186,6 +1213,7 @@ static int components_check(const bp5_mf *mf, const double *coef, int n_componen
   const size_t extent = (size_t)(n_components - 1) * ld + mf->n_local();
   if (src < dst + extent && dst < src + extent) return fail(BP5_ERR_INVALID, "src and dst overlap");
   if (mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: FP32 metric planes are not supported");
+  if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the mass operator is not supported");
   if (mf->operator_kind != BP5_OP_POISSON) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the Helmholtz operator is not supported");
   if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "block vectors: meshes with hanging nodes are not supported");
   if (mf->geometry_mode != BP5_GEOM_MERGED6) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the affine geometry mode is not supported");
@@ -1264,6 +1292,11 @@ static int launch_diagonal(bp5_mf *mf, const double *coef, double *diag)
 {
   const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65536u);
   const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
+  if (mf->operator_kind == BP5_OP_MASS) { // (conforming, one double plane: bp5_mf_set_operator refuses everything else)
+    hipLaunchKernelGGL(mass_diagonal_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, coef, mf->coef_cell_stride, mf->d_tab, mf->n_cells, diag);
+    KERNEL_CHECK();
+    return BP5_OK;
+  }
   if (mf->f32_metric()) // (conforming, six planes: bp5_mf_set_metric_precision refuses everything else)
     hipLaunchKernelGGL((diagonal_kernel<n, float>), dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, reinterpret_cast<const float *>(coef), mf->coef_plane_stride,
                        mf->coef_cell_stride, (const double *)nullptr, mf->d_tab, mf->n_cells, diag, (const uint32_t *)nullptr, mf->n_planes());

@@ -55,9 +55,10 @@ struct bp5_mf {
   int degree = 0, quadrature = 0, coefficient = 0, n = 0, n3 = 0, device = 0;
   uint32_t n_cells = 0, n_interior = 0, n_owned = 0, n_ghost = 0, n_constrained = 0;
   int apply_variant = 0, n_cus = 0, geometry_mode = 0, march_max_steps = 32;
-  int operator_kind = 0; // BP5_OP_POISSON | BP5_OP_HELMHOLTZ (seven planes: six merged + the mass plane a JxW)
+  int operator_kind = 0; // BP5_OP_POISSON | BP5_OP_HELMHOLTZ (seven planes: six merged + the mass plane a JxW) | BP5_OP_MASS (one plane: rho JxW)
   mutable int coef_planes_committed = 0; // planes of the metric array the caller has sized (bp5_mf_coef_size) or filled: set_operator may not change the count afterwards
-  int n_planes() const { return operator_kind == BP5_OP_HELMHOLTZ ? 7 : 6; }
+  static int planes_of(int op) { return op == BP5_OP_HELMHOLTZ ? 7 : op == BP5_OP_MASS ? 1 : 6; }
+  int n_planes() const { return planes_of(operator_kind); }
   // BP5_METRIC_F64 | BP5_METRIC_F32 (bp5_mf_set_metric_precision): entry type of the merged-metric planes behind every `coef` argument.  F32: the
   // same pair layout with float entries (coef_plane_stride / coef_cell_stride then count floats), read by the BLK_F32M builds of the pencil
   // and block kernel; fixed once the array has been sized or filled (coef_planes_committed)
@@ -381,6 +382,26 @@ inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_compo
   KERNEL_CHECK();
   return BP5_OK;
 }
+// BP5_OP_MASS: cells [c0, c1) through the mass pencil kernel (atomic scatter: an overwriting launch zero-fills dst first)
+template <int P, bool COLL, int TW, int LPC, int TPB>
+inline int launch_apply_mass_t(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite)
+{
+  constexpr int n = P + 1;
+  constexpr int CPT = 64 * TW / LPC;
+  if (overwrite) BP5_TRY(zero_dst(mf, dst));
+  ApplyArgs a = apply_args(mf, false, coef, src, dst);
+  a.cell_begin = c0; a.cell_end = c1;
+  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
+  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
+  a.teams_per_xcd = (nblk + 7) / 8;
+  ShapeArg<n> sh;
+  fill_shape(sh, mf);
+  const size_t lds = COLL ? 0 : (size_t)TPB * CPT * mass_tile_stride<n, LPC>() * sizeof(double); // one field per cell slot (collocation: pointwise, no tile)
+  snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_mass_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", TW, LPC, TPB);
+  hipLaunchKernelGGL((apply_pencil_mass_kernel<P, COLL, TW, LPC, TPB>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a, sh);
+  KERNEL_CHECK();
+  return BP5_OK;
+}
 // the degree's default pencil shape, both quadratures
 template <int DEG>
 int apply_components_degree_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1)
@@ -416,6 +437,23 @@ inline size_t block_default_lds_bytes(int degree, uint32_t max_list)
     case 8: return block_lds_bytes<8, false, block_lpc(8), D>(max_list);
   }
   return ~(size_t)0;
+}
+
+// workgroups per CU the BLK_MASS build of a degree is compiled for and launched with (block_wg_per_cu), for the library's automatic kernel choice
+inline int mass_block_wg_per_cu(int degree)
+{
+  constexpr int M = BLK_DEFAULT | BLK_MASS;
+  switch (degree) {
+    case 1: return block_wg_per_cu<1, M>();
+    case 2: return block_wg_per_cu<2, M>();
+    case 3: return block_wg_per_cu<3, M>();
+    case 4: return block_wg_per_cu<4, M>();
+    case 5: return block_wg_per_cu<5, M>();
+    case 6: return block_wg_per_cu<6, M>();
+    case 7: return block_wg_per_cu<7, M>();
+    case 8: return block_wg_per_cu<8, M>();
+  }
+  return 2;
 }
 
 // block-assembled kernel; falls back to the team kernel path when the range is partial
@@ -670,7 +708,7 @@ inline int launch_march_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
 // The builds of the default block kernel that exist, per degree: a mask each, Gauss-only where marked (the others are compiled for both
 // quadratures).  The list IS the inventory: launch_block_default launches nothing else, every entry is instantiated.  Within an operator class
 // the builds with more optional features come first.  Every degree: Poisson on double planes, plain or fused, packed or lattice indices; on
-// float planes (never fused); Helmholtz and hanging nodes, plain or fused, packed indices only.  p = 4 alone: the face carry (in every lattice
+// float planes (never fused); Helmholtz, mass and hanging nodes, plain or fused, packed indices only.  p = 4 alone: the face carry (in every lattice
 // build; BP5_TUNE_FACE_CARRY switches it per launch), non-temporal metric loads (Gauss only; with lattice blocks, or on hanging-node meshes; never
 // on float planes), the affine build, and two older shapes for plans without packed indices (run-length write-out with list loads; list write-out)
 template <int M, bool GAUSS_ONLY = false> struct Bld {};
@@ -679,7 +717,7 @@ template <int DEG>
 struct DefaultBlockBuilds {
   static constexpr int D = BLK_DEFAULT, F = BLK_FUSE;
   using list = BuildList<Bld<D | BLK_LATT>, Bld<D | F | BLK_LATT>, Bld<D>, Bld<D | F>, Bld<D | BLK_F32M | BLK_LATT>, Bld<D | BLK_F32M>, Bld<D | BLK_HELM>,
-                         Bld<D | F | BLK_HELM>, Bld<D | BLK_HANG>, Bld<D | F | BLK_HANG>>;
+                         Bld<D | F | BLK_HELM>, Bld<D | BLK_MASS>, Bld<D | F | BLK_MASS>, Bld<D | BLK_HANG>, Bld<D | F | BLK_HANG>>;
 };
 template <>
 struct DefaultBlockBuilds<4> {
@@ -689,7 +727,7 @@ struct DefaultBlockBuilds<4> {
                          Bld<D | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | F | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | BLK_LATT | BLK_ROLL, true>,
                          Bld<D | F | BLK_LATT | BLK_ROLL, true>,
 #endif
-                         Bld<D | BLK_F32M | LATC>, Bld<D | BLK_F32M>, Bld<D | BLK_HELM>, Bld<D | F | BLK_HELM>, Bld<D | BLK_HANG | BLK_NTM, true>,
+                         Bld<D | BLK_F32M | LATC>, Bld<D | BLK_F32M>, Bld<D | BLK_HELM>, Bld<D | F | BLK_HELM>, Bld<D | BLK_MASS>, Bld<D | F | BLK_MASS>, Bld<D | BLK_HANG | BLK_NTM, true>,
                          Bld<D | F | BLK_HANG | BLK_NTM, true>, Bld<D | BLK_HANG>, Bld<D | F | BLK_HANG>, Bld<D | BLK_AFFINE>,
                          Bld<BLK_SINGLE | BLK_SEQ | BLK_RUNS>, Bld<BLK_SINGLE | BLK_SEQ>>;
 };
@@ -728,7 +766,7 @@ inline int launch_block_default(bp5_mf *mf, ApplyCall &call, const double *coef,
   bp5_mf::DevPlan *dp = nullptr;
   BP5_TRY(get_plan_raw(mf, -(256 / block_lpc(DEG)), &dp));
   const int cls = // operator class (apply_degree_impl has refused the combinations of them, and returned on an empty range)
-      mf->f32_metric() ? BLK_F32M : mf->operator_kind == BP5_OP_HELMHOLTZ ? BLK_HELM : mf->has_hanging ? BLK_HANG : mf->geometry_mode == BP5_GEOM_AFFINE ? BLK_AFFINE : 0;
+      mf->f32_metric() ? BLK_F32M : mf->operator_kind == BP5_OP_HELMHOLTZ ? BLK_HELM : mf->operator_kind == BP5_OP_MASS ? BLK_MASS : mf->has_hanging ? BLK_HANG : mf->geometry_mode == BP5_GEOM_AFFINE ? BLK_AFFINE : 0;
   int want;
   if (dp->packed && variant != 49) {
     want = BLK_DEFAULT | cls | (call.fuse ? BLK_FUSE : 0);
@@ -804,6 +842,17 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
 #endif
     if (call.variant != 0) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
     return LAUNCH_DEFAULT_PENCIL(BLK_HELM, coef);
+  }
+  if (mf->operator_kind == BP5_OP_MASS) {
+    // the mass operator (v, rho u) on one plane (CEED BP1, deal.II MatrixFreeOperators::MassOperator): the mass pencil kernel in the degree's default
+    // pencil shape (any conforming mesh and cell range), or the BLK_MASS build of the block kernel on cell bricks (variant 56; with the CG dot
+    // products fused when the solver asks)
+    if (mf->has_hanging || affine) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs a conforming mesh and the plane geometry (no hanging nodes, no affine mode)");
+    if (call.variant == 56) return launch_block_default<DEG>(mf, call, coef, src, dst);
+    if (call.fuse) return fail(BP5_ERR_INVALID, "fused dot products need the packed block kernel");
+    if (call.variant != 0) return fail(BP5_ERR_UNSUPPORTED, "the mass operator runs apply variants 0 (pencil kernel) and 56 (block kernel)");
+    if (coll) return launch_apply_mass_t<DEG, true, DP::TW, DP::LPC, DP::TPB>(mf, coef, src, dst, c0, c1, overwrite);
+    return launch_apply_mass_t<DEG, false, DP::TW, DP::LPC, DP::TPB>(mf, coef, src, dst, c0, c1, overwrite);
   }
   if (mf->has_hanging) {
     // 2:1 refined meshes (resolve_hanging_nodes, bp5/fe_evaluation_gl.h:150-151,167-168): the hanging-node fix-up after the gather and its

@@ -44,6 +44,7 @@ enum : int {
   BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
   BLK_ROLL = 67108864, BLK_CARRY = 268435456,
   BLK_F32M = 536870912, // the metric planes are float (bp5_mf_set_metric_precision)
+  BLK_MASS = 1073741824, // the mass operator (bp5_mf_set_operator(BP5_OP_MASS)): values only, ONE plane rho JxW
   // the default shape: metric loaded in its own pass, sequential tiles, run-length write-out, packed indices
   BLK_DEFAULT = BLK_SINGLE | BLK_SEQ | BLK_RUNS | BLK_PACK
 };
@@ -1444,6 +1445,122 @@ __global__ void __launch_bounds__(64 * TW * TPB, components_waves_per_simd(P, CO
 #undef TL
 }
 
+// ------------------------------------------------------------------------------------ fused mass operator
+// BP5_OP_MASS: dst += P^T B^T S B P src with B = N x N x N and S = rho(x_q) JxW, ONE plane (CEED BP1; deal.II MatrixFreeOperators::MassOperator:
+// evaluate(values), submit_value(rho * get_value(q)), integrate(values)).  A kernel of its own: one tile field instead of three, 6 one-dimensional
+// contractions per cell instead of the Helmholtz build's 18, and a metric stream of 8 instead of 56 bytes per quadrature point -- what is left is
+// the gather, the atomics and their latency.  Launch shape, lanes, tile layout and the idle-lane rule are apply_pencil_kernel's.
+// Gauss: z-contraction in registers, tile to the y-owner, tile to the x-owner (the orientation the plane's pencil is stored for), the pointwise
+// product, and the transpose sequence back.
+// GLL collocation (N == I): the operator is pointwise and nothing is contracted.  The nodal values stay in the gather orientation (z-owner) and the
+// plane is read THROUGH coef_off at this lane's (i, j) for k = 0..n-1: n 8-byte loads per lane instead of n / 2 16-byte ones, no LDS and no
+// barrier at all, where re-orienting u through the tile and back would cost 4 n LDS operations per lane and two team syncs for no arithmetic.  A
+// cell's plane is n^3 contiguous doubles, so every cache line a wave touches is consumed whole within the k loop.
+// doubles per cell slot: ONE tile field (n planes of PS) plus the padding LdsLayout gives a slot -- a third of the LDS of the three-field kernels, so
+// the workgroups per CU are set by the registers, not by the tiles (p = 4: 10 KB instead of 30 KB per workgroup)
+template <int n, int LPC>
+constexpr int mass_tile_stride()
+{
+  using L = LdsLayout<n, LPC>;
+  static_assert((n - 1) * (L::PS + L::RS + 1) < n * L::PS && L::CS >= 3 * n * L::PS, "a field holds every (k, j, i) entry");
+  return L::CS - 2 * n * L::PS;
+}
+template <int P, bool COLL, int TW, int LPC, int TPB>
+__global__ void __launch_bounds__(64 * TW * TPB) apply_pencil_mass_kernel(ApplyArgs a, ShapeArg<P + 1> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= n2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<n, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // XCD-aware mapping, as apply_pencil_kernel
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < n2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  // idle lanes mirror a valid lane: every load is unconditional and in bounds; LDS writes and the atomics are predicated
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < n2 ? ab : ab % n2;
+  const int a_ = abm % n, b_ = abm / n;
+
+  // ---- gather (z-owner: a_ = i, b_ = j; registers hold k)
+  uint32_t idx[n];
+  double u[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+#pragma unroll
+  for (int k = 0; k < n; ++k) u[k] = a.src[idx[k]];
+  const double *cf = a.coef + cell * a.cell_stride; // the cell's plane
+  double y[n];
+  if constexpr (COLL) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) y[k] = u[k] * cf[coef_off<n>(a_, b_ + n * k)];
+  } else {
+    double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * mass_tile_stride<n, LPC>();
+#define TM(k, j, i) T[(k) * L::PS + (j) * L::RS + (i)]
+    double S[n];
+    load_pencil<n>(cf, abm, S); // x-owner: a_ = j, b_ = k; registers hold i
+    // ---- evaluate: N along z, y, x
+    double aN[n];
+    MV_N(sh.N, u, aN);
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < n; ++k) TM(k, b_, a_) = aN[k];
+    }
+    team_sync<TW>();
+    double vN[n], c1[n]; // y-owner: a_ = i, b_ = k
+#pragma unroll
+    for (int j = 0; j < n; ++j) vN[j] = TM(b_, j, a_);
+    MV_N(sh.N, vN, c1);
+    if (active) { // each y-owner lane rewrites only the column it has just read
+#pragma unroll
+      for (int j = 0; j < n; ++j) TM(b_, j, a_) = c1[j];
+    }
+    team_sync<TW>();
+    double r1[n], um[n]; // x-owner: a_ = j, b_ = k
+#pragma unroll
+    for (int i = 0; i < n; ++i) r1[i] = TM(b_, a_, i);
+    MV_N(sh.N, r1, um);
+    // ---- quadrature-point operation: submit_value(rho * get_value(q)), JxW folded into the plane
+#pragma unroll
+    for (int i = 0; i < n; ++i) um[i] *= S[i];
+    // ---- integrate: N^T along x, y, z
+    double e1[n];
+    MV_NT(sh.N, um, e1);
+    if (active) { // each x-owner lane rewrites only the row it has just read
+#pragma unroll
+      for (int i = 0; i < n; ++i) TM(b_, a_, i) = e1[i];
+    }
+    team_sync<TW>();
+    double w1[n], f1[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) w1[j] = TM(b_, j, a_);
+    MV_NT(sh.N, w1, f1);
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < n; ++j) TM(b_, j, a_) = f1[j];
+    }
+    team_sync<TW>();
+    double z1[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) z1[k] = TM(k, b_, a_);
+    MV_NT(sh.N, z1, y);
+#undef TM
+  }
+  // ---- scatter-add (distribute_local_to_global)
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) atomic_add_f64(a.dst + idx[k], y[k]);
+  }
+}
+
 // degrees whose block-kernel cells span waves (n^2 lanes per cell: p = 2, 5, 8) and exchange their tiles through the workgroup barrier: two
 // tiles used alternately halve the barriers of a pass (BlockPass::PP) where the second tile still fits the LDS share of the workgroup
 #ifndef BP5_PINGPONG_P2
@@ -1586,7 +1703,10 @@ struct BlockPass {
   static constexpr bool SINGLE = (ABL & BLK_SINGLE) != 0;
   // HELM: step-64's Helmholtz operator, see apply_pencil_kernel (one more contraction each way, one more plane: a(x_q) JxW)
   static constexpr bool HELM = (ABL & BLK_HELM) != 0;
-  static constexpr int NPL = HELM ? 7 : 6;
+  // MASS: the mass operator (v, rho u) -- ONE plane rho JxW, the section of the pass between the gathered pencil and the integrated one replaced by
+  // the values-only sequence on one tile field (6 contractions; none under collocation); gather, run tables, accumulator, write-out, combine unchanged
+  static constexpr bool MASS = (ABL & BLK_MASS) != 0;
+  static constexpr int NPL = HELM ? 7 : MASS ? 1 : 6;
   static_assert(!HELM || (!AFFINE && (ABL & BLK_SEQ) != 0), "Helmholtz build: six-plane geometry, sequential tiles");
   // HANG: 2:1 refined meshes -- resolve_hanging_nodes after the gather and its adjoint before the accumulation into the brick vector
   // (bp5/fe_evaluation_gl.h:150-151,167-168), through the cell's transpose tile like apply_pencil_kernel; a pass without a flagged
@@ -1605,6 +1725,8 @@ struct BlockPass {
   // registers until the quadrature-point loop widens them, the arithmetic is double as in every other build
   using MT = metric_t<ABL>;
   static_assert((ABL & BLK_F32M) == 0 || (!AFFINE && !HELM && !ROLL && (ABL & BLK_FUSE) == 0), "FP32 metric planes: Poisson operator, six-plane geometry, no fused dot products");
+  static_assert(!MASS || (!AFFINE && !HANG && !ROLL && !HELM && (ABL & BLK_F32M) == 0 && (ABL & BLK_DEFAULT) == BLK_DEFAULT),
+                "mass build: one double plane, conforming mesh, no rolling prefetch, the default (packed) shape");
   using R = PassRegs<n, AFFINE, NPL, ROLL, MT>;
   // all lanes of a cell slot sit in one wave when LPC divides 64: the tile exchanges then need no block barrier
   // WPACK (round 4, p = 2): 9 lanes per cell do not divide a wave, but SEVEN whole cells fit one (63 lanes) and 4 x 7 = 28 = 256 / 9 cells fill the pass
@@ -1797,244 +1919,316 @@ struct BlockPass {
         else hang_any = __syncthreads_or(flagged) != 0;
         if (hang_any) pencil_hang_resolve<n, WAVE_LOCAL ? 1 : 4, false, L>(cur.mask, a.hang_I, uu, T, a_, b_, act);
       }
-      double q0[n], q1[n], q2[n];
-      double um[HELM ? n : 1]; // HELM: u at this lane's quadrature points, then a JxW u
-      if constexpr (!COLL) {
-        double aN[n], aD[n], vN[n], vD[n];
-        MV_N(sh.N, uu, aN);
-        MV_D(sh.D, uu, aD);
-        if (act) {
-#pragma unroll
-          for (int k = 0; k < n; ++k) T1(k, b_, a_) = aN[k];
-        }
-        tile_sync();
-#pragma unroll
-        for (int j = 0; j < n; ++j) vN[j] = T1(b_, j, a_);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int k = 0; k < n; ++k) T2(k, b_, a_) = aD[k];
-        }
-        tile_sync();
-#pragma unroll
-        for (int j = 0; j < n; ++j) vD[j] = T2(b_, j, a_);
-        tile_sync_r();
-        double c1[n], c2[n], c3[n], r1[n], r2[n], r3[n];
-        MV_N(sh.N, vN, c1);
-        MV_D(sh.D, vN, c2);
-        MV_N(sh.N, vD, c3);
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T1(b_, j, a_) = c1[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int i = 0; i < n; ++i) r1[i] = T1(b_, a_, i);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T2(b_, j, a_) = c2[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int i = 0; i < n; ++i) r2[i] = T2(b_, a_, i);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T1(b_, j, a_) = c3[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int i = 0; i < n; ++i) r3[i] = T1(b_, a_, i);
-        tile_sync_r();
-        MV_D(sh.D, r1, q0);
-        MV_N(sh.N, r2, q1);
-        MV_N(sh.N, r3, q2);
-        if constexpr (HELM) MV_N(sh.N, r1, um);
-      } else {
-        double gz[n], vN[n], c2[n], r1[n];
-        MV_D(sh.D, uu, gz);
-        if (act) {
-#pragma unroll
-          for (int k = 0; k < n; ++k) T1(k, b_, a_) = uu[k];
-        }
-        tile_sync();
-#pragma unroll
-        for (int j = 0; j < n; ++j) vN[j] = T1(b_, j, a_);
-#pragma unroll
-        for (int i = 0; i < n; ++i) r1[i] = T1(b_, a_, i);
-        tile_sync_r();
-        MV_D(sh.D, vN, c2);
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T2(b_, j, a_) = c2[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int i = 0; i < n; ++i) q1[i] = T2(b_, a_, i);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int k = 0; k < n; ++k) T1(k, b_, a_) = gz[k];
-        }
-        tile_sync();
-#pragma unroll
-        for (int i = 0; i < n; ++i) q2[i] = T1(b_, a_, i);
-        tile_sync_r();
-        MV_D(sh.D, r1, q0);
-        if constexpr (HELM) {
-#pragma unroll
-          for (int i = 0; i < n; ++i) um[i] = r1[i];
-        }
-      }
-      BP5_STAMP(1)
-      if constexpr (!PACK) issue_gather(a, nxt); // PACK: after the pass, once the next block's run table is parked
-      BP5_STAMP(2)
-      auto qpoint = [&](int i, auto &&SM) { // SM(plane): the metric entry of this lane's quadrature point i
-        const double x0 = q0[i], x1 = q1[i], x2 = q2[i];
-        if constexpr (AFFINE) {
-          const double sc = SM(0);
-          q0[i] = sc * (cur.Gc[0] * x0 + cur.Gc[3] * x1 + cur.Gc[4] * x2);
-          q1[i] = sc * (cur.Gc[3] * x0 + cur.Gc[1] * x1 + cur.Gc[5] * x2);
-          q2[i] = sc * (cur.Gc[4] * x0 + cur.Gc[5] * x1 + cur.Gc[2] * x2);
-        } else {
-          q0[i] = SM(0) * x0 + SM(3) * x1 + SM(4) * x2;
-          q1[i] = SM(3) * x0 + SM(1) * x1 + SM(5) * x2;
-          q2[i] = SM(4) * x0 + SM(5) * x1 + SM(2) * x2;
-        }
-        // fused CG: src . (A src) is the sum over cells and quadrature points of ghat^T S ghat -- everything is in
-        // registers here, the dot product costs no memory traffic at all
-        if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += x0 * q0[i] + x1 * q1[i] + x2 * q2[i]; }
-        if constexpr (HELM) {
-          const double uq = um[i];
-          um[i] = SM(6) * uq; // submit_value(coef * get_value(q)), JxW folded into the plane
-          if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += uq * um[i]; }
-        }
-      };
-      if constexpr (ROLL) {
-        // consume the metric pair by pair and refill each pair with the NEXT pass's values right away (same registers)
-        const double *cfn = a.coef + (uint64_t)(nxt.ent & 0x7fffffffu) * a.cell_stride;
-        constexpr bool NTM = (ABL & BLK_NTM) != 0;
-#pragma unroll
-        for (int m = 0; m < n / 2; ++m) {
-          qpoint(2 * m, [&](int pl) { return Sr[pl][2 * m]; });
-          qpoint(2 * m + 1, [&](int pl) { return Sr[pl][2 * m + 1]; });
-          __builtin_amdgcn_sched_barrier(0); // the refill must not be hoisted above the last use of the registers it overwrites (it would need new ones)
-          if constexpr (!(ABL & 2)) {
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) load_pencil_pair<n, NTM>(cfn + pl * a.plane_stride, abm, m, Sr[pl][2 * m], Sr[pl][2 * m + 1]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (n & 1) {
-          qpoint(n - 1, [&](int pl) { return Sr[pl][n - 1]; });
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (!(ABL & 2)) {
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) Sr[pl][n - 1] = load_pencil_tail<n, NTM>(cfn + pl * a.plane_stride, abm);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < n; ++i) qpoint(i, [&](int pl) { return cur.S[pl][i]; });
-      }
-      BP5_STAMP(3)
       double yy[n];
-      if constexpr (!COLL) {
-        double e1[n], e2[n], e3[n], w1[n], w2[n], w3[n];
-        MV_DT(sh.D, q0, e1);
-        if constexpr (HELM) MV_NT_ADD(sh.N, um, e1);
-        MV_NT(sh.N, q1, e2);
-        MV_NT(sh.N, q2, e3);
-        if (act) {
+      if constexpr (MASS) {
+        // the mass operator: values only, ONE tile field.  Every rewrite of the tile is done by the lane that has just read the very entries it
+        // writes (a column in the y-owner orientation, a row in the x-owner one; the next pass's first write meets this pass's last read in the
+        // same lane too), so the only syncs are the four (collocation: two) in front of the re-oriented reads
+        double um[n];
+        if constexpr (!COLL) {
+          double aN[n], vN[n], c1[n], r1[n];
+          MV_N(sh.N, uu, aN);
+          if (act) {
 #pragma unroll
-          for (int i = 0; i < n; ++i) T2(b_, a_, i) = e1[i];
+            for (int k = 0; k < n; ++k) T1(k, b_, a_) = aN[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) vN[j] = T1(b_, j, a_);
+          MV_N(sh.N, vN, c1);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T1(b_, j, a_) = c1[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) r1[i] = T1(b_, a_, i);
+          MV_N(sh.N, r1, um);
+        } else { // collocation: pointwise, but the plane's pencil is prefetched in the x-owner orientation: u goes there and back
+          if (act) {
+#pragma unroll
+            for (int k = 0; k < n; ++k) T1(k, b_, a_) = uu[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) um[i] = T1(b_, a_, i);
         }
-        tile_sync();
+        BP5_STAMP(1)
+        BP5_STAMP(2)
 #pragma unroll
-        for (int j = 0; j < n; ++j) w1[j] = T2(b_, j, a_);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int i = 0; i < n; ++i) T1(b_, a_, i) = e2[i];
+        for (int i = 0; i < n; ++i) {
+          const double uq = um[i];
+          um[i] = cur.S[0][i] * uq; // submit_value(rho * get_value(q)), JxW folded into the plane
+          if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += uq * um[i]; } // fused CG: src . (M src) from registers
         }
-        tile_sync();
+        BP5_STAMP(3)
+        if constexpr (!COLL) {
+          double e1[n], w1[n], f1[n], z1[n];
+          MV_NT(sh.N, um, e1);
+          if (act) {
 #pragma unroll
-        for (int j = 0; j < n; ++j) w2[j] = T1(b_, j, a_);
-        tile_sync_r();
-        if (act) {
+            for (int i = 0; i < n; ++i) T1(b_, a_, i) = e1[i];
+          }
+          tile_sync();
 #pragma unroll
-          for (int i = 0; i < n; ++i) T2(b_, a_, i) = e3[i];
+          for (int j = 0; j < n; ++j) w1[j] = T1(b_, j, a_);
+          MV_NT(sh.N, w1, f1);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T1(b_, j, a_) = f1[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) z1[k] = T1(k, b_, a_);
+          MV_NT(sh.N, z1, yy);
+        } else {
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T1(b_, a_, i) = um[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) yy[k] = T1(k, b_, a_);
         }
-        tile_sync();
-#pragma unroll
-        for (int j = 0; j < n; ++j) w3[j] = T2(b_, j, a_);
-        tile_sync_r();
-        double f1[n], f2[n], z1[n], z2[n];
-        MV_NT(sh.N, w1, f1);
-        MV_DT_ADD(sh.D, w2, f1);
-        MV_NT(sh.N, w3, f2);
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T1(b_, j, a_) = f1[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int k = 0; k < n; ++k) z1[k] = T1(k, b_, a_);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T2(b_, j, a_) = f2[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int k = 0; k < n; ++k) z2[k] = T2(k, b_, a_);
-        tile_sync_r();
-        MV_NT(sh.N, z1, yy);
-        MV_DT_ADD(sh.D, z2, yy);
       } else {
-        double e1[n], w1[n], w2[n], z2[n];
-        MV_DT(sh.D, q0, e1);
-        if constexpr (HELM) {
+        double q0[n], q1[n], q2[n];
+        double um[HELM ? n : 1]; // HELM: u at this lane's quadrature points, then a JxW u
+        if constexpr (!COLL) {
+          double aN[n], aD[n], vN[n], vD[n];
+          MV_N(sh.N, uu, aN);
+          MV_D(sh.D, uu, aD);
+          if (act) {
 #pragma unroll
-          for (int i = 0; i < n; ++i) e1[i] += um[i];
+            for (int k = 0; k < n; ++k) T1(k, b_, a_) = aN[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) vN[j] = T1(b_, j, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int k = 0; k < n; ++k) T2(k, b_, a_) = aD[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) vD[j] = T2(b_, j, a_);
+          tile_sync_r();
+          double c1[n], c2[n], c3[n], r1[n], r2[n], r3[n];
+          MV_N(sh.N, vN, c1);
+          MV_D(sh.D, vN, c2);
+          MV_N(sh.N, vD, c3);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T1(b_, j, a_) = c1[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) r1[i] = T1(b_, a_, i);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T2(b_, j, a_) = c2[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) r2[i] = T2(b_, a_, i);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T1(b_, j, a_) = c3[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) r3[i] = T1(b_, a_, i);
+          tile_sync_r();
+          MV_D(sh.D, r1, q0);
+          MV_N(sh.N, r2, q1);
+          MV_N(sh.N, r3, q2);
+          if constexpr (HELM) MV_N(sh.N, r1, um);
+        } else {
+          double gz[n], vN[n], c2[n], r1[n];
+          MV_D(sh.D, uu, gz);
+          if (act) {
+#pragma unroll
+            for (int k = 0; k < n; ++k) T1(k, b_, a_) = uu[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) vN[j] = T1(b_, j, a_);
+#pragma unroll
+          for (int i = 0; i < n; ++i) r1[i] = T1(b_, a_, i);
+          tile_sync_r();
+          MV_D(sh.D, vN, c2);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T2(b_, j, a_) = c2[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) q1[i] = T2(b_, a_, i);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int k = 0; k < n; ++k) T1(k, b_, a_) = gz[k];
+          }
+          tile_sync();
+#pragma unroll
+          for (int i = 0; i < n; ++i) q2[i] = T1(b_, a_, i);
+          tile_sync_r();
+          MV_D(sh.D, r1, q0);
+          if constexpr (HELM) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) um[i] = r1[i];
+          }
         }
-        // y-direction: w1 = e1 + D^T q1 (both re-oriented x-owner -> y-owner)
-        if (act) {
+        BP5_STAMP(1)
+        if constexpr (!PACK) issue_gather(a, nxt); // PACK: after the pass, once the next block's run table is parked
+        BP5_STAMP(2)
+        auto qpoint = [&](int i, auto &&SM) { // SM(plane): the metric entry of this lane's quadrature point i
+          const double x0 = q0[i], x1 = q1[i], x2 = q2[i];
+          if constexpr (AFFINE) {
+            const double sc = SM(0);
+            q0[i] = sc * (cur.Gc[0] * x0 + cur.Gc[3] * x1 + cur.Gc[4] * x2);
+            q1[i] = sc * (cur.Gc[3] * x0 + cur.Gc[1] * x1 + cur.Gc[5] * x2);
+            q2[i] = sc * (cur.Gc[4] * x0 + cur.Gc[5] * x1 + cur.Gc[2] * x2);
+          } else {
+            q0[i] = SM(0) * x0 + SM(3) * x1 + SM(4) * x2;
+            q1[i] = SM(3) * x0 + SM(1) * x1 + SM(5) * x2;
+            q2[i] = SM(4) * x0 + SM(5) * x1 + SM(2) * x2;
+          }
+          // fused CG: src . (A src) is the sum over cells and quadrature points of ghat^T S ghat -- everything is in
+          // registers here, the dot product costs no memory traffic at all
+          if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += x0 * q0[i] + x1 * q1[i] + x2 * q2[i]; }
+          if constexpr (HELM) {
+            const double uq = um[i];
+            um[i] = SM(6) * uq; // submit_value(coef * get_value(q)), JxW folded into the plane
+            if constexpr ((ABL & BLK_FUSE) != 0) { if (act) energy += uq * um[i]; }
+          }
+        };
+        if constexpr (ROLL) {
+          // consume the metric pair by pair and refill each pair with the NEXT pass's values right away (same registers)
+          const double *cfn = a.coef + (uint64_t)(nxt.ent & 0x7fffffffu) * a.cell_stride;
+          constexpr bool NTM = (ABL & BLK_NTM) != 0;
 #pragma unroll
-          for (int i = 0; i < n; ++i) T2(b_, a_, i) = e1[i];
+          for (int m = 0; m < n / 2; ++m) {
+            qpoint(2 * m, [&](int pl) { return Sr[pl][2 * m]; });
+            qpoint(2 * m + 1, [&](int pl) { return Sr[pl][2 * m + 1]; });
+            __builtin_amdgcn_sched_barrier(0); // the refill must not be hoisted above the last use of the registers it overwrites (it would need new ones)
+            if constexpr (!(ABL & 2)) {
+#pragma unroll
+              for (int pl = 0; pl < NPL; ++pl) load_pencil_pair<n, NTM>(cfn + pl * a.plane_stride, abm, m, Sr[pl][2 * m], Sr[pl][2 * m + 1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          if constexpr (n & 1) {
+            qpoint(n - 1, [&](int pl) { return Sr[pl][n - 1]; });
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!(ABL & 2)) {
+#pragma unroll
+              for (int pl = 0; pl < NPL; ++pl) Sr[pl][n - 1] = load_pencil_tail<n, NTM>(cfn + pl * a.plane_stride, abm);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < n; ++i) qpoint(i, [&](int pl) { return cur.S[pl][i]; });
         }
-        tile_sync();
+        BP5_STAMP(3)
+        if constexpr (!COLL) {
+          double e1[n], e2[n], e3[n], w1[n], w2[n], w3[n];
+          MV_DT(sh.D, q0, e1);
+          if constexpr (HELM) MV_NT_ADD(sh.N, um, e1);
+          MV_NT(sh.N, q1, e2);
+          MV_NT(sh.N, q2, e3);
+          if (act) {
 #pragma unroll
-        for (int j = 0; j < n; ++j) w1[j] = T2(b_, j, a_);
-        tile_sync_r();
-        if (act) {
+            for (int i = 0; i < n; ++i) T2(b_, a_, i) = e1[i];
+          }
+          tile_sync();
 #pragma unroll
-          for (int i = 0; i < n; ++i) T1(b_, a_, i) = q1[i];
+          for (int j = 0; j < n; ++j) w1[j] = T2(b_, j, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T1(b_, a_, i) = e2[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) w2[j] = T1(b_, j, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T2(b_, a_, i) = e3[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) w3[j] = T2(b_, j, a_);
+          tile_sync_r();
+          double f1[n], f2[n], z1[n], z2[n];
+          MV_NT(sh.N, w1, f1);
+          MV_DT_ADD(sh.D, w2, f1);
+          MV_NT(sh.N, w3, f2);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T1(b_, j, a_) = f1[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) z1[k] = T1(k, b_, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T2(b_, j, a_) = f2[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) z2[k] = T2(k, b_, a_);
+          tile_sync_r();
+          MV_NT(sh.N, z1, yy);
+          MV_DT_ADD(sh.D, z2, yy);
+        } else {
+          double e1[n], w1[n], w2[n], z2[n];
+          MV_DT(sh.D, q0, e1);
+          if constexpr (HELM) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) e1[i] += um[i];
+          }
+          // y-direction: w1 = e1 + D^T q1 (both re-oriented x-owner -> y-owner)
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T2(b_, a_, i) = e1[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) w1[j] = T2(b_, j, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T1(b_, a_, i) = q1[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int j = 0; j < n; ++j) w2[j] = T1(b_, j, a_);
+          tile_sync_r();
+          MV_DT_ADD(sh.D, w2, w1);
+          if (act) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) T2(b_, j, a_) = w1[j];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) yy[k] = T2(k, b_, a_);
+          tile_sync_r();
+          if (act) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) T1(b_, a_, i) = q2[i];
+          }
+          tile_sync();
+#pragma unroll
+          for (int k = 0; k < n; ++k) z2[k] = T1(k, b_, a_);
+          tile_sync_r();
+          MV_DT_ADD(sh.D, z2, yy);
         }
-        tile_sync();
-#pragma unroll
-        for (int j = 0; j < n; ++j) w2[j] = T1(b_, j, a_);
-        tile_sync_r();
-        MV_DT_ADD(sh.D, w2, w1);
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) T2(b_, j, a_) = w1[j];
-        }
-        tile_sync();
-#pragma unroll
-        for (int k = 0; k < n; ++k) yy[k] = T2(k, b_, a_);
-        tile_sync_r();
-        if (act) {
-#pragma unroll
-          for (int i = 0; i < n; ++i) T1(b_, a_, i) = q2[i];
-        }
-        tile_sync();
-#pragma unroll
-        for (int k = 0; k < n; ++k) z2[k] = T1(k, b_, a_);
-        tile_sync_r();
-        MV_DT_ADD(sh.D, z2, yy);
       }
       if constexpr (HANG) { if (hang_any) pencil_hang_resolve<n, WAVE_LOCAL ? 1 : 4, true, L>(cur.mask, a.hang_I, yy, T, a_, b_, act); } // adjoint
       BP5_STAMP(4)
@@ -2875,6 +3069,31 @@ __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, 
   }
 }
 
+// The ONE plane of a mass handle (BP5_OP_MASS): rho(x_q) JxW in the pair layout, rho = the handle's BP5_COEF_* function -- the entry geometry_kernel
+// writes as plane 6 of a Helmholtz handle, by the same expressions.  A kernel of its own so that no build of geometry_kernel changes; conforming
+// meshes only (bp5_mf_set_operator refuses hanging-node masks).
+template <int n>
+__global__ void __launch_bounds__(n *n *n) mass_plane_kernel(const uint32_t *l2g, const double *coords, const double *tab, int kappa_mode, uint32_t n_cells,
+                                                            double *coef, uint64_t cell_stride)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double X[3 * n3], t1[n3], t2[n3];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    const uint32_t g = l2g[cell * n3 + q];
+    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
+    __syncthreads();
+    double J[3][3], K[3][3], xq[3];
+    cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
+    const double det = invert3(J, K);
+    const double *w = tab + 2 * n2;
+    const double jxw = fabs(det) * w[i] * w[j] * w[k];
+    coef[cell * cell_stride + coef_off<n>(i, j + n * k)] = jxw * kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
+    __syncthreads();
+  }
+}
+
 // permute merged metric between the device layout (x slowest) and the reference layout
 // (MT: entry type of the device planes; the reference layout is always double -- float entries widened, exactly)
 template <int n, typename MT = double>
@@ -2961,6 +3180,26 @@ __global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, 
     const uint32_t hm = hang_mask ? hang_mask[cell] : 0u;
     const bool coarse_entry = (hm & BP5_HANG_ANY) && (hang_on_line(hm, 0, i, j, k, n - 1) || hang_on_line(hm, 1, i, j, k, n - 1) || hang_on_line(hm, 2, i, j, k, n - 1));
     if (!coarse_entry) atomic_add_f64(diag + l2g[cell * n3 + q], acc);
+  }
+}
+
+// diag(M) of a mass handle (BP5_OP_MASS): diag_ijk += sum_abc S(a,b,c) NN[a,i] NN[b,j] NN[c,k], S = the handle's one plane rho JxW and NN = N*N
+// entrywise -- the term diagonal_kernel adds for plane 6 of a Helmholtz handle, as a kernel of its own so that no build of diagonal_kernel changes
+template <int n>
+__global__ void __launch_bounds__(n *n *n) mass_diagonal_kernel(const uint32_t *l2g, const double *coef, uint64_t cell_stride, const double *tab, uint32_t n_cells,
+                                                               double *diag)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double S[n3], t1[n3], t2[n3], NN[n2];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  if (q < n2) NN[q] = tab[q] * tab[q];
+  __syncthreads();
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    S[q] = coef[cell * cell_stride + coef_off<n>(i, j + n * k)]; // this thread's q-point (a,b,c) = (i,j,k) in the device (pair) layout
+    __syncthreads();
+    const double y = Cell3<n>::template tensor3<true>(NN, NN, NN, S, t1, t2, i, j, k);
+    atomic_add_f64(diag + l2g[cell * n3 + q], y);
   }
 }
 

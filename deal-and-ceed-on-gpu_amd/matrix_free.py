@@ -159,7 +159,8 @@ class MatrixFree:
         _lib.check(_lib.lib().bp5_mf_set_apply_variant(self.handle, int(v)))
 
     def set_operator(self, op):
-        """OP_POISSON (bp5/step-64.cu:147-194, default) or OP_HELMHOLTZ (step-64/step-64.cu:154-160,201-219: seven planes)."""
+        """OP_POISSON (bp5/step-64.cu:147-194, default), OP_HELMHOLTZ (step-64/step-64.cu:154-160,201-219: seven planes) or OP_MASS
+        (MatrixFreeOperators::MassOperator, CEED BP1: one plane)."""
         _lib.check(_lib.lib().bp5_mf_set_operator(self.handle, int(op)))
 
     METRIC_PRECISION = {"float64": 0, "float32": 1}   # bp5.h: BP5_METRIC_*
@@ -365,6 +366,23 @@ class HelmholtzOperator(PoissonOperator):
     def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=1, device=0, comm=None, stream=None):
         self.mf_data = MatrixFree().reinit(mesh, quadrature, coefficient, device, stream, comm)
         self.mf_data.set_operator(_lib.OP_HELMHOLTZ)
+        self.geometry = 0
+        self.metric_precision = "float64"
+        self.coef = self.mf_data.evaluate_coefficients()
+        self.n_owned_cells = mesh.n_cells
+        self.do_zero_out = True
+        self.distributed = comm is not None and comm.n_ranks > 1
+
+
+class MassOperator(PoissonOperator):
+    """== MatrixFreeOperators::MassOperator<3,fe_degree> (CEED BP1): (v, rho(x) u) as the library's native mass kernel
+    (bp5_mf_set_operator(BP5_OP_MASS)): `coef` holds ONE plane, rho JxW, rho = `coefficient` (COEF_ONE by default).  vmult,
+    compute_diagonal, assemble_rhs, l2_norm_solution, the solvers (the PoissonOperator branch of Solver.solve) and the halo exchange
+    are the ones of the Poisson operator; block vectors are refused (BP5Error 5)."""
+
+    def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, device=0, comm=None, stream=None):
+        self.mf_data = MatrixFree().reinit(mesh, quadrature, coefficient, device, stream, comm)
+        self.mf_data.set_operator(_lib.OP_MASS)
         self.geometry = 0
         self.metric_precision = "float64"
         self.coef = self.mf_data.evaluate_coefficients()

@@ -202,8 +202,19 @@ int bp5_mf_sync(bp5_mf *mf); /* hipStreamSynchronize */
  *                     planes JxW K K^T (coefficient 1) and the mass plane a(x_q) JxW, a = the handle's BP5_COEF_* function
  *                     (VaryingCoefficientFunctor, step-64/step-64.cu:99-118, with JxW folded in): G = 7 doubles per q-point.
  *                     Conforming meshes, BP5_GEOM_MERGED6; apply variants 0 (pencil kernel) and 56 (block kernel on cell bricks).
- * Set before bp5_mf_coef_size / bp5_mf_compute_merged_metric. */
-enum { BP5_OP_POISSON = 0, BP5_OP_HELMHOLTZ = 1 };
+ *   BP5_OP_MASS       the mass operator (v, rho(x) u): CEED BP1, deal.II's MatrixFreeOperators::MassOperator -- evaluate(values),
+ *                     submit_value(rho * get_value()), integrate(values) -- L2 projection and every explicit time step, as a native kernel
+ *                     of its own (apply_pencil_mass_kernel): six 1-D contractions per cell with Gauss quadrature, none under GLL
+ *                     collocation, where the operator is diagonal.  The metric array holds ONE plane, rho(x_q) JxW, rho = the handle's
+ *                     BP5_COEF_* function, in the pair layout of the other planes: G = 1 double per q-point.  Every entry point of the
+ *                     other operators takes such a handle with the same dst contracts (bp5_apply, bp5_apply_cells,
+ *                     bp5_apply_distributed, bp5_copy_constrained, bp5_compute_diagonal, both bp5_cg_solve variants,
+ *                     bp5_cg_solve_preconditioned, bp5_chebyshev_*), also with n_constrained == 0 (BP1 has no boundary condition).
+ *                     Conforming meshes, BP5_GEOM_MERGED6, double planes, apply variants 0 (pencil kernel) and 56 (block kernel on cell
+ *                     bricks, packed indices): BP5_ERR_UNSUPPORTED for hanging-node masks, BP5_GEOM_AFFINE, BP5_METRIC_F32 -- in
+ *                     either order of the two calls --, every other apply variant and block vectors.
+ * Set before bp5_mf_coef_size / bp5_mf_compute_merged_metric (afterwards, between operators of different plane counts: BP5_ERR_INVALID). */
+enum { BP5_OP_POISSON = 0, BP5_OP_HELMHOLTZ = 1, BP5_OP_MASS = 2 };
 int bp5_mf_set_operator(bp5_mf *mf, int op);
 /* Storage precision of the merged-metric planes (per handle, like bp5_mf_set_operator):
  *   BP5_METRIC_F64  (default) the planes are doubles;
@@ -231,7 +242,8 @@ int bp5_mf_set_operator(bp5_mf *mf, int op);
 enum { BP5_METRIC_F64 = 0, BP5_METRIC_F32 = 1 };
 int bp5_mf_set_metric_precision(bp5_mf *mf, int precision);
 int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision);
-/* number of doubles of the merged-metric array: 6 * n_cells * (p+1)^3  (bp5/step-64.cu:253-254); 7 planes for BP5_OP_HELMHOLTZ;
+/* number of doubles of the merged-metric array: 6 * n_cells * (p+1)^3  (bp5/step-64.cu:253-254); 7 planes for BP5_OP_HELMHOLTZ, 1 plane
+ * (n_cells * (p+1)^3) for BP5_OP_MASS;
  * BP5_METRIC_F32: ceil(6 * n_cells * (p+1)^3 / 2) */
 int bp5_mf_coef_size(const bp5_mf *mf, size_t *n_doubles);
 
@@ -256,7 +268,8 @@ int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef);
  *                     Fails with BP5_ERR_UNSUPPORTED if K K^T varies by more than 1e-10 (relative) inside a cell. */
 enum { BP5_GEOM_MERGED6 = 0, BP5_GEOM_AFFINE = 1 };
 int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode);
-/* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop); coef_ref: 6 n_cells (p+1)^3 DOUBLES in either precision */
+/* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop); coef_ref: 6 n_cells (p+1)^3 DOUBLES in either precision
+ * (BP5_OP_HELMHOLTZ: 7 planes; BP5_OP_MASS: the one plane as [cell][q]) */
 int bp5_mf_metric_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref);
 
 /* MatrixFree::Data mirror (bp5/fe_evaluation_gl.h:112-120, bp5/step-64.cu:94-97):
@@ -377,7 +390,8 @@ int bp5_mf_get_apply_variant(bp5_mf *mf, int *effective);
  * Jacobi preconditioner for the `diag` slot every solver kernel of the reference already threads through
  * (bp5/solver.h:68,100,131,170; bp5/step-64.cu:428-432 fills it with ones).  Setup-time, matrix-free
  * (sum-factorised, no element matrices); ghost contributions are sent to their owners when a communicator is set.
- * diag: owned + ghost storage, ghost entries are left zero.  BP5_OP_HELMHOLTZ: the mass term is included. */
+ * diag: owned + ghost storage, ghost entries are left zero.  BP5_OP_HELMHOLTZ: the mass term is included.
+ * BP5_OP_MASS: diag_i = sum_cells sum_q (N.N x N.N x N.N) rho JxW (under GLL collocation the whole operator). */
 int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag, int invert);
 
 /* b_i = int phi_i with Gauss(p+1), constrained rows 0 (assemble_rhs, bp5/step-64.cu:372-418) */
