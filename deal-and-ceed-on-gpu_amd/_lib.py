@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _LIB = None
 
-QUAD_GAUSS, QUAD_GLL = 0, 1
+QUAD_GAUSS, QUAD_GLL, QUAD_GAUSS_OVER = 0, 1, 2     # bp5.h: BP5_QUAD_*; GAUSS_OVER: Gauss(p+2), CEED BP1 - BP4
 COEF_ONE, COEF_STEP64 = 0, 1
 CG_PLAIN, CG_MERGED = 0, 1
 GEOM_MERGED6, GEOM_AFFINE = 0, 1
@@ -124,6 +124,7 @@ def lib():
         "bp5_strerror": (C.c_char_p, [i32]),
         "bp5_last_error": (C.c_char_p, []),
         "bp5_shape_tables": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+        "bp5_quadrature_points_1d": (i32, [i32, i32, C.POINTER(i32)]),
         "bp5_mesh_create_brick": (i32, [C.POINTER(MeshDesc), C.POINTER(vp)]),
         "bp5_mesh_view_get": (i32, [vp, C.POINTER(MeshView)]),
         "bp5_mesh_destroy": (None, [vp]),
@@ -243,11 +244,18 @@ def tridiagonal_eigenvalues(diag, offdiag):
     return out
 
 
+def quadrature_points_1d(degree, quadrature):
+    """Quadrature points per direction (p + 1; p + 2 for QUAD_GAUSS_OVER) -- host-only, works without a GPU."""
+    nq = C.c_int()
+    check(lib().bp5_quadrature_points_1d(degree, quadrature, C.byref(nq)))
+    return nq.value
+
+
 def shape_tables(degree, quadrature):
-    """(nodes, pts, w, N, D) as numpy arrays -- host-only, works without a GPU."""
-    n = degree + 1
-    nodes, pts, w = (np.zeros(n) for _ in range(3))
-    N, D = np.zeros((n, n)), np.zeros((n, n))
+    """(nodes[n], pts[Q], w[Q], N[Q, n], D[Q, n]) as numpy arrays, Q = quadrature_points_1d -- host-only, works without a GPU."""
+    n, nq = degree + 1, quadrature_points_1d(degree, quadrature)      # (refuses a bad degree or quadrature id before anything is sized)
+    nodes, pts, w = np.zeros(n), np.zeros(nq), np.zeros(nq)
+    N, D = np.zeros((nq, n)), np.zeros((nq, n))
     check(lib().bp5_shape_tables(degree, quadrature, nodes.ctypes.data, pts.ctypes.data, w.ctypes.data,
                                  N.ctypes.data, D.ctypes.data))
     return nodes, pts, w, N, D

@@ -29,11 +29,11 @@ extern "C" int bp5_copy_d2h(void *dst, const void *src, size_t bytes) { HIP_TRY(
 static void tuning_from_environment(bp5_mf *mf);
 static void pack_tab(const Tables &t, std::vector<double> &v)
 {
-  const int n = t.n;
-  v.assign(2 * n * n + n, 0.0);
-  memcpy(v.data(), t.N, n * n * sizeof(double));
-  memcpy(v.data() + n * n, t.D, n * n * sizeof(double));
-  memcpy(v.data() + 2 * n * n, t.w, n * sizeof(double));
+  const int n = t.n, nq = t.nq; // N[nq n], D[nq n], w[nq]
+  v.assign(2 * nq * n + nq, 0.0);
+  memcpy(v.data(), t.N, nq * n * sizeof(double));
+  memcpy(v.data() + nq * n, t.D, nq * n * sizeof(double));
+  memcpy(v.data() + 2 * nq * n, t.w, nq * sizeof(double));
 }
 
 extern "C" int bp5_mf_create(const bp5_mf_desc *d, bp5_mf **out)
@@ -57,15 +57,16 @@ extern "C" int bp5_mf_create(const bp5_mf_desc *d, bp5_mf **out)
   } guard{mf};
   mf->degree = d->degree; mf->quadrature = d->quadrature; mf->coefficient = d->coefficient;
   mf->n = d->degree + 1; mf->n3 = mf->n * mf->n * mf->n; mf->device = d->device;
+  mf->nq = tab.nq; mf->nq3 = tab.nq * tab.nq * tab.nq;
   mf->n_cells = d->n_cells; mf->n_interior = d->n_interior_cells; mf->n_owned = d->n_owned; mf->n_ghost = d->n_ghost;
   mf->n_constrained = d->n_constrained;
   mf->tab = tab; mf->tab_gauss = tabg;
   tuning_from_environment(mf);
   { // metric layout (A/B knob: BP5_COEF_LAYOUT = plane | cell)
     const char *e = getenv("BP5_COEF_LAYOUT");
-    const bool cell_major = e && !strcmp(e, "cell");
-    mf->coef_plane_stride = cell_major ? (uint64_t)mf->n3 : (uint64_t)mf->n_cells * mf->n3;
-    mf->coef_cell_stride = cell_major ? (uint64_t)6 * mf->n3 : (uint64_t)mf->n3;
+    const bool cell_major = e && !strcmp(e, "cell") && !mf->overint(); // (an over-integrated handle keeps the plane-major layout)
+    mf->coef_plane_stride = cell_major ? (uint64_t)mf->n3 : (uint64_t)mf->n_cells * mf->nq3;
+    mf->coef_cell_stride = cell_major ? (uint64_t)6 * mf->n3 : (uint64_t)mf->nq3;
   }
   // validate indices on the host: a bad index would fault on the GPU
   const size_t nl = (size_t)d->n_cells * mf->n3, nloc = mf->n_local();
@@ -127,6 +128,7 @@ extern "C" int bp5_mf_create(const bp5_mf_desc *d, bp5_mf **out)
         }
       mf->has_hanging = true;
     }
+    if (mf->has_hanging && mf->overint()) return overint_refuse("meshes with hanging nodes are not supported");
     if (mf->has_hanging) {
       BP5_TRY(upload(&mf->d_hang_mask, hm.data(), hm.size()));
       const int n = mf->n;
@@ -226,7 +228,7 @@ extern "C" int bp5_mf_sync(bp5_mf *mf)
 extern "C" int bp5_mf_coef_size(const bp5_mf *mf, size_t *n)
 {
   if (!mf || !n) return fail(BP5_ERR_INVALID, "null argument");
-  *n = (size_t)mf->n_planes() * mf->n_cells * mf->n3;
+  *n = (size_t)mf->n_planes() * mf->n_cells * mf->nq3; // (nq3 == n3 but on a BP5_QUAD_GAUSS_OVER handle: (p+2)^3)
   if (mf->f32_metric()) *n = (*n + 1) / 2; // float entries: the doubles that hold them
   mf->coef_planes_committed = mf->n_planes();
   return BP5_OK;
@@ -239,6 +241,7 @@ extern "C" int bp5_mf_set_metric_precision(bp5_mf *mf, int precision)
   if (mf->coef_planes_committed)
     return fail(BP5_ERR_INVALID, "the metric array of this handle has been sized or filled in another precision: set the metric precision before bp5_mf_coef_size / bp5_mf_compute_merged_metric");
   if (precision == BP5_METRIC_F32) {
+    if (mf->overint()) return overint_refuse("FP32 metric planes are not supported");
     if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: meshes with hanging nodes keep double planes");
     if (mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the Helmholtz operator keeps double planes");
     if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the mass operator keeps its double plane");
@@ -258,6 +261,7 @@ extern "C" int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision)
 extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
 {
   if (!mf || (op != BP5_OP_POISSON && op != BP5_OP_HELMHOLTZ && op != BP5_OP_MASS)) return fail(BP5_ERR_INVALID, "unknown operator");
+  if (op == BP5_OP_HELMHOLTZ && mf->overint()) return overint_refuse("the Helmholtz operator is not supported (Poisson and mass operator only)");
   if (op == BP5_OP_HELMHOLTZ && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator keeps double metric planes (bp5_mf_set_metric_precision)");
   if (op == BP5_OP_HELMHOLTZ && (mf->has_hanging || mf->geometry_mode == BP5_GEOM_AFFINE))
     return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs a conforming mesh and the six-plane geometry (hanging nodes: the facade's FEEvaluation)");
@@ -267,7 +271,7 @@ extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
     if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs a conforming mesh (hanging nodes: the facade's FEEvaluation)");
     if (mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "the mass operator has no build for the affine geometry mode");
     if (mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "the mass operator runs apply variants 0 and 56");
-    if (mf->coef_cell_stride != (uint64_t)mf->n3) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs the plane-major metric layout");
+    if (mf->coef_cell_stride != (uint64_t)mf->nq3) return fail(BP5_ERR_UNSUPPORTED, "the mass operator needs the plane-major metric layout");
   }
   if (mf->coef_planes_committed && mf->coef_planes_committed != bp5_mf::planes_of(op))
     return fail(BP5_ERR_INVALID, "the metric array of this handle has been sized or filled for another plane count: set the operator before bp5_mf_coef_size / bp5_mf_compute_merged_metric");
@@ -297,6 +301,7 @@ static bool product_variant(int degree, int v)
 extern "C" int bp5_mf_set_apply_variant(bp5_mf *mf, int v)
 {
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
+  if (mf->overint() && v != 0) return overint_refuse("only apply variant 0, the pencil kernel apply_pencil_q_kernel / apply_pencil_mass_q_kernel (no block, team or march build)");
   if (mf->has_hanging) { // 0: the library decides; 56: block kernel (deterministic; needs cell blocks); 90: pencil kernel with atomics (any mesh)
     if (v != 0 && v != 90 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "meshes with hanging nodes run apply variants 90 (pencil kernel) and 56 (block kernel)");
     if (v == 56 && mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "hanging nodes in the affine geometry mode run the pencil kernel: apply variants 0 and 90");
@@ -410,6 +415,7 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
   if (mode != BP5_GEOM_MERGED6 && mode != BP5_GEOM_AFFINE) return fail(BP5_ERR_INVALID, "unknown geometry mode");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mode == BP5_GEOM_AFFINE && mf->overint()) return overint_refuse("the affine geometry mode is not supported");
   if (mode == BP5_GEOM_AFFINE && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes need the six-plane geometry (the affine mode has no six-plane stream to shrink)");
   if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs the six-plane geometry");
   if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "the mass operator has no build for the affine geometry mode");
@@ -454,6 +460,10 @@ extern "C" int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef)
 {
   if (!mf || !coef) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mf->overint()) { // Q^3 entries per cell and plane, six planes or the mass plane: a kernel of its own
+    mf->coef_planes_committed = mf->n_planes();
+    return overint_compute_metric(mf, coef);
+  }
   if (mf->operator_kind == BP5_OP_MASS) { // one plane rho JxW (plane-major layout, conforming mesh: bp5_mf_set_operator has seen to both)
     mf->coef_planes_committed = mf->n_planes();
     return mass_plane_dispatch(mf, coef);
@@ -484,6 +494,7 @@ extern "C" int bp5_mf_metric_to_reference_layout(bp5_mf *mf, const double *coef,
 {
   if (!mf || !coef || !coef_ref) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mf->overint()) return overint_to_reference_layout(mf, coef, coef_ref);
   DISPATCH_N(launch_permute, mf, coef, coef_ref);
 }
 
@@ -499,6 +510,7 @@ extern "C" int bp5_mf_get_data(bp5_mf *mf, int color, bp5_mf_data *out)
 {
   if (!mf || !out) return fail(BP5_ERR_INVALID, "null argument");
   if (color != 0) return fail(BP5_ERR_INVALID, "this build keeps all cells in one colour");
+  if (mf->overint()) return overint_refuse("bp5_mf_get_data (the unmerged geometry at the quadrature points) is not supported");
   HIP_TRY(hipSetDevice(mf->device));
   if (!mf->d_inv_jac) {
     mf->pad = padding_length(mf->n);
@@ -1088,6 +1100,7 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
 {
   const int v = mf->apply_variant;
   if (v != 0) return v;
+  if (mf->overint()) return 0; // the pencil kernel whatever the mesh: no block, team or march build reads Q^3 points (so no fused dot products either)
   if (mf->has_hanging && mf->geometry_mode == BP5_GEOM_AFFINE) return 90;
   uint32_t b0, b1;
   if (mf->f32_metric() || mf->operator_kind == BP5_OP_MASS) {
@@ -1212,6 +1225,7 @@ static int components_check(const bp5_mf *mf, const double *coef, int n_componen
   if (ld < mf->n_local()) return fail(BP5_ERR_INVALID, "block vectors: ld < n_owned + n_ghost");
   const size_t extent = (size_t)(n_components - 1) * ld + mf->n_local();
   if (src < dst + extent && dst < src + extent) return fail(BP5_ERR_INVALID, "src and dst overlap");
+  if (mf->overint()) return overint_refuse("block vectors (CEED BP2 / BP4) are not supported");
   if (mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: FP32 metric planes are not supported");
   if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the mass operator is not supported");
   if (mf->operator_kind != BP5_OP_POISSON) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the Helmholtz operator is not supported");
@@ -1319,7 +1333,7 @@ extern "C" int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag
   if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !diag) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
   HIP_TRY(hipMemsetAsync(diag, 0, mf->n_local() * sizeof(double), mf->stream));
-  if (mf->n_cells) BP5_TRY(diagonal_dispatch(mf, coef, diag));
+  if (mf->n_cells) BP5_TRY(mf->overint() ? overint_diagonal(mf, coef, diag) : diagonal_dispatch(mf, coef, diag));
   if (mf->has_neighbors()) { // ghost contributions to their owners
     BP5_TRY(bp5_halo_scatter_add(mf, diag));
     BP5_TRY(bp5_halo_zero_ghosts(mf, diag));
@@ -3363,6 +3377,7 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   for (int l = 0; l < n_levels; ++l) {
     if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
     if (mfs[l]->stream != mfs[0]->stream) return fail(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
+    if (mfs[l]->overint()) return overint_refuse("multigrid levels are not supported");
   }
   for (int l = 0; l + 1 < n_levels; ++l)
     if (!transfers[l] || transfers[l]->fine != mfs[l] || transfers[l]->coarse != mfs[l + 1])

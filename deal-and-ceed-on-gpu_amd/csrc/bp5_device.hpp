@@ -53,6 +53,10 @@ struct bp5_event {
 constexpr size_t STREAMING_MAX_DOFS = 24000000; // see bp5_mf_set_streaming (include/bp5.h)
 struct bp5_mf {
   int degree = 0, quadrature = 0, coefficient = 0, n = 0, n3 = 0, device = 0;
+  // quadrature points per direction and per cell: n and n3 but on a BP5_QUAD_GAUSS_OVER handle (n + 1 points per direction), whose metric planes,
+  // tables and kernels are its own (the bp5_overint unit): Poisson and mass operator, pencil kernels, conforming mesh, six double planes or one
+  int nq = 0, nq3 = 0;
+  bool overint() const { return quadrature == BP5_QUAD_GAUSS_OVER; }
   uint32_t n_cells = 0, n_interior = 0, n_owned = 0, n_ghost = 0, n_constrained = 0;
   int apply_variant = 0, n_cus = 0, geometry_mode = 0, march_max_steps = 32;
   int operator_kind = 0; // BP5_OP_POISSON | BP5_OP_HELMHOLTZ (seven planes: six merged + the mass plane a JxW) | BP5_OP_MASS (one plane: rho JxW)
@@ -311,6 +315,16 @@ inline void fill_shape(ShapeArg<n> &sh, const bp5_mf *mf)
     pack_even_odd<n>(mf->tab.D, true, sh.D);
   }
 }
+
+// The over-integrated handle (BP5_QUAD_GAUSS_OVER), defined in overint/bp5_overint.hip -- a translation unit of its own, off the per-degree units:
+// the operator (refuses every variant but the pencil kernel and every class but Poisson and mass), the planes, the diagonal (contributions of the
+// cells; the caller has zeroed diag) and the permutation to the reference layout
+int overint_apply(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst);
+int overint_compute_metric(bp5_mf *mf, double *coef);
+int overint_diagonal(bp5_mf *mf, const double *coef, double *diag);
+int overint_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref);
+// the reason an over-integrated handle refuses something with (BP5_ERR_UNSUPPORTED)
+inline int overint_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED, std::string("Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER): ") + what); }
 
 // What every operator launch takes from the handle (affine builds read ONE scalar plane, cells n^3 entries apart); the launcher adds range and team counts
 inline ApplyArgs apply_args(const bp5_mf *mf, bool affine, const double *coef, const double *src, double *dst)
@@ -815,6 +829,7 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
   const bool coll = mf->quadrature == BP5_QUAD_GLL;
   const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
   if (c1 <= c0) return overwrite ? zero_dst(mf, dst) : BP5_OK; // the empty range, for every operator and variant
+  if (mf->overint()) return overint_apply(mf, call, coef, src, dst); // Gauss(p+2) points: kernels, tables and planes of its own, Poisson and mass class
   if (mf->f32_metric()) {
     // FP32 metric planes (bp5_mf_set_metric_precision): the BLK_F32M builds of what the dispatch picks for an unfused application of the Poisson
     // operator on six planes -- variant 56: the default block kernel, cell ranges and two-part launches included; variant 0: the degree's default

@@ -85,20 +85,28 @@ static void gll(int n, std::vector<long double> &x, std::vector<long double> &w)
   for (int i = 0; i < n; ++i) { long double P, dP; legendre(m, x[i], P, dP); w[i] = 2 / (m * (m + 1.0L) * P * P); }
 }
 
+int quadrature_points_1d(int degree, int quadrature)
+{
+  if (degree < 1 || degree > BP5_MAX_DEGREE) { fail(BP5_ERR_INVALID, "degree must be in 1..8"); return 0; }
+  if (quadrature != BP5_QUAD_GAUSS && quadrature != BP5_QUAD_GLL && quadrature != BP5_QUAD_GAUSS_OVER) { fail(BP5_ERR_INVALID, "unknown quadrature"); return 0; }
+  return quadrature == BP5_QUAD_GAUSS_OVER ? degree + 2 : degree + 1;
+}
+
 int shape_tables(int degree, int quadrature, Tables &t)
 {
-  if (degree < 1 || degree > BP5_MAX_DEGREE) return fail(BP5_ERR_INVALID, "degree must be in 1..8");
-  if (quadrature != BP5_QUAD_GAUSS && quadrature != BP5_QUAD_GLL) return fail(BP5_ERR_INVALID, "unknown quadrature");
+  const int nq = quadrature_points_1d(degree, quadrature);
+  if (!nq) return BP5_ERR_INVALID;
   const int n = degree + 1;
-  t.n = n;
+  t.n = n; t.nq = nq;
   std::vector<long double> xn, wn, xq, wq;
   gll(n, xn, wn);
-  if (quadrature == BP5_QUAD_GLL) gll(n, xq, wq); else gauss(n, xq, wq);
+  if (quadrature == BP5_QUAD_GLL) gll(n, xq, wq); else gauss(nq, xq, wq);
   for (auto &v : xn) v = (v + 1) / 2;
   for (auto &v : xq) v = (v + 1) / 2;
   for (auto &v : wq) v /= 2;
-  for (int i = 0; i < n; ++i) { t.nodes[i] = (double)xn[i]; t.pts[i] = (double)xq[i]; t.w[i] = (double)wq[i]; }
-  for (int q = 0; q < n; ++q)
+  for (int i = 0; i < n; ++i) t.nodes[i] = (double)xn[i];
+  for (int q = 0; q < nq; ++q) { t.pts[q] = (double)xq[q]; t.w[q] = (double)wq[q]; }
+  for (int q = 0; q < nq; ++q)
     for (int i = 0; i < n; ++i) {
       long double den = 1, num = 1, s = 0;
       for (int m = 0; m < n; ++m) if (m != i) { den *= xn[i] - xn[m]; num *= xq[q] - xn[m]; }
@@ -113,10 +121,11 @@ int shape_tables(int degree, int quadrature, Tables &t)
     }
   if (quadrature == BP5_QUAD_GLL)
     for (int q = 0; q < n; ++q) for (int i = 0; i < n; ++i) t.N[q * n + i] = (q == i) ? 1.0 : 0.0;
-  // bitwise (anti)symmetry under x -> 1-x: the device kernels read only half of each table
-  for (int q = 0; q < n; ++q)
+  // bitwise (anti)symmetry under x -> 1-x (the rectangular tables of BP5_QUAD_GAUSS_OVER too: N[q][i] == N[nq-1-q][n-1-i]): the device kernels
+  // read only half of each table
+  for (int q = 0; q < nq; ++q)
     for (int i = 0; i < n; ++i) {
-      const int f = q * n + i, g = (n - 1 - q) * n + (n - 1 - i);
+      const int f = q * n + i, g = (nq - 1 - q) * n + (n - 1 - i);
       if (f < g) {
         const double a = 0.5 * (t.N[f] + t.N[g]), b = 0.5 * (t.D[f] - t.D[g]);
         t.N[f] = a; t.N[g] = a; t.D[f] = b; t.D[g] = -b;
@@ -409,12 +418,20 @@ extern "C" int bp5_shape_tables(int degree, int quadrature, double *nodes, doubl
   Tables t;
   int st = shape_tables(degree, quadrature, t);
   if (st) return st;
-  const int n = t.n;
+  const int n = t.n, nq = t.nq;
   if (nodes) memcpy(nodes, t.nodes, n * sizeof(double));
-  if (pts) memcpy(pts, t.pts, n * sizeof(double));
-  if (w) memcpy(w, t.w, n * sizeof(double));
-  if (N) memcpy(N, t.N, n * n * sizeof(double));
-  if (D) memcpy(D, t.D, n * n * sizeof(double));
+  if (pts) memcpy(pts, t.pts, nq * sizeof(double));
+  if (w) memcpy(w, t.w, nq * sizeof(double));
+  if (N) memcpy(N, t.N, nq * n * sizeof(double));
+  if (D) memcpy(D, t.D, nq * n * sizeof(double));
+  return BP5_OK;
+}
+extern "C" int bp5_quadrature_points_1d(int degree, int quadrature, int *n_q)
+{
+  if (!n_q) return fail(BP5_ERR_INVALID, "null argument");
+  const int nq = quadrature_points_1d(degree, quadrature);
+  if (!nq) return BP5_ERR_INVALID;
+  *n_q = nq;
   return BP5_OK;
 }
 

@@ -8,14 +8,16 @@
 namespace bp5 {
 
 constexpr int MAXN = BP5_MAX_DEGREE + 1;
+constexpr int MAXQ = MAXN + 1; // BP5_QUAD_GAUSS_OVER: p + 2 points per direction
 
 struct Tables {
-  int n = 0;
-  double nodes[MAXN], pts[MAXN], w[MAXN];
-  double N[MAXN * MAXN], D[MAXN * MAXN]; // [q*n+i]
+  int n = 0, nq = 0; // nodes / quadrature points per direction (nq == n but for BP5_QUAD_GAUSS_OVER: n + 1)
+  double nodes[MAXN], pts[MAXQ], w[MAXQ];
+  double N[MAXQ * MAXN], D[MAXQ * MAXN]; // [q*n+i], q < nq
 };
 
 int shape_tables(int degree, int quadrature, Tables &t);
+int quadrature_points_1d(int degree, int quadrature); // 0: unknown degree or quadrature (the reason is in bp5_last_error)
 int fail(int status, const std::string &msg);
 
 // Per-team index plan of the team-assembled operator kernel (bp5_kernels.hpp: apply_team_kernel):

@@ -4515,4 +4515,416 @@ static __global__ void wait_value_probe_consumer(unsigned long long *consumer_ra
   if (threadIdx.x == 0) __hip_atomic_store(consumer_ran, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ==================================================================================== over-integration: BP5_QUAD_GAUSS_OVER
+// Gauss(p + 2) quadrature (CEED BP1 - BP4; FEEvaluation<dim, p, n_q_points_1d = p + 2>, bp5/fe_evaluation_gl.h:28): n = p + 1 nodes and Q = p + 2
+// points per direction, so the 1-D tables are RECTANGULAR, Q x n, and every per-q-point array of a cell holds Q^3 entries.  Kernels of their own
+// -- no build of an existing kernel changes --: two setup kernels (planes, diagonal) and two fused operator kernels (Poisson, mass).
+//
+// In-register Q x n mat-vec with wave-uniform entries.  The tables are (anti)symmetric under reversal of BOTH indices, N[q][i] = N[Q-1-q][n-1-i],
+// D[q][i] = -D[Q-1-q][n-1-i] (enforced bitwise by the host, bp5_host.cpp), and entry f = q n + i mirrors entry Q n - 1 - f: only the first
+// ceil(Q n / 2) entries are ever read, and only those are passed (ShapeArgQ).
+//   out[q] (+)= sum_i M[q][i] in[i], in[n] -> out[Q];   TR: out[i] (+)= sum_q M[q][i] in[q], in[Q] -> out[n].   ANTI selects the table D.
+template <int n, int Q>
+struct ShapeArgQ { // passed by value as a kernel argument: uniform -> scalar loads
+  static constexpr int H = (Q * n + 1) / 2;
+  double N[H];
+  double D[H];
+};
+template <int n, int Q, bool TR, bool ANTI, bool ADD>
+__device__ __forceinline__ void mv_rect(const double *__restrict__ M, const double (&in)[TR ? Q : n], double (&out)[TR ? n : Q])
+{
+  constexpr int NO = TR ? n : Q, NI = TR ? Q : n;
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    double acc = ADD ? out[o] : 0.0;
+#pragma unroll
+    for (int s = 0; s < NI; ++s) {
+      const int q = TR ? s : o, i = TR ? o : s;
+      const int f = q * n + i, g = Q * n - 1 - f;
+      const double m = (f <= g) ? M[f] : (ANTI ? -M[g] : M[g]);
+      if (!ADD && s == 0) acc = m * in[0];
+      else acc = fma(m, in[s], acc);
+    }
+    out[o] = acc;
+  }
+}
+
+// Launch shape of the two operator kernels, per degree: Q^2 lanes per cell.  p <= 3: four one-wave teams per workgroup (7 / 4 / 2 cells per wave);
+// p = 6: Q^2 = 64, a cell IS a wave (four one-wave teams, no workgroup barrier); p = 4, 5, 7, 8: one four-wave team (7 / 5 / 3 / 2 cells), cells
+// span waves and the tile exchanges go through the workgroup barrier.  The six planes are prefetched up to p = 4 (6 Q doubles = 72 VGPRs there);
+// beyond, the q-point loop reads them where it uses them (p = 8: 120 VGPRs of prefetch alone would spill)
+template <int P>
+struct OverintShape {
+  static constexpr int Q = P + 2, LPC = Q * Q;
+  static constexpr int TW = (P <= 3 || P == 6) ? 1 : 4, TPB = (P <= 3 || P == 6) ? 4 : 1;
+  static constexpr int CPT = 64 * TW / LPC;
+  static constexpr bool PF = P <= 4;
+};
+
+// Fused Poisson operator, dst += P^T B^T S B P src with B = (D x N x N, N x D x N, N x N x D) on Q^3 points and S the six planes of Q^3 entries
+// in the pair layout TAKEN AT Q (coef_off<Q>: lane ab = qj + Q qk owns the x-pencil qi = 0 .. Q-1).  apply_pencil_kernel's transpose-tile scheme with
+// rectangular contractions: the data grows n -> Q direction by direction (z in registers, y and x through the tile) and shrinks back the same way.
+//   z-owner  lanes (i, j), i, j < n   hold k = 0..n-1 -> kq = 0..Q-1     gather / scatter orientation
+//   y-owner  lanes (i, kq), i < n     hold j = 0..n-1 -> jq = 0..Q-1
+//   x-owner  lanes (jq, kq), all Q^2  hold i = 0..n-1 -> qi = 0..Q-1     the orientation the planes are stored for
+// A lane outside its orientation's live set mirrors a live lane (clamped coordinates): it does every load and writes neither LDS nor memory, like
+// the lanes of a tail cell.  The tile is LdsLayout<Q, Q^2>: three fields of Q planes.  Every tile write is separated by a team_sync from the last
+// read of the same words by ANOTHER lane (rule 2); where a lane rewrites only words it alone has read, the sync in front of the write
+// is kept all the same, as in apply_pencil_kernel.
+template <int P, int TW, int LPC, int TPB, bool PF>
+__global__ void __launch_bounds__(64 * TW * TPB) apply_pencil_q_kernel(ApplyArgs a, ShapeArgQ<P + 1, P + 2> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n, Q = P + 2, Q2 = Q * Q;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= Q2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<Q, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // XCD-aware mapping, as apply_pencil_kernel
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < Q2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < Q2 ? ab : ab % Q2;
+  const int a_ = abm % Q, b_ = abm / Q;
+  const int am = a_ < n ? a_ : n - 1, bm = b_ < n ? b_ : n - 1; // the live lane this lane mirrors where a coordinate must be a node index
+  const bool live_z = active && a_ < n && b_ < n, live_y = active && a_ < n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * L::CS;
+#define TL(f, k, j, i) T[(f) * (Q * L::PS) + (k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- gather (z-owner: am = i, bm = j; registers hold k)
+  uint32_t idx[n];
+  double u[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + bm * n + am;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+#pragma unroll
+  for (int k = 0; k < n; ++k) u[k] = a.src[idx[k]];
+  // ---- metric planes (x-owner: a_ = qj, b_ = qk; registers hold qi), Q^3 entries per cell and plane
+  const double *cf = a.coef + cell * a.cell_stride;
+  double S[PF ? 6 : 1][Q];
+  if constexpr (PF) {
+#pragma unroll
+    for (int pl = 0; pl < 6; ++pl) load_pencil<Q>(cf + pl * a.plane_stride, abm, S[pl]);
+  }
+
+  double g0[Q], g1[Q], g2[Q];
+  {
+    // z-pass in registers: n -> Q
+    double aN[Q], aD[Q];
+    mv_rect<n, Q, false, false, false>(sh.N, u, aN);
+    mv_rect<n, Q, false, true, false>(sh.D, u, aD);
+    if (live_z) {
+#pragma unroll
+      for (int k = 0; k < Q; ++k) { TL(0, k, b_, a_) = aN[k]; TL(1, k, b_, a_) = aD[k]; }
+    }
+    team_sync<TW>();
+    // y-owner: am = i, b_ = kq
+    double vN[n], vD[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) { vN[j] = TL(0, b_, j, am); vD[j] = TL(1, b_, j, am); }
+    double c1[Q], c2[Q], c3[Q];
+    mv_rect<n, Q, false, false, false>(sh.N, vN, c1);
+    mv_rect<n, Q, false, true, false>(sh.D, vN, c2);
+    mv_rect<n, Q, false, false, false>(sh.N, vD, c3);
+    team_sync<TW>();
+    if (live_y) {
+#pragma unroll
+      for (int j = 0; j < Q; ++j) { TL(0, b_, j, a_) = c1[j]; TL(1, b_, j, a_) = c2[j]; TL(2, b_, j, a_) = c3[j]; }
+    }
+    team_sync<TW>();
+    // x-owner: a_ = jq, b_ = kq
+    double r1[n], r2[n], r3[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      r1[i] = TL(0, b_, a_, i);
+      r2[i] = TL(1, b_, a_, i);
+      r3[i] = TL(2, b_, a_, i);
+    }
+    mv_rect<n, Q, false, true, false>(sh.D, r1, g0);
+    mv_rect<n, Q, false, false, false>(sh.N, r2, g1);
+    mv_rect<n, Q, false, false, false>(sh.N, r3, g2);
+  }
+
+  // ---- quadrature-point operation: t = S ghat (symmetric 3x3, bp5/step-64.cu:166-177)
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    double s00, s11, s22, s01, s02, s12;
+    if constexpr (PF) {
+      s00 = S[0][i]; s11 = S[1][i]; s22 = S[2][i]; s01 = S[3][i]; s02 = S[4][i]; s12 = S[5][i];
+    } else {
+      s00 = cf[0 * a.plane_stride + coef_off<Q>(i, abm)];
+      s11 = cf[1 * a.plane_stride + coef_off<Q>(i, abm)];
+      s22 = cf[2 * a.plane_stride + coef_off<Q>(i, abm)];
+      s01 = cf[3 * a.plane_stride + coef_off<Q>(i, abm)];
+      s02 = cf[4 * a.plane_stride + coef_off<Q>(i, abm)];
+      s12 = cf[5 * a.plane_stride + coef_off<Q>(i, abm)];
+    }
+    const double x0 = g0[i], x1 = g1[i], x2 = g2[i];
+    g0[i] = s00 * x0 + s01 * x1 + s02 * x2;
+    g1[i] = s01 * x0 + s11 * x1 + s12 * x2;
+    g2[i] = s02 * x0 + s12 * x1 + s22 * x2;
+  }
+
+  // ---- integrate (transpose sequence): Q -> n
+  double y[n];
+  {
+    double e1[n], e2[n], e3[n];
+    mv_rect<n, Q, true, true, false>(sh.D, g0, e1);
+    mv_rect<n, Q, true, false, false>(sh.N, g1, e2);
+    mv_rect<n, Q, true, false, false>(sh.N, g2, e3);
+    team_sync<TW>();
+    if (active) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = e2[i]; TL(2, b_, a_, i) = e3[i]; }
+    }
+    team_sync<TW>();
+    double w1[Q], w2[Q], w3[Q];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      w1[j] = TL(0, b_, j, am);
+      w2[j] = TL(1, b_, j, am);
+      w3[j] = TL(2, b_, j, am);
+    }
+    double f1[n], f2[n];
+    mv_rect<n, Q, true, false, false>(sh.N, w1, f1);
+    mv_rect<n, Q, true, true, true>(sh.D, w2, f1);
+    mv_rect<n, Q, true, false, false>(sh.N, w3, f2);
+    team_sync<TW>();
+    if (live_y) {
+#pragma unroll
+      for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = f1[j]; TL(1, b_, j, a_) = f2[j]; }
+    }
+    team_sync<TW>();
+    double z1[Q], z2[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) { z1[k] = TL(0, k, bm, am); z2[k] = TL(1, k, bm, am); }
+    mv_rect<n, Q, true, false, false>(sh.N, z1, y);
+    mv_rect<n, Q, true, true, true>(sh.D, z2, y);
+  }
+#undef TL
+  // ---- scatter-add (distribute_local_to_global, bp5/fe_evaluation_gl.h:170-180)
+  if (live_z) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) atomic_add_f64(a.dst + idx[k], y[k]);
+  }
+}
+
+// Fused mass operator on Q^3 points (CEED BP1 as CEED defines it): values only -- N along z, y, x (n -> Q each), um[q] *= S[q] with the ONE plane
+// rho JxW, N^T back -- on ONE tile field, as apply_pencil_mass_kernel.  Orientations, mirrored lanes and launch shape as apply_pencil_q_kernel.
+template <int P, int TW, int LPC, int TPB>
+__global__ void __launch_bounds__(64 * TW * TPB) apply_pencil_mass_q_kernel(ApplyArgs a, ShapeArgQ<P + 1, P + 2> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n, Q = P + 2, Q2 = Q * Q;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= Q2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<Q, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3);
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < Q2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < Q2 ? ab : ab % Q2;
+  const int a_ = abm % Q, b_ = abm / Q;
+  const int am = a_ < n ? a_ : n - 1, bm = b_ < n ? b_ : n - 1;
+  const bool live_z = active && a_ < n && b_ < n, live_y = active && a_ < n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * mass_tile_stride<Q, LPC>();
+#define TM(k, j, i) T[(k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- gather (z-owner: am = i, bm = j; registers hold k)
+  uint32_t idx[n];
+  double u[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + bm * n + am;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+#pragma unroll
+  for (int k = 0; k < n; ++k) u[k] = a.src[idx[k]];
+  double S[Q];
+  load_pencil<Q>(a.coef + cell * a.cell_stride, abm, S); // x-owner: a_ = qj, b_ = qk; registers hold qi
+  // ---- evaluate: N along z, y, x
+  double aN[Q];
+  mv_rect<n, Q, false, false, false>(sh.N, u, aN);
+  if (live_z) {
+#pragma unroll
+    for (int k = 0; k < Q; ++k) TM(k, b_, a_) = aN[k];
+  }
+  team_sync<TW>();
+  double vN[n], c1[Q]; // y-owner: am = i, b_ = kq
+#pragma unroll
+  for (int j = 0; j < n; ++j) vN[j] = TM(b_, j, am);
+  mv_rect<n, Q, false, false, false>(sh.N, vN, c1);
+  team_sync<TW>(); // (mirrored lanes a_ >= n have read the column of lane am, which is rewritten below)
+  if (live_y) {
+#pragma unroll
+    for (int j = 0; j < Q; ++j) TM(b_, j, a_) = c1[j];
+  }
+  team_sync<TW>();
+  double r1[n], um[Q]; // x-owner: a_ = jq, b_ = kq
+#pragma unroll
+  for (int i = 0; i < n; ++i) r1[i] = TM(b_, a_, i);
+  mv_rect<n, Q, false, false, false>(sh.N, r1, um);
+  // ---- quadrature-point operation: submit_value(rho * get_value(q)), JxW folded into the plane
+#pragma unroll
+  for (int i = 0; i < Q; ++i) um[i] *= S[i];
+  // ---- integrate: N^T along x, y, z
+  double e1[n];
+  mv_rect<n, Q, true, false, false>(sh.N, um, e1);
+  if (active) { // each x-owner lane rewrites only the row it has just read (every x-owner lane of a cell is live: none mirrors another)
+#pragma unroll
+    for (int i = 0; i < n; ++i) TM(b_, a_, i) = e1[i];
+  }
+  team_sync<TW>();
+  double w1[Q], f1[n];
+#pragma unroll
+  for (int j = 0; j < Q; ++j) w1[j] = TM(b_, j, am);
+  mv_rect<n, Q, true, false, false>(sh.N, w1, f1);
+  team_sync<TW>(); // (mirrored lanes, as above)
+  if (live_y) {
+#pragma unroll
+    for (int j = 0; j < n; ++j) TM(b_, j, a_) = f1[j];
+  }
+  team_sync<TW>();
+  double z1[Q], y[n];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) z1[k] = TM(k, bm, am);
+  mv_rect<n, Q, true, false, false>(sh.N, z1, y);
+#undef TM
+  // ---- scatter-add (distribute_local_to_global)
+  if (live_z) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) atomic_add_f64(a.dst + idx[k], y[k]);
+  }
+}
+
+// Planes of an over-integrated handle: the Jacobian of MappingQGeneric(p) from the cell's n^3 node coordinates at the Q^3 Gauss(p + 2) points, by
+// three sum-factorised rectangular contractions per coordinate; then kappa JxW K K^T in the order 00, 11, 22, 01, 02, 12 (JacobianFunctor,
+// bp5/step-64.cu:84-114) or, for the mass class (n_planes == 1), the one plane rho JxW -- pair layout taken at Q (coef_off<Q>).  One cell per
+// workgroup, Q^3 threads (thread = q-point); tab: N[Q n], D[Q n], w[Q].
+template <int n>
+__global__ void __launch_bounds__((n + 1) * (n + 1) * (n + 1)) overint_metric_kernel(const uint32_t *l2g, const double *coords, const double *tab, int kappa_mode,
+                                                                                     uint32_t n_cells, int n_planes, double *coef, uint64_t plane_stride,
+                                                                                     uint64_t cell_stride)
+{
+  constexpr int Q = n + 1, n2 = n * n, n3 = n2 * n, Q2 = Q * Q, Q3 = Q2 * Q;
+  // X: one coordinate of the cell's nodes [k][j][i];  A[f]: x-contracted [k][j][qi], f = 0 with N, 1 with D;  B[f]: y-contracted [k][qj][qi],
+  // f = 0: N N, 1: D(x) N(y), 2: N(x) D(y)
+  __shared__ double X[n3], A[2][n2 * Q], B[3][n * Q2];
+  const double *N = tab, *D = tab + Q * n, *w = tab + 2 * Q * n;
+  const int tid = threadIdx.x, qi = tid % Q, qj = (tid / Q) % Q, qk = tid / Q2;
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    double J[3][3], K[3][3], xq[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { // (unrolled: J and xq stay in registers; the contraction loops inside are kept rolled -- setup time, and 1000 threads leave 128 VGPRs)
+      if (tid < n3) X[tid] = coords[3 * (uint64_t)l2g[cell * n3 + tid] + e];
+      __syncthreads();
+      for (int s = tid; s < n2 * Q; s += Q3) {
+        const int q = s % Q, kj = s / Q;
+        double vn = 0.0, vd = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < n; ++i) { vn += N[q * n + i] * X[kj * n + i]; vd += D[q * n + i] * X[kj * n + i]; }
+        A[0][s] = vn; A[1][s] = vd;
+      }
+      __syncthreads();
+      for (int s = tid; s < n * Q2; s += Q3) {
+        const int q = s % Q, qy = (s / Q) % Q, k = s / Q2;
+        double nn = 0.0, dn = 0.0, nd = 0.0;
+#pragma unroll 1
+        for (int j = 0; j < n; ++j) {
+          const double an = A[0][(k * n + j) * Q + q], ad = A[1][(k * n + j) * Q + q];
+          nn += N[qy * n + j] * an; dn += N[qy * n + j] * ad; nd += D[qy * n + j] * an;
+        }
+        B[0][s] = nn; B[1][s] = dn; B[2][s] = nd;
+      }
+      __syncthreads();
+      double v = 0.0, dx = 0.0, dy = 0.0, dz = 0.0;
+#pragma unroll 1
+      for (int k = 0; k < n; ++k) {
+        const int s = (k * Q + qj) * Q + qi;
+        v += N[qk * n + k] * B[0][s]; dx += N[qk * n + k] * B[1][s]; dy += N[qk * n + k] * B[2][s]; dz += D[qk * n + k] * B[0][s];
+      }
+      xq[e] = v; J[e][0] = dx; J[e][1] = dy; J[e][2] = dz;
+      __syncthreads(); // X, A, B are rewritten for the next coordinate / cell
+    }
+    const double det = invert3(J, K);
+    const double jxw = fabs(det) * w[qi] * w[qj] * w[qk];
+    const double s = jxw * kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
+    double *c = coef + cell * cell_stride + coef_off<Q>(qi, qj + Q * qk);
+    if (n_planes == 1) c[0] = s;
+    else {
+      c[0 * plane_stride] = s * (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]);
+      c[1 * plane_stride] = s * (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]);
+      c[2 * plane_stride] = s * (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]);
+      c[3 * plane_stride] = s * (K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2]);
+      c[4 * plane_stride] = s * (K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2]);
+      c[5 * plane_stride] = s * (K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2]);
+    }
+  }
+}
+
+// diag(A) of an over-integrated handle: diag_ijk += sum_abc S_de(a,b,c) X_de[a,i] Y_de[b,j] Z_de[c,k] with the entrywise products N*N, D*D, N*D, now
+// Q x n, as 1-D factors -- six transposed sum-factorised contractions per cell (diagonal_kernel's, rectangular); the mass class (n_planes == 1):
+// (N*N x N*N x N*N)^T applied to the one plane.  One cell per workgroup, Q^3 threads.
+template <int n>
+__global__ void __launch_bounds__((n + 1) * (n + 1) * (n + 1)) overint_diagonal_kernel(const uint32_t *l2g, const double *coef, uint64_t plane_stride, uint64_t cell_stride,
+                                                                                       const double *tab, uint32_t n_cells, int n_planes, double *diag)
+{
+  constexpr int Q = n + 1, n2 = n * n, n3 = n2 * n, Q2 = Q * Q, Q3 = Q2 * Q;
+  __shared__ double S[Q3], T1[Q2 * n], T2[Q * n2], NN[Q * n], DD[Q * n], ND[Q * n];
+  const int tid = threadIdx.x, qi = tid % Q, qj = (tid / Q) % Q, qk = tid / Q2;
+  if (tid < Q * n) {
+    const double a = tab[tid], b = tab[Q * n + tid];
+    NN[tid] = a * a;
+    DD[tid] = b * b;
+    ND[tid] = a * b;
+  }
+  __syncthreads();
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    double acc = 0.0;
+    for (int c = 0; c < n_planes; ++c) {
+      const bool mass = n_planes == 1;
+      S[tid] = coef[(uint64_t)c * plane_stride + cell * cell_stride + coef_off<Q>(qi, qj + Q * qk)]; // S[qi + Q (qj + Q qk)]
+      __syncthreads();
+      const double *X = (!mass && c == 0) ? DD : (!mass && (c == 3 || c == 4)) ? ND : NN;
+      const double *Y = (!mass && c == 1) ? DD : (!mass && (c == 3 || c == 5)) ? ND : NN;
+      const double *Z = (!mass && c == 2) ? DD : (!mass && (c == 4 || c == 5)) ? ND : NN;
+      for (int s = tid; s < Q2 * n; s += Q3) { // T1[k][qj][qi] = sum_qk Z[qk][k] S
+        const int ab = s % Q2, k = s / Q2;
+        double v = 0.0;
+        for (int q = 0; q < Q; ++q) v += Z[q * n + k] * S[q * Q2 + ab];
+        T1[s] = v;
+      }
+      __syncthreads();
+      for (int s = tid; s < Q * n2; s += Q3) { // T2[k][j][qi] = sum_qj Y[qj][j] T1
+        const int a = s % Q, j = (s / Q) % n, k = s / (Q * n);
+        double v = 0.0;
+        for (int q = 0; q < Q; ++q) v += Y[q * n + j] * T1[(k * Q + q) * Q + a];
+        T2[s] = v;
+      }
+      __syncthreads();
+      if (tid < n3) {
+        const int i = tid % n, kj = tid / n;
+        double v = 0.0;
+        for (int q = 0; q < Q; ++q) v += X[q * n + i] * T2[kj * Q + q];
+        acc += (mass || c < 3) ? v : 2.0 * v;
+      }
+      __syncthreads(); // S, T1, T2 are rewritten for the next plane / cell
+    }
+    if (tid < n3) atomic_add_f64(diag + l2g[cell * n3 + tid], acc);
+  }
+}
+
 } // namespace bp5

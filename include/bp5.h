@@ -45,7 +45,9 @@ const char *bp5_strerror(int status);
 const char *bp5_last_error(void); /* detail of the last failure on this thread */
 
 enum { BP5_QUAD_GAUSS = 0, /* QGauss<1>(p+1), bp5/step-64.cu:246 (reference default) */
-       BP5_QUAD_GLL = 1    /* QGaussLobatto<1>(p+1), bp5/step-64.cu:244 (COLLOCATION) */ };
+       BP5_QUAD_GLL = 1,   /* QGaussLobatto<1>(p+1), bp5/step-64.cu:244 (COLLOCATION) */
+       BP5_QUAD_GAUSS_OVER = 2 /* QGauss<1>(p+2): CEED BP1 - BP4; the n_q_points_1d = p + 2 of FEEvaluationGL<dim, p, n_q_points_1d, n_components>,
+                                  bp5/fe_evaluation_gl.h:28.  See "over-integration" at bp5_mf_create */ };
 
 enum { BP5_COEF_ONE = 0,   /* kappa == 1: the reference folds only JxW, bp5/step-64.cu:107-113 */
        BP5_COEF_STEP64 = 1 /* kappa = 10/(0.05+2|x|^2), step-64/step-64.cu:117 */ };
@@ -55,8 +57,14 @@ enum { BP5_COEF_ONE = 0,   /* kappa == 1: the reference folds only JxW, bp5/step
 /* ------------------------------------------------------------------------------------------ */
 /* host-only helpers (run without a GPU)                                                       */
 
+/* Quadrature points per direction: Q = degree + 1 for BP5_QUAD_GAUSS and BP5_QUAD_GLL, degree + 2 for BP5_QUAD_GAUSS_OVER.
+ * BP5_ERR_INVALID for a degree outside 1..BP5_MAX_DEGREE or an unknown quadrature id. */
+int bp5_quadrature_points_1d(int degree, int quadrature, int *n_q);
+
 /* 1-D data of FE_Q(degree) on GLL nodes with the chosen quadrature, all on [0,1]:
- * nodes[n], pts[n], w[n], N[q*n+i] = phi_i(x_q), D[q*n+i] = phi_i'(x_q), n = degree+1.
+ * nodes[n], pts[Q], w[Q], N[q*n+i] = phi_i(x_q), D[q*n+i] = phi_i'(x_q), n = degree+1, q < Q = bp5_quadrature_points_1d
+ * (Q == n but for BP5_QUAD_GAUSS_OVER, whose tables are rectangular: (n + 1) x n entries each).  Bitwise (anti)symmetric under
+ * x -> 1 - x: N[q][i] == N[Q-1-q][n-1-i], D[q][i] == -D[Q-1-q][n-1-i].
  * Replaces the shape_values/shape_gradients tables MatrixFree::reinit builds
  * (call site bp5/step-64.cu:243-248). */
 int bp5_shape_tables(int degree, int quadrature, double *nodes_host, double *pts_host, double *w_host,
@@ -187,7 +195,27 @@ enum { BP5_HANG_FACE_X = 1, BP5_HANG_FACE_Y = 2, BP5_HANG_FACE_Z = 4,
        BP5_HANG_EDGE_X = 512, BP5_HANG_EDGE_Y = 1024, BP5_HANG_EDGE_Z = 2048 };
 
 /* == MatrixFree::reinit(mapping, dof_handler, constraints, quad, additional_data),
- *    bp5/step-64.cu:234-248.  Uploads the flat arrays; computes nothing yet. */
+ *    bp5/step-64.cu:234-248.  Uploads the flat arrays; computes nothing yet.
+ *
+ * Over-integration, desc->quadrature == BP5_QUAD_GAUSS_OVER: Q = p + 2 Gauss points per direction on n = p + 1 nodes (CEED BP1 - BP4; deal.II's
+ * FEEvaluation<dim, p, n_q_points_1d = p + 2>, the ordinary way to over-integrate a deformed geometry or a variable coefficient).  On affine cells
+ * with a constant coefficient the operator equals the Gauss(p+1) one to rounding; on deformed cells or with BP5_COEF_STEP64 it does not.
+ *   operators       BP5_OP_POISSON (CEED BP3) and BP5_OP_MASS (bp5_mf_set_operator; CEED BP1), as kernels of their own: apply_pencil_q_kernel and
+ *                   apply_pencil_mass_q_kernel, Q^2 lanes per cell, rectangular Q x n contractions, atomic scatter (not bitwise reproducible);
+ *                   bp5_mf_get_apply_variant reports 0, the pencil kernel, on every mesh -- also on cell bricks where a p + 1 handle resolves to 56;
+ *   metric array    bp5_mf_coef_size = planes * n_cells * Q^3 doubles (6 planes, or 1 for the mass operator), each plane in the pair layout of
+ *                   bp5_mf_compute_merged_metric TAKEN AT Q: coef[c*n_cells*Q^3 + cell*Q^3 + off_Q(qi, qj + Q*qk)], off_Q the formula there with Q for n
+ *                   (lane ab = qj + Q qk owns the x-pencil qi = 0 .. Q-1); bp5_mf_metric_to_reference_layout returns [c][cell][qi + Q (qj + Q qk)];
+ *   entry points    everything that is operator-agnostic works with the same dst contracts: bp5_mf_compute_merged_metric, bp5_apply (zero_dst 0 / 1),
+ *                   bp5_apply_cells (accumulates, ragged ranges), bp5_apply_distributed (the atomic kernels' unsplit and three-phase schedules),
+ *                   bp5_copy_constrained, bp5_compute_diagonal (also inverted), bp5_cg_solve in both variants (separate dot-product kernels:
+ *                   bp5_cg_result.dot_products_fused is 0), bp5_cg_solve_operator, bp5_cg_solve_preconditioned, bp5_chebyshev_*; n_constrained == 0 is
+ *                   fine (BP1 has no boundary condition).  bp5_assemble_rhs and bp5_l2_norm_solution keep their own Gauss(p+1) tables: their definition;
+ *   refusals        BP5_ERR_UNSUPPORTED, decided before any launch and in either call order, bp5_last_error names the "quadrature": BP5_OP_HELMHOLTZ,
+ *                   hanging-node masks (by bp5_mf_create itself), BP5_GEOM_AFFINE, BP5_METRIC_F32, every apply variant other than 0,
+ *                   bp5_apply_components* and bp5_cg_solve_components* (block vectors: CEED BP2 / BP4), bp5_mf_get_data, bp5_mg_create with such a
+ *                   level.  The facade's MatrixFree::reinit refuses the id too (its device-side FEEvaluation holds n_q_points_1d == p + 1):
+ *                   examples/bp5_bp3.hip shows a native operator class over this descriptor. */
 int bp5_mf_create(const bp5_mf_desc *desc, bp5_mf **out);
 int bp5_mf_destroy(bp5_mf *mf);
 int bp5_mf_set_stream(bp5_mf *mf, void *hip_stream);
@@ -244,7 +272,8 @@ int bp5_mf_set_metric_precision(bp5_mf *mf, int precision);
 int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision);
 /* number of doubles of the merged-metric array: 6 * n_cells * (p+1)^3  (bp5/step-64.cu:253-254); 7 planes for BP5_OP_HELMHOLTZ, 1 plane
  * (n_cells * (p+1)^3) for BP5_OP_MASS;
- * BP5_METRIC_F32: ceil(6 * n_cells * (p+1)^3 / 2) */
+ * BP5_METRIC_F32: ceil(6 * n_cells * (p+1)^3 / 2);
+ * BP5_QUAD_GAUSS_OVER: 6 * n_cells * (p+2)^3, or n_cells * (p+2)^3 for BP5_OP_MASS */
 int bp5_mf_coef_size(const bp5_mf *mf, size_t *n_doubles);
 
 /* == mf_data.evaluate_coefficients(JacobianFunctor), bp5/step-64.cu:84-114,256-258:
@@ -269,7 +298,7 @@ int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef);
 enum { BP5_GEOM_MERGED6 = 0, BP5_GEOM_AFFINE = 1 };
 int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode);
 /* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop); coef_ref: 6 n_cells (p+1)^3 DOUBLES in either precision
- * (BP5_OP_HELMHOLTZ: 7 planes; BP5_OP_MASS: the one plane as [cell][q]) */
+ * (BP5_OP_HELMHOLTZ: 7 planes; BP5_OP_MASS: the one plane as [cell][q]; BP5_QUAD_GAUSS_OVER: [c][cell][qi + Q (qj + Q qk)], Q = p + 2) */
 int bp5_mf_metric_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref);
 
 /* MatrixFree::Data mirror (bp5/fe_evaluation_gl.h:112-120, bp5/step-64.cu:94-97):

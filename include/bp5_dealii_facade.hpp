@@ -157,6 +157,10 @@ public:
   void reinit(const bp5_mf_desc &desc, const AdditionalData & = AdditionalData())
   {
     static_assert(dim == 3, "this build covers dim == 3");
+    // (the facade's device-side FEEvaluation and the table buffers below hold n_q_points_1d == p + 1: an operator on Gauss(p+2) points is a
+    // native one over the C ABI, see examples/bp5_bp3.hip)
+    if (desc.quadrature == BP5_QUAD_GAUSS_OVER)
+      throw std::runtime_error("MatrixFree::reinit (facade): Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER) is not supported: n_q_points_1d == fe_degree + 1 only");
     if (mf) { bp5_mf_destroy(mf); mf = nullptr; }
     check(bp5_mf_create(&desc, &mf));
     degree = desc.degree;
