@@ -814,6 +814,39 @@ int build_carry_tables(bp5_mf *mf, bp5_mf::DevPlan *dp, const std::vector<uint32
   return BP5_OK;
 }
 
+// Fused vector update (BLK_UPD, BP5_TUNE_FUSED_UPDATE): the block kernel may apply the merged solver's update to the interior run of every brick
+// (lattice entity (1,1,1)) when those runs are disjoint, together cover exactly the DoFs [0, n_int), every one of their DoFs is touched by its
+// block alone, owned and unconstrained -- what bp5_mesh_create_brick's block-major numbering produces (interior class first; the planes of the
+// domain boundary are brick planes).  Returns n_int, or 0 for a plan (a mesh numbered by someone else) without that property.
+static uint32_t interior_runs_cover(const bp5_mf *mf, int p, const TeamPlanHost &h, const std::vector<uint32_t> &lat)
+{
+  const size_t ng = h.off.size() - 1;
+  std::vector<std::pair<uint32_t, uint32_t>> runs(ng);
+  bool ok = true;
+#pragma omp parallel for schedule(dynamic, 16) reduction(&& : ok)
+  for (int64_t g = 0; g < (int64_t)ng; ++g) {
+    const uint32_t *row = lat.data() + (size_t)g * BLOCK_LATTICE_WORDS;
+    const uint32_t hdr = row[54];
+    if (!(hdr >> 31)) { ok = false; continue; }
+    const uint32_t len = ((hdr & 255u) * p - 1u) * (((hdr >> 8) & 255u) * p - 1u) * (((hdr >> 16) & 255u) * p - 1u), dof = row[27 + 13], slot = row[13];
+    runs[g] = {dof, len};
+    if (!len || (uint64_t)h.off[g] + slot + len > h.off[g + 1]) { ok = false; continue; }
+    const uint32_t *l = h.dofs.data() + h.off[g] + slot;
+    for (uint32_t k = 0; k < len; ++k)
+      if (l[k] != ((dof + k) | 0x80000000u)) { ok = false; break; } // consecutive, and bit 31: no other block touches it
+  }
+  if (!ok) return 0;
+  std::sort(runs.begin(), runs.end());
+  uint64_t end = 0;
+  for (const auto &r : runs) {
+    if (r.first != end) return 0;
+    end += r.second;
+  }
+  if (end == 0 || end > mf->n_owned) return 0;
+  for (uint64_t i = 0; i < end; ++i) if (mf->h_constrained[i]) return 0;
+  return (uint32_t)end;
+}
+
 // key > 0: uniform teams of `key` cells (team kernel); key < 0: cell blocks walked in passes of
 // -key cells (block kernel) -- the caller's blocks if given, else groups of `default_block` cells
 int get_plan_raw(bp5_mf *mf, int key, bp5_mf::DevPlan **dpo, int default_block)
@@ -900,6 +933,7 @@ int get_plan_raw(bp5_mf *mf, int key, bp5_mf::DevPlan **dpo, int default_block)
         if (!faces.empty()) mark_carry_faces(h, faces, run_off, runs, lat, dp);
         BP5_TRY(upload(&dp.lattice, lat.data(), lat.size()));
         BP5_TRY(upload(&dp.cell_pos, cpos.data(), cpos.size()));
+        if (dp.n_lattice_blocks == (uint32_t)(h.off.size() - 1)) dp.upd_n_int = interior_runs_cover(mf, mf->degree, h, lat);
       } else
         dp.n_lattice_blocks = 0;
     } else
@@ -1587,6 +1621,7 @@ static void tuning_from_environment(bp5_mf *mf)
   mf->tune[BP5_TUNE_INTERIOR_STORES] = env_int("BP5_INTERIOR_STORES", 1) != 0;
   mf->tune[BP5_TUNE_GHOST_COMBINE_ON_COMM] = env_int("BP5_GHOST_COMBINE_ON_COMM", 0) != 0;
   mf->tune[BP5_TUNE_FACE_CARRY] = env_int("BP5_FACE_CARRY", 1) != 0;
+  { const int v = env_int("BP5_FUSED_UPDATE", -1); mf->tune[BP5_TUNE_FUSED_UPDATE] = (v >= -1 && v <= 1) ? v : -1; }
 }
 extern "C" int bp5_mf_set_tuning(bp5_mf *mf, int knob, int value)
 {
@@ -1597,6 +1632,9 @@ extern "C" int bp5_mf_set_tuning(bp5_mf *mf, int knob, int value)
       break;
     case BP5_TUNE_UPDATE_NT:
       if (value < -1 || value > 1) return fail(BP5_ERR_INVALID, "BP5_TUNE_UPDATE_NT: -1, 0 or 1");
+      break;
+    case BP5_TUNE_FUSED_UPDATE:
+      if (value < -1 || value > 1) return fail(BP5_ERR_INVALID, "BP5_TUNE_FUSED_UPDATE: -1, 0 or 1");
       break;
     case BP5_TUNE_COMBINE_WG_PER_CU:
       if (value < 0 || value > 32) return fail(BP5_ERR_INVALID, "BP5_TUNE_COMBINE_WG_PER_CU: 0 ... 32");
@@ -2122,6 +2160,11 @@ struct SolveState {
   bool gather_in_flight = false; // the solver started the ghost gather of p under its update kernel
   // one rank, separate dot-product kernel: dst arrives zeroed (the update kernel stored the zeros) / the Dirichlet copy follows in the dots kernel
   bool dst_prezeroed = false, copies_dirichlet = false;
+  // merged solve with the vector update of the brick interiors inside the block kernel (OperatorPlan::fused_update): what the next operator
+  // application is to apply (FuseState::upd_*; 0: nothing -- the first iteration)
+  int upd_mode = 0;
+  double *upd_x = nullptr;
+  const double *upd_diag = nullptr;
   // profile == 2: stamps of the iteration `phase_it` (0-based; stamps beyond MAX_ITERS are dropped); bit k of phase_recorded[it]: mark k recorded
   bool phase_on = false;
   int phase_it = 0;
@@ -2301,7 +2344,7 @@ static int solver_vmult(bp5_mf *mf, SolveState &ss, const double *coef, double *
   BP5_TRY(prof.mark(1));
   if (prof.on) call.mark_event = mf->ev_pool[prof.used + 2];
   FuseState fuse;
-  if (fusing) { fuse.p = src; fuse.r = fuse_r; call.fuse = &fuse; }
+  if (fusing) { fuse.p = src; fuse.r = fuse_r; fuse.upd_mode = ss.upd_mode; fuse.upd_x = ss.upd_x; fuse.upd_diag = ss.upd_diag; call.fuse = &fuse; }
   call.overwrite = zero;
   BP5_TRY(launch_apply(mf, call, coef, src, dst));
   if (fusing) *n_cols = fuse.n_cols;
@@ -2389,6 +2432,7 @@ struct OperatorPlan {
   bool fused_dots = false; // the operator kernels form the dot products with its result
   bool fold_small = false; // the dot-product kernel applies the Dirichlet copy ...
   bool prezero = false;    // ... and the update kernel stores the zeros an atomic scatter needs
+  uint32_t fused_update = 0; // merged solver: the block kernel updates the DoFs [0, fused_update & ~1) itself (brick interiors); 0: the update kernel all of them
   int schedule = 0;        // bp5_cg_result.exchange_schedule
 };
 // own_operator: the library's operator, not a callback.  fusable: no preconditioner enters the dot products the kernel would form
@@ -2415,6 +2459,16 @@ static int plan_operator(bp5_mf *mf, bool own_operator, bool fusable, SolveState
       // automatic: one launch, ghost rows combined first, exchange under the owned-row combine (needs the run-length combine windows)
       late = op.fused_dots && mf->overlap == 2 && (dp->n_shared == 0 || dp->cr_tile); // (variant 56 / 63: the run-length pass wherever its tables exist)
     }
+  }
+  // BP5_TUNE_FUSED_UPDATE: the vector update of the brick interiors inside the block kernel -- one-rank solves with fused dot products on the p = 4
+  // lattice build of variant 56, on a plan whose interior runs cover a leading range of the DoFs (interior_runs_cover); -1: where the vectors do
+  // not fit the memory-side cache anyway.  Everything else takes the separate update launch over all DoFs
+  if (op.fused_dots && !op.dist && !mf->comm && mf->n_ghost == 0 && mf->degree == 4 && mf->tune[BP5_TUNE_FUSED_UPDATE] != 0 &&
+      mf->operator_kind == BP5_OP_POISSON && !mf->has_hanging && !mf->overint() && effective_variant(mf, 0, mf->n_cells) == 56) {
+    bp5_mf::DevPlan *dp = nullptr;
+    BP5_TRY(get_plan_raw(mf, -block_cpt(mf), &dp));
+    const bool by_size = mf->tune[BP5_TUNE_FUSED_UPDATE] < 0;
+    if (dp->lattice && dp->n_lattice_blocks == dp->n_groups && dp->upd_n_int >= 2 && (!by_size || mf->n_local() > STREAMING_MAX_DOFS)) op.fused_update = dp->upd_n_int;
   }
   ss.exchange = split ? EXCHANGE_BOUNDARY_FIRST : late ? EXCHANGE_GHOST_ROWS_FIRST : EXCHANGE_NONE;
   // whole-range launches of a distributed fused solve walk the ghost-touching bricks first in EITHER exchange schedule: same workgroup
@@ -2599,7 +2653,11 @@ static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, vo
   hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), dim3(VB), 0, s, mf->d_partials, grid1, mf->d_sc + SC_GG, (const int *)nullptr);
   KERNEL_CHECK();
   BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
-  hipLaunchKernelGGL(cgm_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
+  // Fused update (op.fused_update, plan_operator): in the iterations after the first the block kernel updates the brick interiors [0, n_first)
+  // itself and the update launch shrinks to the rest.  A stopped solve: the block kernel is a no-op, so the in-loop rest launch is one too, and the x
+  // epilogue stays pending (ST_HOLD) for the whole-range launch behind the loop, whatever number of stopped iterations check_every lets through
+  const size_t n_first = fused && !user ? (size_t)(op.fused_update & ~1u) : 0; // (even: the rest launch starts on a 16-byte boundary)
+  hipLaunchKernelGGL(cgm_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, n_first ? 1 : 0);
   KERNEL_CHECK();
   // update kernels: U chunks of 256 pairs per workgroup (flat launch: one trip per workgroup), all loads ahead of the first store.
   // profiles/r4 hbm_sweep: U = 1 flat 5.5-5.9 TB/s, the capped grid-stride grid of rounds 1-3 (U = 4, 2048 workgroups) 4.8-4.9
@@ -2617,6 +2675,16 @@ static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, vo
     if (mode == 1) BP5_UPD_U(1, false, false); else BP5_UPD_U(2, false, false);
 #undef BP5_UPD_U
 #undef BP5_UPD
+  };
+  const int gridr = n > n_first ? stream_grid_flat(mf, n - n_first, 2 * unroll) : 0;
+  auto launch_update_rest = [&](int mode) {
+    if (!gridr) return;
+#define BP5_UPR(M, U, NT) hipLaunchKernelGGL((cgm_update_rest_kernel<M, U, NT>), dim3(gridr), dim3(VB), 0, s, d, g, h, x, diag, n_first, n - n_first, mf->d_sc, mf->d_st)
+#define BP5_UPR_U(M, NT) do { if (unroll == 1) BP5_UPR(M, 1, NT); else if (unroll == 2) BP5_UPR(M, 2, NT); else BP5_UPR(M, 4, NT); } while (0)
+    if (streaming) { if (mode == 1) BP5_UPR_U(1, true); else BP5_UPR_U(2, true); return; }
+    if (mode == 1) BP5_UPR_U(1, false); else BP5_UPR_U(2, false);
+#undef BP5_UPR_U
+#undef BP5_UPR
   };
   // fused iteration across ranks: the values of the NEW p at the DoFs this rank sends are computed into the send buffer first, so the
   // ghost gather of p runs on the communication stream underneath the update kernel (which touches owned entries only); the operator
@@ -2639,7 +2707,10 @@ static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, vo
     const int mode = it == 1 ? 0 : it % 2 == 0 ? 1 : 2;
     BP5_TRY(phase_mark(mf, ss, 0));
     if (early_gather) { BP5_TRY(gather_under_update(mode)); ss.gather_in_flight = true; }
-    if (mode != 0) launch_update(mode); // (mode 0, p = -D r: written by cgm_init_kernel already)
+    if (mode != 0) { // (mode 0, p = -D r: written by cgm_init_kernel already)
+      if (n_first) launch_update_rest(mode); else launch_update(mode);
+    }
+    ss.upd_mode = n_first ? mode : 0; ss.upd_x = x; ss.upd_diag = diag;
     KERNEL_CHECK();
     BP5_TRY(phase_mark(mf, ss, 1));
     const bool one_launch = fused && !mf->comm; // no all-reduce between the local sums and the scalar step
@@ -2676,6 +2747,7 @@ static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, vo
   // iteration has been done and nothing is pending
   if (prm->max_iter > 0) {
     launch_update(1);
+    if (n_first) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(mf->d_st + ST_HOLD), 0, 1, s)); // the epilogue is applied: the control step may clear the flag
     hipLaunchKernelGGL(cgm_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st);
     KERNEL_CHECK();
   }

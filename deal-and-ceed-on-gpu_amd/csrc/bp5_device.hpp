@@ -109,7 +109,7 @@ struct bp5_mf {
   int wait_value_ok = -1;     // -1 not probed; 1: hipDeviceAttributeCanUseStreamWaitValue AND the producer / consumer self-check saw a mid-kernel release
   int can_wait_value = -1;    // wait_value_ok and not switched off by BP5_TUNE_BOUNDARY_FIRST = 0
   // per-handle tuning / A-B knobs (bp5.h: BP5_TUNE_*): initial values from the environment, read once by bp5_mf_create
-  int tune[BP5_TUNE_COUNT] = {1, 1, 0, 1, 1, 1, 1, -1, 16, 1, 0, 1};
+  int tune[BP5_TUNE_COUNT] = {1, 1, 0, 1, 1, 1, 1, -1, 16, 1, 0, 1, -1};
   bool cell_interiors_first = false; // the mesh numbers the DoFs strictly inside a cell ahead of all others, cell after cell, x fastest (bp5_mesh_desc.dof_numbering = 2)
   // solver workspace
   double *d_partials = nullptr, *d_sc = nullptr, *d_scalar = nullptr;
@@ -154,6 +154,9 @@ struct bp5_mf {
     uint32_t *lattice = nullptr;
     uint16_t *cell_pos = nullptr;
     uint32_t n_lattice_blocks = 0;
+    // fused vector update (BP5_TUNE_FUSED_UPDATE): the interior runs of the lattice blocks are disjoint, cover exactly the DoFs [0, upd_n_int),
+    // hold no Dirichlet DoF and nothing another block touches (get_plan_raw: interior_runs_cover); 0: the plan does not qualify
+    uint32_t upd_n_int = 0;
     std::vector<double> h_cost;                       // [n_groups+1] prefix sum of the estimated cost of the blocks (pass units)
     // block ranges of the persistent workgroups, one device array per (n_wg, first block, end block) ever launched: the
     // interior / boundary ranges of the overlapped schedule alternate, nothing is freed or re-uploaded inside a solve
@@ -186,6 +189,10 @@ struct FuseState {
   const double *p = nullptr, *r = nullptr;
   uint32_t n_cols = 0;        // columns of d_partials written so far (block kernel workgroups, then the combine pass, then the unpack kernels)
   bool ghosts_zeroed = false; // the exchange's unpack kernel has zeroed the ghost ranges of v and p
+  // the launch also applies the merged solver's vector update to the brick interiors (BLK_UPD; cg_solve_merged decided that the plan qualifies)
+  int upd_mode = 0;           // 0: no; 1 / 2: cgm_update_one<1 / 2>
+  double *upd_x = nullptr;
+  const double *upd_diag = nullptr;
 };
 // What an apply variant number means (include/bp5.h: bp5_mf_set_apply_variant), the ONE place that knows the ranges: 1xx = variant xx with the
 // global-atomic scatter, 0-6 pencil shapes, 10-14 team kernel, 48-63 block kernel (56 its default shape, the others A/B siblings and older shapes),
@@ -573,6 +580,12 @@ inline int launch_block_t(bp5_mf *mf, ApplyCall &call, const double *coef, const
     }
   }
   bp.cg_r = call.fuse ? call.fuse->r : nullptr; bp.dot_partials = mf->d_partials; bp.n_owned = mf->n_owned; bp.cg_state = mf->d_st;
+  if constexpr ((ABL & BLK_UPD) != 0) { // the vector update of the brick interiors: one-part whole-range launches of a merged solve on a plan that qualifies
+    if (!call.fuse || !call.fuse->upd_mode || !call.fuse->r || !dp->upd_n_int || sub_range || bp.n_parts != 1 || mf->n_ghost)
+      return fail(BP5_ERR_INVALID, "the fused-update build needs a one-rank merged solve on a plan whose brick interiors are numbered first");
+    bp.upd_p = const_cast<double *>(src); bp.upd_r = const_cast<double *>(call.fuse->r); bp.upd_v = dst; bp.upd_x = call.fuse->upd_x;
+    bp.upd_diag = call.fuse->upd_diag; bp.upd_sc = mf->d_sc; bp.upd_mode = (uint32_t)call.fuse->upd_mode; bp.upd_end = dp->upd_n_int & ~1u;
+  }
   bp.stamps = nullptr;
   if (ABL & BLK_STAMPS) {
     if (!mf->d_stamps) HIP_TRY(hipMalloc((void **)&mf->d_stamps, 4096 * 16 * sizeof(unsigned long long)));
@@ -736,7 +749,8 @@ struct DefaultBlockBuilds {
 template <>
 struct DefaultBlockBuilds<4> {
   static constexpr int D = BLK_DEFAULT, F = BLK_FUSE, LATC = BLK_LATT | BLK_CARRY;
-  using list = BuildList<Bld<D | LATC | BLK_NTM, true>, Bld<D | F | LATC | BLK_NTM, true>, Bld<D | LATC>, Bld<D | F | LATC>, Bld<D>, Bld<D | F>,
+  using list = BuildList<Bld<D | F | LATC | BLK_UPD | BLK_NTM>, Bld<D | F | LATC | BLK_UPD>, // + the merged CG's vector update of the brick interiors (both quadratures)
+                         Bld<D | LATC | BLK_NTM, true>, Bld<D | F | LATC | BLK_NTM, true>, Bld<D | LATC>, Bld<D | F | LATC>, Bld<D>, Bld<D | F>,
 #ifdef BP5_TIMING_BUILDS // variant 63: the rolling metric prefetch (BlockPass::ROLL) -- a measured loss (profiles/r4 d_*)
                          Bld<D | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | F | BLK_LATT | BLK_NTM | BLK_ROLL, true>, Bld<D | BLK_LATT | BLK_ROLL, true>,
                          Bld<D | F | BLK_LATT | BLK_ROLL, true>,
@@ -785,7 +799,14 @@ inline int launch_block_default(bp5_mf *mf, ApplyCall &call, const double *coef,
   if (dp->packed && variant != 49) {
     want = BLK_DEFAULT | cls | (call.fuse ? BLK_FUSE : 0);
     if (dp->lattice && dp->n_lattice_blocks == dp->n_groups && variant != 48) want |= BLK_LATT | BLK_CARRY; // every block a lattice block: closed-form indices, no per-DoF index stream
-    if (streaming_accesses(mf)) want |= BLK_NTM;
+    // the merged solver asks for its vector update inside the launch (it has checked plan, degree and variant: fused_update_wanted); such a launch
+    // reads the metric non-temporally at every size unless told otherwise -- p' and r' are to stay in the memory-side cache until they are read
+    const bool upd = call.fuse && call.fuse->upd_mode != 0;
+    if (upd) {
+      if (DEG != 4 || !(want & BLK_LATT) || cls != 0) return fail(BP5_ERR_INVALID, "the fused vector update needs the p = 4 lattice build of the Poisson operator");
+      want |= BLK_UPD;
+    }
+    if (upd && mf->streaming < 0 ? true : streaming_accesses(mf)) want |= BLK_NTM;
   } else { // more than 128 runs in some block: only the Poisson operator at p = 4 keeps kernels for such plans, none of them fused
     if (DEG != 4 || cls != 0) return fail(BP5_ERR_UNSUPPORTED, "variant " + std::to_string(variant) + " needs packed indices (<= 128 runs per cell block)");
     if (call.fuse) return fail(BP5_ERR_INVALID, "fused dot products need the packed block kernel");

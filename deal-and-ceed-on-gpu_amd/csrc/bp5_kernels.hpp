@@ -40,7 +40,7 @@ struct ShapeArg { // passed by value as a kernel argument: uniform -> scalar loa
 // team kernels read the AFFINE, HANG, HELM and F32M bits of their own mask with the same meaning.  Bits below 1024 (and a few probes above, spelled as
 // numbers where they are used) are timing-only ablations: no write-out, no metric loads, no gather ...
 enum : int {
-  BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_PACK = 262144,
+  BLK_AFFINE = 1024, BLK_SINGLE = 2048, BLK_STAMPS = 4096, BLK_SEQ = 8192, BLK_RUNS = 16384, BLK_NTM = 32768, BLK_UPD = 131072, BLK_PACK = 262144,
   BLK_STAGE = 524288, BLK_FUSE = 1048576, BLK_HANG = 2097152, BLK_LDSADD = 4194304, BLK_HELM = 8388608, BLK_LATT = 16777216,
   BLK_ROLL = 67108864, BLK_CARRY = 268435456,
   BLK_F32M = 536870912, // the metric planes are float (bp5_mf_set_metric_precision)
@@ -1226,6 +1226,8 @@ __device__ __forceinline__ void load_pencil_idx(const T *base, int ab, T (&v)[n]
 // and a wave on another SIMD can pass the barrier and read-modify-write the same word first (lost update; seen as
 // rare wrong sums in multi-round passes at full size).  tools/check_lds_barrier.py checks the ISA for this pattern.
 __device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// ... and every vector memory access of the wave (loads returned, stores acknowledged)
+__device__ __forceinline__ void vmem_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------ fused operator on a block vector
 // FEEvaluation<dim, p, n_q, n_components> on a BlockVector over ONE scalar DoFHandler (the reference carries n_components_ and asserts it
@@ -1642,7 +1644,18 @@ struct BlockPlan {
   uint32_t dot_col0;          // first column of this launch (the boundary-first schedule runs the bricks in two launches)
   uint32_t n_owned;           // dot products run over owned entries only
   const int *cg_state;        // st[ST_DONE] != 0: the solve has stopped, the launch is a no-op (iterate frozen)
+  // builds with ABL & BLK_UPD (the merged CG's vector update of the brick interiors inside this launch, apply_block_kernel: update_interior):
+  // src == upd_p.  The interior runs of the bricks cover [0, n_int) (verified on the host); the launch updates [0, upd_end), the rest goes
+  // through cgm_update_rest_kernel ahead of it
+  double *upd_p, *upd_r, *upd_x; // search direction (read AND written), residual, iterate
+  const double *upd_v;        // A p of the previous iteration (== dst: an interior entry is read here before this launch's write-out stores it)
+  const double *upd_diag;     // inverse diagonal, NULL = identity
+  const double *upd_sc;       // the solver's device scalars (alpha, beta, ...)
+  uint32_t upd_mode;          // 1: cgm_update_one<1>, 2: cgm_update_one<2> (x as well)
+  uint32_t upd_end;           // n_int rounded down to an even index (16-byte accesses of the rest launch start there)
 };
+// (defined with the CG kernels below)
+template <int MODE> __device__ __forceinline__ void block_update_run(const BlockPlan &bp, uint32_t lo, uint32_t hi, int t);
 
 // register set of one pass (cell ids, positions, gathered values, metric)
 template <int n, bool AFFINE, int NPL = 6, bool ROLL = false, typename MT = double>
@@ -2493,6 +2506,28 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
       return;
     }
   }
+  // UPD: the merged CG's update of p, r (and x) on the INTERIOR run of every brick happens here, right before the brick is processed, instead of
+  // in the update launch a kernel earlier: p' and r' are then read back (gather, fused write-out) tens of microseconds after they were
+  // written, from the memory-side cache, not from HBM.  update_interior(g) runs the run of physical block g: lattice entity (1,1,1), first DoF
+  // in lattice word 27 + 13, (NX - 1)(NY - 1)(NZ - 1) DoFs; all 256 threads, the arithmetic of cgm_update_one (same bits as the update kernel).
+  // Why the plain (L1-cached) gathers and r loads that follow stay correct:
+  //  - the interior DoFs of a brick are read and written by that brick's workgroup only;
+  //  - within a workgroup (not in threadgroup-split mode) the waves share the CU's L1, through which every store goes: a wave's stores are
+  //    visible to the others once it has waited for them (vmcnt(0)) and all have passed a barrier -- a barrier of its own ahead of the first gather for
+  //    the workgroup's first brick (top of the pass loop), the write-out barrier of brick b (finish_pass) for brick b + 1, whose update runs at the top of b's last pass;
+  //  - an interior run is odd (3375 doubles for a full brick), so the runs of consecutive bricks share a 128-byte line; another workgroup
+  //    writing ITS bytes of that line is byte-masked in L2, and a workgroup never reads another brick's bytes of that line for their value.
+  // The early return above (solve stopped) skips the update as well; nothing of it lives across BlockPass::run.
+  constexpr bool UPD = (ABL & BLK_UPD) != 0;
+  static_assert(!UPD || (DOTS && BP::LATT), "fused vector update: lattice blocks, fused dot products");
+  auto update_interior = [&](uint32_t g) {
+    const uint32_t *lrow = bp.lattice + (uint64_t)g * BLOCK_LATTICE_WORDS; // (uniform: scalar loads)
+    const uint32_t hdr = lrow[54], lo = lrow[27 + 13];
+    const uint32_t len = ((hdr & 255u) * P - 1u) * (((hdr >> 8) & 255u) * P - 1u) * (((hdr >> 16) & 255u) * P - 1u);
+    const uint32_t hi = lo + len < bp.upd_end ? lo + len : bp.upd_end;
+    if (bp.upd_mode == 2u) block_update_run<2>(bp, lo, hi, t);
+    else block_update_run<1>(bp, lo, hi, t);
+  };
   // The workgroup's blocks: [ba0, ba1) (part 0) then [bb0, bb1) (part 1; empty in one-part launches), walked as ONE sequence of
   // virtual block indices vb = 0 .. nb - 1 and virtual pass indices gp = 0 .. gp_end - 1; only the look-ups translate (scalar
   // arithmetic: everything here is wave-uniform)
@@ -2594,7 +2629,8 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
       enter_block(rt0, n_runs, m);
       __syncthreads();
     }
-    BP::decode_and_gather(a, A, rt0, staged, use_lattice ? lat_tab + (b & 1u) * BLOCK_LATTICE_WORDS : nullptr, a_, b_);
+    // (UPD: the first gather follows the first brick's update, at the top of the pass loop)
+    if constexpr (!UPD) BP::decode_and_gather(a, A, rt0, staged, use_lattice ? lat_tab + (b & 1u) * BLOCK_LATTICE_WORDS : nullptr, a_, b_);
   } else
     BP::issue_gather(a, A);
 
@@ -2619,6 +2655,8 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
         nx_r1 = bp.run_off[p1 + 1];
       }
       if constexpr (use_lattice) { if (t < BLOCK_LATTICE_WORDS) lat_word = bp.lattice[(uint64_t)p1 * BLOCK_LATTICE_WORDS + t]; }
+      // UPD: the next brick's interior, while only the current pass's register set is live; its first gather follows this brick's write-out barrier
+      if constexpr (UPD) update_interior(p1);
     }
     if (gp + 1 == boundary) {
       if constexpr (BP::PACK) {
@@ -2745,6 +2783,7 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
           rt[BLOCK_MAX_RUNS + t] = run_dof;
         }
       }
+      if constexpr (UPD) vmem_drain(); // this wave's stores of the next brick's p', r' (issued a pass ago) are done before the barrier
       __syncthreads(); // every wave has added its last contributions of this block
       BP5_PRIO_WO_HI
       if constexpr (CARRY) {
@@ -2856,6 +2895,16 @@ __global__ void __launch_bounds__(256, (block_wg_per_cu<P, ABL>())) apply_block_
   };
 
   while (gp < gp_end) {
+    if constexpr (UPD) {
+      // the workgroup's first brick: its interior is updated here, the stores waited for ahead of a barrier, the first gather behind it.  (Inside the
+      // loop, not in front of it: a call site ahead of the loop costs the kernel 21 / 34 spilled registers.)
+      if (gp == 0) {
+        update_interior(pb);
+        vmem_drain();
+        __syncthreads();
+        BP::decode_and_gather(a, A, run_tab, staged, lat_tab, a_, b_);
+      }
+    }
     prefetch_list();
     BP5_PRIO_HI BP::issue_loads(a, bp, B, abm, lane_ok, gp + 1 < gp_end); BP5_PRIO_LO
     const uint32_t entA2 = entry(gp + 2);
@@ -3786,7 +3835,7 @@ static __global__ void __launch_bounds__(VB) count_nonzero_kernel(const double *
 // Device-resident solver state.  sc[] doubles, st[] ints.
 enum { SC_GH = 0, SC_DH, SC_GG, SC_GDG, SC_ALPHA, SC_BETA, SC_ALPHA_OLD, SC_BETA_OLD, SC_RES, SC_RES0, SC_TOL, SC_R0 /* 7 merged dots R0..R6 */,
        SC_COUNT = SC_R0 + 7 };
-enum { ST_DONE = 0, ST_ITER, ST_PENDING, ST_MAXIT, ST_BREAKDOWN, ST_COUNT };
+enum { ST_DONE = 0, ST_ITER, ST_PENDING, ST_MAXIT, ST_BREAKDOWN, ST_HOLD, ST_COUNT };
 
 // Dirichlet copy of a block vector: dst = src on the constrained DoFs of every block (component = blockIdx.y, blocks ld apart)
 static __global__ void copy_constrained_components_kernel(const uint32_t *cdofs, uint32_t n, const double *src, double *dst, size_t ld)
@@ -3970,12 +4019,10 @@ __device__ __forceinline__ void cgm_update_one(double &p, double &r, const doubl
 // launch -- two fill kernels in the runtime -- less per iteration)
 // NTX: v (consumed here for the last time) and x (touched by nothing else) go past the caches with non-temporal accesses, so that on a mesh whose
 // vectors fit the 256 MB memory-side cache p and r are still there when the operator kernel gathers them (bp5_mf_set_streaming)
-template <int MODE, int U = 2, bool ZV = false, bool NTX = false>
-__global__ void __launch_bounds__(VB) cgm_update_kernel(double *p, double *r, typename std::conditional<ZV, double, const double>::type *v, double *x,
-                                                       const double *diag, size_t n, const double *sc, const int *st)
+template <int MODE, int U, bool ZV, bool NTX>
+__device__ __forceinline__ void cgm_update_body(double *p, double *r, typename std::conditional<ZV, double, const double>::type *v, double *x,
+                                                const double *diag, size_t n, const double *sc, const int *st, const bool done)
 {
-  const bool done = st[ST_DONE];
-  if (done && !st[ST_PENDING]) return;
   const double alpha = sc[SC_ALPHA], beta = sc[SC_BETA];
   const double aob = (MODE == 2 || done) ? sc[SC_ALPHA_OLD] / sc[SC_BETA_OLD] : 0.0;
   const bool epi_odd = done && (st[ST_ITER] & 1);
@@ -4027,6 +4074,78 @@ __global__ void __launch_bounds__(VB) cgm_update_kernel(double *p, double *r, ty
         if (touch_rp) { p[i] = pv[u].x; if (MODE != 0) r[i] = rv[u].x; }
         if (touch_x) x[i] = xv[u].x;
         if constexpr (ZV) { if (MODE != 0 && !done) v[i] = 0.0; }
+      }
+    }
+  }
+}
+template <int MODE, int U = 2, bool ZV = false, bool NTX = false>
+__global__ void __launch_bounds__(VB) cgm_update_kernel(double *p, double *r, typename std::conditional<ZV, double, const double>::type *v, double *x,
+                                                       const double *diag, size_t n, const double *sc, const int *st)
+{
+  const bool done = st[ST_DONE];
+  if (done && !st[ST_PENDING]) return;
+  cgm_update_body<MODE, U, ZV, NTX>(p, r, v, x, diag, n, sc, st, done);
+}
+// The update of a solve whose block kernel updates the brick interiors itself (BLK_UPD): the entries [first, first + n) behind them (first even:
+// 16-byte accesses), MODE 1 or 2.  A stopped solve: nothing at all -- the x epilogue belongs to the whole-range launch behind the loop (ST_HOLD)
+template <int MODE, int U, bool NTX>
+__global__ void __launch_bounds__(VB) cgm_update_rest_kernel(double *p, double *r, const double *v, double *x, const double *diag, size_t first, size_t n,
+                                                            const double *sc, const int *st)
+{
+  if (st[ST_DONE]) return;
+  cgm_update_body<MODE, U, false, NTX>(p + first, r + first, v + first, x + first, diag ? diag + first : nullptr, n, sc, st, false);
+}
+// BLK_UPD builds of apply_block_kernel: the entries [lo, hi) of one brick's interior run, all 256 threads of the workgroup (t), cgm_update_one<MODE>
+// as in cgm_update_kernel.  Pairs from lo on (16-byte accesses from an 8-byte aligned address, as the block kernel's write-out uses them; the last
+// entry of an odd run goes alone), BP5_UPD_UNROLL pairs per thread and trip with all loads of a trip ahead of its first store; every load
+// non-temporal (v and x are touched once, and nothing read here is wanted in L1), x stored non-temporally, p' and r' with plain stores: the
+// workgroup reads them next
+// (three: a full brick's 3375 entries in three trips, 168 registers and none spilled; four spills two in the Gauss build)
+#ifndef BP5_UPD_UNROLL
+#define BP5_UPD_UNROLL 3
+#endif
+template <int MODE>
+__device__ __forceinline__ void block_update_run(const BlockPlan &bp, uint32_t lo, uint32_t hi, int t)
+{
+  static_assert(MODE == 1 || MODE == 2, "the first iteration's p comes from cgm_init_kernel");
+  constexpr int U = BP5_UPD_UNROLL;
+  constexpr uint32_t TRIP = 2u * 256u;
+  const double *sc = bp.upd_sc;
+  const double alpha = sc[SC_ALPHA], beta = sc[SC_BETA];
+  const double aob = MODE == 2 ? sc[SC_ALPHA_OLD] / sc[SC_BETA_OLD] : 0.0;
+  double *const p = bp.upd_p, *const r = bp.upd_r, *const x = bp.upd_x;
+  const double *const v = bp.upd_v, *const diag = bp.upd_diag;
+  for (uint32_t base = lo + 2u * (uint32_t)t; base < hi; base += TRIP * U) {
+    bp5_d2u pv[U], rv[U], vv[U], xv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = base + (uint32_t)u * TRIP;
+      pv[u] = rv[u] = vv[u] = xv[u] = bp5_d2u{0.0, 0.0};
+      if (i + 1 < hi) {
+        pv[u] = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(p + i));
+        rv[u] = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(r + i));
+        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(v + i));
+        if (MODE == 2) xv[u] = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(x + i));
+      } else if (i < hi) {
+        pv[u].x = __builtin_nontemporal_load(p + i); rv[u].x = __builtin_nontemporal_load(r + i); vv[u].x = __builtin_nontemporal_load(v + i);
+        if (MODE == 2) xv[u].x = __builtin_nontemporal_load(x + i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = base + (uint32_t)u * TRIP;
+      if (i >= hi) continue;
+      const bool pair = i + 1 < hi;
+      double p0 = pv[u].x, p1 = pv[u].y, r0 = rv[u].x, r1 = rv[u].y, x0 = xv[u].x, x1 = xv[u].y;
+      cgm_update_one<MODE>(p0, r0, vv[u].x, x0, diag ? diag[i] : 1.0, false, false, alpha, beta, aob);
+      if (pair) {
+        cgm_update_one<MODE>(p1, r1, vv[u].y, x1, diag ? diag[i + 1] : 1.0, false, false, alpha, beta, aob);
+        *reinterpret_cast<bp5_d2u *>(p + i) = bp5_d2u{p0, p1};
+        *reinterpret_cast<bp5_d2u *>(r + i) = bp5_d2u{r0, r1};
+        if (MODE == 2) __builtin_nontemporal_store(bp5_d2u{x0, x1}, reinterpret_cast<bp5_d2u *>(x + i));
+      } else {
+        p[i] = p0; r[i] = r0;
+        if (MODE == 2) __builtin_nontemporal_store(x0, x + i);
       }
     }
   }
@@ -4089,7 +4208,9 @@ static __global__ void cgm_control_kernel(double *sc, int *st);
 // one-launch probe used seven workgroups and a device-scope fence, which cost more than it saved)
 __device__ __forceinline__ void cgm_control_step(double *sc, int *st)
 {
-  if (st[ST_DONE]) { st[ST_PENDING] = 0; return; }
+  // (ST_HOLD: a solve whose in-loop update launches cover only part of the vectors keeps the x epilogue pending for the whole-range launch behind
+  // its loop, however many stopped iterations are launched in between: cg_solve_merged)
+  if (st[ST_DONE]) { if (!st[ST_HOLD]) st[ST_PENDING] = 0; return; }
   const double *R = sc + SC_R0;
   if (!(R[0] == R[0]) || R[0] == 0.0) { st[ST_BREAKDOWN] = 1; st[ST_DONE] = 1; return; }
   sc[SC_ALPHA_OLD] = sc[SC_ALPHA];
@@ -4162,11 +4283,11 @@ static __global__ void __launch_bounds__(VB) cgm_init_kernel(const double *b, do
   acc[1] = acc[0];
   block_reduce_store<2>(acc, partials);
 }
-static __global__ void cgm_init_control_kernel(double *sc, int *st)
+static __global__ void cgm_init_control_kernel(double *sc, int *st, int hold)
 {
   sc[SC_RES0] = sc[SC_RES] = sqrt(sc[SC_GG]);
   sc[SC_ALPHA] = sc[SC_BETA] = sc[SC_ALPHA_OLD] = sc[SC_BETA_OLD] = 0.0;
-  st[ST_ITER] = 0; st[ST_PENDING] = 0; st[ST_BREAKDOWN] = 0;
+  st[ST_ITER] = 0; st[ST_PENDING] = 0; st[ST_BREAKDOWN] = 0; st[ST_HOLD] = hold;
   st[ST_DONE] = (sc[SC_RES] <= sc[SC_TOL]) ? 1 : 0;
 }
 

@@ -390,10 +390,18 @@ int bp5_mf_set_streaming(bp5_mf *mf, int policy);
  *   BP5_TUNE_FACE_CARRY        (env BP5_FACE_CARRY, default 1) block kernel on lattice bricks (p = 4): the interior of the face two CONSECUTIVE bricks of one
  *                              workgroup's range share stays in LDS from the first brick's write-out to the second's, which stores the sum as an owner store;
  *                              the combine pass of that launch skips those DoFs.  v is the same bits as without (a + b == b + a); the fused dot products are
- *                              summed over other workgroups (rounding-level differences, reproducible run to run). */
+ *                              summed over other workgroups (rounding-level differences, reproducible run to run).
+ *   BP5_TUNE_FUSED_UPDATE      (env BP5_FUSED_UPDATE, -1 | 0 | 1, default -1) merged CG with fused dot products on one rank, p = 4, lattice bricks, DoFs numbered
+ *                              brick by brick (bp5_mesh_desc.dof_numbering = 1): the block kernel applies the solver's vector update to the interior DoFs of every
+ *                              brick right before it processes the brick, and the update launch shrinks to the brick surfaces -- p and r are read back while they
+ *                              are still in the memory-side cache.  Same bits as the separate update; on such a solve p, r and x are updated by the OPERATOR launch.
+ *                              1 = wherever the plan qualifies (anything else takes the separate update silently), -1 = only above 2.4e7 local DoFs (where the
+ *                              vectors do not fit that cache from one launch to the next: -3 % per iteration at 1e8 DoFs, profiles/fused_update), 0 = off.
+ *                              Such a launch reads the metric non-temporally unless bp5_mf_set_streaming says 0. */
 enum { BP5_TUNE_LATTICE_INDICES = 0, BP5_TUNE_EARLY_GATHER = 1, BP5_TUNE_COMBINE_SIGNAL = 2, BP5_TUNE_BOUNDARY_FIRST = 3,
        BP5_TUNE_FOLD_SMALL = 4, BP5_TUNE_UPDATE_UNROLL = 5, BP5_TUNE_UPDATE_FLAT = 6, BP5_TUNE_UPDATE_NT = 7, BP5_TUNE_COMBINE_WG_PER_CU = 8,
-       BP5_TUNE_INTERIOR_STORES = 9, BP5_TUNE_GHOST_COMBINE_ON_COMM = 10, BP5_TUNE_FACE_CARRY = 11, BP5_TUNE_COUNT = 12 };
+       BP5_TUNE_INTERIOR_STORES = 9, BP5_TUNE_GHOST_COMBINE_ON_COMM = 10, BP5_TUNE_FACE_CARRY = 11, BP5_TUNE_FUSED_UPDATE = 12,
+       BP5_TUNE_COUNT = 13 };
 int bp5_mf_set_tuning(bp5_mf *mf, int knob, int value);
 int bp5_mf_get_tuning(const bp5_mf *mf, int knob, int *value);
 /* 1 when the in-launch stream wait-value schedules are available on this handle (capability + self-check, see BP5_TUNE_BOUNDARY_FIRST);
