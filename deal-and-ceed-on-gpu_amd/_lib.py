@@ -193,6 +193,12 @@ def lib():
         "bp5_cg_solve_components_distributed": (i32, [vp, vp, i32, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve": (i32, [vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_components": (i32, [vp, vp, i32, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_elasticity_coef_size": (i32, [vp, C.POINTER(sz)]),
+        "bp5_elasticity_compute_metric": (i32, [vp, vp]),
+        "bp5_elasticity_apply": (i32, [vp, vp, f64, f64, sz, vp, vp, i32]),
+        "bp5_elasticity_apply_cells": (i32, [vp, vp, f64, f64, sz, vp, vp, u32, u32]),
+        "bp5_elasticity_compute_diagonal": (i32, [vp, vp, f64, f64, sz, vp, i32]),
+        "bp5_cg_solve_elasticity": (i32, [vp, vp, f64, f64, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_operator": (i32, [vp, VMULT_FN, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_preconditioned": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_chebyshev_create": (i32, [vp, vp, vp, vp, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),

@@ -1315,6 +1315,89 @@ extern "C" int bp5_apply_components(bp5_mf *mf, const double *coef, int n_compon
   return components_copy_constrained(mf, n_components, ld, src, dst);
 }
 
+// ------------------------------------------------------------------------------------ linear elasticity (three coupled components)
+// every refusal of the bp5_elasticity_* entries and of bp5_cg_solve_elasticity, decided before any launch, each naming "elasticity".  What needs
+// no handle comes first (layout, then the parameters), so that a bad layout is named as such whatever the handle is.
+static int elasticity_refuse(int status, const char *what) { return fail(status, std::string("elasticity: ") + what); }
+static int elasticity_parameter_check(double lambda, double mu)
+{
+  if (!std::isfinite(lambda) || !std::isfinite(mu)) return elasticity_refuse(BP5_ERR_INVALID, "lambda and mu must be finite");
+  if (!(mu > 0.0)) return elasticity_refuse(BP5_ERR_INVALID, "mu must be positive");
+  if (!(lambda + 2.0 / 3.0 * mu > 0.0)) return elasticity_refuse(BP5_ERR_INVALID, "the bulk modulus lambda + 2/3 mu must be positive");
+  return BP5_OK;
+}
+// the handle can serve the operator at all (the ten planes, the kernels): what bp5_elasticity_coef_size / _compute_metric check
+static int elasticity_handle_check(const bp5_mf *mf)
+{
+  if (!mf) return elasticity_refuse(BP5_ERR_INVALID, "null handle");
+  if (mf->overint()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER) is not supported");
+  if (mf->operator_kind != BP5_OP_POISSON) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "a handle of the Helmholtz or mass operator class is not supported (Poisson class only)");
+  if (mf->has_hanging) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "meshes with hanging nodes are not supported");
+  if (mf->geometry_mode != BP5_GEOM_MERGED6) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "the affine geometry mode is not supported");
+  if (mf->f32_metric()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "FP32 metric planes are not supported");
+  if (mf->has_neighbors()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "no halo exchange (a handle with a communicator and neighbours)");
+  return BP5_OK;
+}
+// v, w: the block vectors of the call (w == NULL: one vector); distinct: they must not overlap
+static int elasticity_check(const bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *v, const double *w, bool distinct)
+{
+  if (!v || (distinct && !w) || !coef) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  if (ld & 1) return elasticity_refuse(BP5_ERR_INVALID, "ld must be even (every block 16-byte aligned)");
+  if (!aligned16(v) || (w && !aligned16(w))) return elasticity_refuse(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  if (distinct && v == w) return elasticity_refuse(BP5_ERR_INVALID, "src and dst overlap");
+  BP5_TRY(elasticity_parameter_check(lambda, mu));
+  if (!mf) return elasticity_refuse(BP5_ERR_INVALID, "null handle");
+  if (ld < mf->n_local()) return elasticity_refuse(BP5_ERR_INVALID, "ld < n_owned + n_ghost");
+  const size_t extent = 2 * ld + mf->n_local();
+  if (distinct && v < w + extent && w < v + extent) return elasticity_refuse(BP5_ERR_INVALID, "src and dst overlap");
+  return elasticity_handle_check(mf);
+}
+extern "C" int bp5_elasticity_coef_size(const bp5_mf *mf, size_t *n_doubles)
+{
+  if (!n_doubles) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(elasticity_handle_check(mf));
+  *n_doubles = 10 * (size_t)mf->n_cells * mf->n3; // (the handle's own plane count stays uncommitted: this array is not the one bp5_apply reads)
+  return BP5_OK;
+}
+extern "C" int bp5_elasticity_compute_metric(bp5_mf *mf, double *coef)
+{
+  if (!coef) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(elasticity_handle_check(mf));
+  HIP_TRY(hipSetDevice(mf->device));
+  return elasticity_compute_metric(mf, coef);
+}
+extern "C" int bp5_elasticity_apply(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, int zero_dst)
+{
+  BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, src, dst, true));
+  HIP_TRY(hipSetDevice(mf->device));
+  if (zero_dst) BP5_TRY(components_zero(mf, 3, ld, dst));
+  BP5_TRY(elasticity_apply_cells(mf, coef, lambda, mu, ld, src, dst, 0, mf->n_cells));
+  return components_copy_constrained(mf, 3, ld, src, dst);
+}
+extern "C" int bp5_elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t cell_begin,
+                                          uint32_t cell_end)
+{
+  BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, src, dst, true));
+  if (cell_begin > cell_end || cell_end > mf->n_cells) return elasticity_refuse(BP5_ERR_INVALID, "cell range outside [0, n_cells]");
+  HIP_TRY(hipSetDevice(mf->device));
+  return elasticity_apply_cells(mf, coef, lambda, mu, ld, src, dst, cell_begin, cell_end);
+}
+extern "C" int bp5_elasticity_compute_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag, int invert)
+{
+  BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, diag, nullptr, false));
+  HIP_TRY(hipSetDevice(mf->device));
+  BP5_TRY(components_zero(mf, 3, ld, diag));
+  BP5_TRY(elasticity_diagonal(mf, coef, lambda, mu, ld, diag));
+  for (int c = 0; c < 3; ++c) { // bp5_compute_diagonal's convention, block by block: A_eff = P A P + (I - P)
+    BP5_TRY(bp5_set_constrained(mf, 1.0, diag + (size_t)c * ld));
+    if (invert && mf->n_owned) {
+      hipLaunchKernelGGL(reciprocal_kernel, dim3((mf->n_owned + 255) / 256), dim3(256), 0, mf->stream, diag + (size_t)c * ld, (size_t)mf->n_owned);
+      KERNEL_CHECK();
+    }
+  }
+  return BP5_OK;
+}
+
 // ------------------------------------------------------------------------------------ rhs / norms
 template <int n>
 static int launch_rhs(bp5_mf *mf, double *b)
@@ -2499,8 +2582,13 @@ struct PlainCG {
   bp5_vmult_fn user = nullptr;
   void *user_ctx = nullptr;
   bool block = false, exchange = false;
-  // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g (scalar vectors)
+  // elasticity: the block operator is the coupled three-component one (coef: its ten planes; lambda, mu by value)
+  bool elasticity = false;
+  double lambda = 0.0, mu = 0.0;
+  // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g (scalar vectors).  diag_ld: doubles between the diagonals
+  // of two components -- 0: ONE scalar diagonal applied to every block; ld: a block inverse diagonal
   const double *diag = nullptr;
+  size_t diag_ld = 0;
   bp5_vmult_fn precond = nullptr;
   void *precond_ctx = nullptr;
   double *z = nullptr;
@@ -2519,6 +2607,7 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
   const int nc = cg.n_components;
   double *g = cg.g, *d = cg.d, *h = cg.h, *z = cg.z;
   const double *diag = cg.diag;
+  const size_t dld = cg.diag_ld;
   // launch geometry: the component is the second grid dimension and owns PARTIAL_STRIDE / n_components columns of a partial-sum row (a scalar
   // vector: all of them, stream_grid never asks for more).  Scalar vectors launch the direction kernel, which reduces nothing, flat
   const int cols = PARTIAL_STRIDE / nc;
@@ -2539,7 +2628,8 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     BP5_TRY(prof.mark(0));
     BP5_TRY(components_zero(mf, nc, ld, h));
     BP5_TRY(prof.mark(1));
-    if (cg.exchange) BP5_TRY(components_apply_exchanged(mf, cg.coef, nc, ld, d, h, false));
+    if (cg.elasticity) BP5_TRY(elasticity_apply_cells(mf, cg.coef, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
+    else if (cg.exchange) BP5_TRY(components_apply_exchanged(mf, cg.coef, nc, ld, d, h, false));
     else BP5_TRY(components_apply(mf, cg.coef, nc, ld, d, h, false));
     BP5_TRY(prof.mark(2));
     BP5_TRY(components_copy_constrained(mf, nc, ld, d, h));
@@ -2553,20 +2643,20 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
   };
   // g = -b, d = -D g, x = 0   (x0 = 0 short-circuit, bp5/solver.h:375-381); a callback: z = P g and d = -z behind the control step
   if (cg.precond) {
-    hipLaunchKernelGGL(cg_init_kernel<false>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
+    hipLaunchKernelGGL(cg_init_kernel<false>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials, dld);
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
     KERNEL_CHECK();
     BP5_TRY(apply_P());
     hipLaunchKernelGGL(dot_kernel, grid2, block, 0, s, g, z, n, mf->d_partials);
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, no_flag);
   } else {
-    hipLaunchKernelGGL(cg_init_kernel<true>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials);
+    hipLaunchKernelGGL(cg_init_kernel<true>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials, dld);
     hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
   }
   KERNEL_CHECK();
   if (cg.allreduce) BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2));
   hipLaunchKernelGGL(cg_init_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res0, gh = g.Dg (g.z), stop test
-  if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, true>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st);
+  if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, true>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st, dld);
   KERNEL_CHECK();
   if (op.prezero) HIP_TRY(hipMemsetAsync(h, 0, mf->n_local() * sizeof(double), s)); // once: every later zero-fill is stored by cg_update_kernel
   const int check = prm->check_every;
@@ -2591,21 +2681,21 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     }
     if (cg.allreduce) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_DH, 1)); }
     if (cg.precond) {
-      hipLaunchKernelGGL(cg_update_kernel<false>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, false);
+      hipLaunchKernelGGL(cg_update_kernel<false>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, false, dld);
       hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
       KERNEL_CHECK();
       BP5_TRY(apply_P()); // (the sum g.g is in SC_GG already: the preconditioner may run reductions of its own)
       hipLaunchKernelGGL(cg_dh_kernel<false>, grid2, block, 0, s, g, z, n, ld, mf->d_partials, mf->d_st, (const uint32_t *)nullptr);
       hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, mf->d_st);
     } else {
-      hipLaunchKernelGGL(cg_update_kernel<true>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, op.prezero);
+      hipLaunchKernelGGL(cg_update_kernel<true>, grid2, block, 0, s, x, g, d, h, diag, n, ld, mf->d_sc, mf->d_st, mf->d_partials, op.prezero, dld);
       hipLaunchKernelGGL(finalize_kernel<2>, dim3(2), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GG, mf->d_st);
     }
     if (cg.allreduce) { KERNEL_CHECK(); BP5_TRY(bp5_comm_allreduce_sum(mf, mf->d_sc + SC_GG, 2)); } // g.g, g.Dg (g.z)
     hipLaunchKernelGGL(cg_control_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st); // res, ++it, stop test, beta
     if (cg.history) hipLaunchKernelGGL(cg_record_kernel, dim3(1), dim3(1), 0, s, mf->d_sc, mf->d_st, cg.history, cg.history_cap);
-    if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, false>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st);
-    else hipLaunchKernelGGL((cg_direction_kernel<false, false>), gridd, block, 0, s, d, g, diag, n, ld, mf->d_sc, mf->d_st);
+    if (cg.precond) hipLaunchKernelGGL((cg_direction_kernel<true, false>), gridd, block, 0, s, d, z, diag, n, ld, mf->d_sc, mf->d_st, dld);
+    else hipLaunchKernelGGL((cg_direction_kernel<false, false>), gridd, block, 0, s, d, g, diag, n, ld, mf->d_sc, mf->d_st, dld);
     KERNEL_CHECK();
     if (check > 0 && it % check == 0 && it < prm->max_iter) {
       BP5_TRY(poll_state(mf));
@@ -2815,6 +2905,21 @@ extern "C" int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, 
   return cg_solve_impl(mf, nullptr, vmult, ctx, diag, b, x, prm, res);
 }
 
+// the work vectors g, d, h of a plain solve on block vectors: 3 n_components ld doubles of the handle, grown on demand and zero-filled (the ghost
+// entries of d are read by the operator: defined, zero); sets the vector part of `cg`
+static int block_cg_workspace(bp5_mf *mf, int n_components, size_t ld, PlainCG &cg)
+{
+  const size_t block = (size_t)n_components * ld, need = 3 * block;
+  if (mf->wsc_cap < need) {
+    if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
+    HIP_TRY(hipMalloc((void **)&mf->wsc_base, need * sizeof(double)));
+    mf->wsc_cap = need;
+  }
+  HIP_TRY(hipMemsetAsync(mf->wsc_base, 0, need * sizeof(double), mf->stream));
+  cg.n_components = n_components; cg.ld = ld;
+  cg.g = mf->wsc_base; cg.d = cg.g + block; cg.h = cg.d + block;
+  return BP5_OK;
+}
 // cg.solve(A, x, b, DiagonalMatrix) on a block vector: the plain recurrence on the stacked system, one launch per BLAS-1 step
 // with_exchange (bp5_cg_solve_components_distributed): a handle with a communicator and neighbours is taken, every operator application carries
 // the halo exchange (components_apply_exchanged) and d.h, g.g and g.z are all-reduced where the scalar plain solver all-reduces them
@@ -2828,16 +2933,8 @@ static int cg_solve_components_impl(bp5_mf *mf, const double *coef, int n_compon
   BP5_TRY(components_check(mf, coef, n_components, ld, b, x, with_exchange));
   if (prm->variant == BP5_CG_MERGED) return fail(BP5_ERR_UNSUPPORTED, "block vectors: SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   HIP_TRY(hipSetDevice(mf->device));
-  const size_t need = 3 * (size_t)n_components * ld;
-  if (mf->wsc_cap < need) {
-    if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
-    HIP_TRY(hipMalloc((void **)&mf->wsc_base, need * sizeof(double)));
-    mf->wsc_cap = need;
-  }
-  HIP_TRY(hipMemsetAsync(mf->wsc_base, 0, need * sizeof(double), mf->stream)); // ghost entries of d are read by the operator: defined, zero
   PlainCG cg;
-  cg.n_components = n_components; cg.ld = ld;
-  cg.g = mf->wsc_base; cg.d = cg.g + (size_t)n_components * ld; cg.h = cg.d + (size_t)n_components * ld;
+  BP5_TRY(block_cg_workspace(mf, n_components, ld, cg));
   cg.coef = coef; cg.block = true; cg.exchange = with_exchange && mf->has_neighbors();
   cg.diag = diag;
   cg.allreduce = with_exchange;
@@ -2852,6 +2949,30 @@ extern "C" int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coe
                                                    double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
   return cg_solve_components_impl(mf, coef, n_components, ld, diag, b, x, prm, res, true);
+}
+
+// cg.solve(A, x, b, DiagonalMatrix) for the elasticity operator: the plain recurrence on the stacked three-component system, the operator step the
+// coupled application and the preconditioner a BLOCK inverse diagonal (three blocks ld apart, as bp5_elasticity_compute_diagonal returns them)
+extern "C" int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, const double *b, double *x,
+                                       const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  if (!prm || !res) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return elasticity_refuse(BP5_ERR_INVALID, "unknown CG variant");
+  if (prm->max_iter < 0) return elasticity_refuse(BP5_ERR_INVALID, "max_iter < 0");
+  if (inv_diag && !aligned16(inv_diag)) return elasticity_refuse(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, b, x, true));
+  if (inv_diag) { // the update kernels read it while they write x
+    const size_t extent = 2 * ld + mf->n_local();
+    if (inv_diag < x + extent && x < inv_diag + extent) return elasticity_refuse(BP5_ERR_INVALID, "inv_diag and x overlap");
+  }
+  if (prm->variant == BP5_CG_MERGED) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
+  HIP_TRY(hipSetDevice(mf->device));
+  PlainCG cg;
+  BP5_TRY(block_cg_workspace(mf, 3, ld, cg));
+  cg.coef = coef; cg.block = true; cg.elasticity = true; cg.lambda = lambda; cg.mu = mu;
+  cg.diag = inv_diag; cg.diag_ld = ld;
+  cg.allreduce = false;
+  return cg_solve_plain(mf, cg, b, x, prm, res);
 }
 
 // cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of D g

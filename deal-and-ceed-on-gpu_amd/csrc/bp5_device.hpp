@@ -333,6 +333,14 @@ int overint_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref
 // the reason an over-integrated handle refuses something with (BP5_ERR_UNSUPPORTED)
 inline int overint_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED, std::string("Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER): ") + what); }
 
+// Linear elasticity (bp5_elasticity_*), defined in elasticity/bp5_elasticity.hip -- a translation unit of its own, off the per-degree units, in a
+// directory of its own (its ISA is kept beside it): the ten planes, the coupled three-component operator over the cells [c0, c1) (accumulates;
+// an empty range launches nothing) and the cells' contributions to the three diagonals (the caller has zeroed diag).  The callers have
+// validated handle, layout and parameters.
+int elasticity_compute_metric(bp5_mf *mf, double *coef);
+int elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1);
+int elasticity_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag);
+
 // What every operator launch takes from the handle (affine builds read ONE scalar plane, cells n^3 entries apart); the launcher adds range and team counts
 inline ApplyArgs apply_args(const bp5_mf *mf, bool affine, const double *coef, const double *src, double *dst)
 {

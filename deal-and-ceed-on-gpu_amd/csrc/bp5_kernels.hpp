@@ -1563,6 +1563,241 @@ __global__ void __launch_bounds__(64 * TW * TPB) apply_pencil_mass_kernel(ApplyA
   }
 }
 
+// ------------------------------------------------------------------------------------ fused linear elasticity operator
+// a(v, u) = int kappa [ lambda (div v)(div u) + 2 mu eps(v) : eps(u) ] on a three-component block vector over ONE scalar DoF layout (deal.II
+// step-8 / step-18: FEEvaluation<dim, p, n_q, dim>::get_symmetric_gradient / submit_symmetric_gradient; the CEED "solids" mini-app): the operator
+// that COUPLES the components at the quadrature points.  Metric: TEN planes of its own (bp5_elasticity_compute_metric), planes 0..8 K[d][e] =
+// d xi_d / d x_e at 3 d + e, plane 9 kappa JxW, each in the pair layout -- K itself, not K K^T: the symmetric gradient mixes the components before
+// the second multiplication by K.  Per cell: local_to_global once; evaluate of the three components (the components kernel's sequence), the nine
+// x-owner gradient pencils kept; ONE quadrature-point loop that reads the ten planes pair by pair where it uses them (9 n doubles are live across
+// it: no whole-plane prefetch) and overwrites the nine pencils with
+//   G[c][e] = sum_d K[d][e] ghat_c[d],  sigma[c][e] = lambda tr(G) delta_ce + mu (G[c][e] + G[e][c]),  t_c[d] = s sum_e K[d][e] sigma[c][e];
+// integrate of the three components and their atomics.  The tile is reused from component to component: every reuse is closed by
+// lds_drain(); team_sync().  Launch shape, lanes, tiles and the idle-lane rule are apply_pencil_kernel's.
+struct ElasticityArgs {
+  double lambda, mu;
+  uint64_t ld; // doubles between two components (even; >= n_owned + n_ghost)
+};
+// waves per SIMD asked of the compiler, decided per degree from the ISA.  Left alone the builds take 114 / 166 / 222 / 274 VGPRs at
+// p = 1 .. 4 (Gauss), far more than the nine pencils (18 n) and one pair of the ten planes (40) account for.  The caps below are the most waves each
+// degree holds without a spill: four, three and two at p = 1, 2, 3.  p = 4 capped at 256 (two waves) spills 8 - 18 VGPRs in every form of the
+// quadrature-point loop that was tried (nine or six stress entries, one or two points in flight), and p <= 4 may not touch scratch: one wave per
+// SIMD, as every p >= 5, whose pencils alone pass 256 registers.  The macro is the A/B knob.
+#ifndef BP5_ELASTICITY_WAVES
+#define BP5_ELASTICITY_WAVES(degree) ((degree) == 1 ? 4 : (degree) == 2 ? 3 : (degree) == 3 ? 2 : 1)
+#endif
+constexpr int elasticity_waves_per_simd(int degree) { return BP5_ELASTICITY_WAVES(degree); }
+template <int P, bool COLL, int TW, int LPC, int TPB>
+__global__ void __launch_bounds__(64 * TW * TPB, elasticity_waves_per_simd(P)) apply_pencil_elasticity_kernel(ApplyArgs a, ElasticityArgs ea, ShapeArg<P + 1> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= n2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<n, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // XCD-aware mapping, as apply_pencil_kernel
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < n2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  // idle lanes mirror a valid lane: every load is unconditional and in bounds; LDS writes and the atomics are predicated, for every component
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < n2 ? ab : ab % n2;
+  const int a_ = abm % n, b_ = abm / n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * L::CS;
+#define TL(f, k, j, i) T[(f) * (n * L::PS) + (k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- once per cell: indices (z-owner)
+  uint32_t idx[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+
+  // ---- evaluate, component after component: g[comp][d] = the x-owner pencil of the reference gradient along d
+  double g[3][3][n];
+#pragma unroll
+  for (int comp = 0; comp < 3; ++comp) {
+    const double *src_c = a.src + (uint64_t)comp * ea.ld;
+    double u[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) u[k] = src_c[idx[k]];
+    if constexpr (!COLL) {
+      double aN[n], aD[n];
+      MV_N(sh.N, u, aN);
+      MV_D(sh.D, u, aD);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = aN[k]; TL(1, k, b_, a_) = aD[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], vD[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { vN[j] = TL(0, b_, j, a_); vD[j] = TL(1, b_, j, a_); }
+      double c1[n], c2[n], c3[n];
+      MV_N(sh.N, vN, c1);
+      MV_D(sh.D, vN, c2);
+      MV_N(sh.N, vD, c3);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = c1[j]; TL(1, b_, j, a_) = c2[j]; TL(2, b_, j, a_) = c3[j]; }
+      }
+      team_sync<TW>();
+      double r1[n], r2[n], r3[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        r2[i] = TL(1, b_, a_, i);
+        r3[i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g[comp][0]);
+      MV_N(sh.N, r2, g[comp][1]);
+      MV_N(sh.N, r3, g[comp][2]);
+    } else {
+      double gz[n];
+      MV_D(sh.D, u, gz);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = u[k]; TL(2, k, b_, a_) = gz[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], c2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) vN[j] = TL(0, b_, j, a_);
+      MV_D(sh.D, vN, c2);
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(1, b_, j, a_) = c2[j];
+      }
+      team_sync<TW>();
+      double r1[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        g[comp][1][i] = TL(1, b_, a_, i);
+        g[comp][2][i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g[comp][0]);
+    }
+    // the next component's (or the integrate's) first tile write follows this component's last tile read
+    lds_drain();
+    team_sync<TW>();
+  }
+
+  // ---- quadrature-point operation (x-owner: a_ = qj, b_ = qk; registers hold qi): the ten planes pair by pair
+  {
+    const double *cf = a.coef + cell * a.cell_stride;
+    const double lambda = ea.lambda, mu = ea.mu;
+    auto qpoint = [&](int i, const double (&K)[10]) {
+      double G[3][3];
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) G[cc][e] = K[e] * g[cc][0][i] + K[3 + e] * g[cc][1][i] + K[6 + e] * g[cc][2][i];
+      // sigma is symmetric: six entries (00, 11, 22, 01, 02, 12), s folded in
+      const double ltr = lambda * (G[0][0] + G[1][1] + G[2][2]), s = K[9], sm = s * mu, two_sm = 2.0 * sm, sl = s * ltr;
+      const double s00 = two_sm * G[0][0] + sl, s11 = two_sm * G[1][1] + sl, s22 = two_sm * G[2][2] + sl;
+      const double s01 = sm * (G[0][1] + G[1][0]), s02 = sm * (G[0][2] + G[2][0]), s12 = sm * (G[1][2] + G[2][1]);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        g[0][d][i] = K[3 * d] * s00 + K[3 * d + 1] * s01 + K[3 * d + 2] * s02;
+        g[1][d][i] = K[3 * d] * s01 + K[3 * d + 1] * s11 + K[3 * d + 2] * s12;
+        g[2][d][i] = K[3 * d] * s02 + K[3 * d + 1] * s12 + K[3 * d + 2] * s22;
+      }
+    };
+#pragma unroll
+    for (int m = 0; m < n / 2; ++m) {
+      double K0[10], K1[10];
+#pragma unroll
+      for (int pl = 0; pl < 10; ++pl) load_pencil_pair<n>(cf + pl * a.plane_stride, abm, m, K0[pl], K1[pl]);
+      qpoint(2 * m, K0);
+      qpoint(2 * m + 1, K1);
+    }
+    if constexpr (n & 1) {
+      double K0[10];
+#pragma unroll
+      for (int pl = 0; pl < 10; ++pl) K0[pl] = load_pencil_tail<n>(cf + pl * a.plane_stride, abm);
+      qpoint(n - 1, K0);
+    }
+  }
+
+  // ---- integrate (transpose sequence) and scatter-add, component after component
+#pragma unroll
+  for (int comp = 0; comp < 3; ++comp) {
+    double y[n];
+    if constexpr (!COLL) {
+      double e1[n], e2[n], e3[n];
+      MV_DT(sh.D, g[comp][0], e1);
+      MV_NT(sh.N, g[comp][1], e2);
+      MV_NT(sh.N, g[comp][2], e3);
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = e2[i]; TL(2, b_, a_, i) = e3[i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n], w3[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        w1[j] = TL(0, b_, j, a_);
+        w2[j] = TL(1, b_, j, a_);
+        w3[j] = TL(2, b_, j, a_);
+      }
+      double f1[n], f2[n];
+      MV_NT(sh.N, w1, f1);
+      MV_DT_ADD(sh.D, w2, f1);
+      MV_NT(sh.N, w3, f2);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = f1[j]; TL(1, b_, j, a_) = f2[j]; }
+      }
+      team_sync<TW>();
+      double z1[n], z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { z1[k] = TL(0, k, b_, a_); z2[k] = TL(1, k, b_, a_); }
+      MV_NT(sh.N, z1, y);
+      MV_DT_ADD(sh.D, z2, y);
+    } else {
+      double e1[n];
+      MV_DT(sh.D, g[comp][0], e1);
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = g[comp][1][i]; TL(2, b_, a_, i) = g[comp][2][i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { w1[j] = TL(0, b_, j, a_); w2[j] = TL(1, b_, j, a_); }
+      MV_DT_ADD(sh.D, w2, w1);
+      if (active) { // each y-owner lane rewrites only the column it has just read
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(0, b_, j, a_) = w1[j];
+      }
+      team_sync<TW>();
+      double z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { y[k] = TL(0, k, b_, a_); z2[k] = TL(2, k, b_, a_); }
+      MV_DT_ADD(sh.D, z2, y);
+    }
+    if (active) {
+      double *dst_c = a.dst + (uint64_t)comp * ea.ld;
+#pragma unroll
+      for (int k = 0; k < n; ++k) atomic_add_f64(dst_c + idx[k], y[k]);
+    }
+    if (comp < 2) { // the next component's first tile write follows this component's last tile read
+      lds_drain();
+      team_sync<TW>();
+    }
+  }
+#undef TL
+}
+
 // degrees whose block-kernel cells span waves (n^2 lanes per cell: p = 2, 5, 8) and exchange their tiles through the workgroup barrier: two
 // tiles used alternately halve the barriers of a pass (BlockPass::PP) where the second tile still fits the LDS share of the workgroup
 #ifndef BP5_PINGPONG_P2
@@ -3252,6 +3487,77 @@ __global__ void __launch_bounds__(n *n *n) mass_diagonal_kernel(const uint32_t *
   }
 }
 
+// The TEN planes of the elasticity operator (apply_pencil_elasticity_kernel): K[d][e] at plane 3 d + e and kappa(x_q) JxW at plane 9, plane-major,
+// each in the pair layout -- what geometry_kernel forms before it merges them, by the same expressions.  A kernel of its own so that no build of
+// geometry_kernel changes; conforming meshes only (the elasticity entry points refuse hanging-node masks).
+template <int n>
+__global__ void __launch_bounds__(n *n *n) elasticity_metric_kernel(const uint32_t *l2g, const double *coords, const double *tab, int kappa_mode, uint32_t n_cells,
+                                                                   double *coef, uint64_t plane_stride)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double X[3 * n3], t1[n3], t2[n3];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    const uint32_t g = l2g[cell * n3 + q];
+    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
+    __syncthreads();
+    double J[3][3], K[3][3], xq[3];
+    cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
+    const double det = invert3(J, K);
+    const double *w = tab + 2 * n2;
+    const double jxw = fabs(det) * w[i] * w[j] * w[k];
+    double *c = coef + cell * n3 + coef_off<n>(i, j + n * k);
+    for (int d = 0; d < 3; ++d)
+      for (int e = 0; e < 3; ++e) c[(uint64_t)(3 * d + e) * plane_stride] = K[d][e];
+    c[9 * plane_stride] = jxw * kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
+    __syncthreads();
+  }
+}
+
+// diag(A) of the elasticity operator, one block per component: diag_a[i] += sum_q s [ (lambda + mu) (d_a phi_i)^2 + mu |grad phi_i|^2 ] with
+// grad phi = K^T ghat phi, i.e. the symmetric 3 x 3 form S^a[d][d'] = s ((lambda + mu) K[d][a] K[d'][a] + mu (K K^T)[d][d']) contracted with the
+// entrywise products N*N, D*D, N*D as 1-D factors: diagonal_kernel's six transposed contractions, per component.  Setup-time kernel (once per
+// mesh, not optimised): one block per cell, one thread per local DoF.
+template <int n>
+__global__ void __launch_bounds__(n *n *n) elasticity_diagonal_kernel(const uint32_t *l2g, const double *coef, uint64_t plane_stride, const double *tab, uint32_t n_cells,
+                                                                     double lambda, double mu, uint64_t ld, double *diag)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double S[n3], t1[n3], t2[n3], NN[n2], DD[n2], ND[n2];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  if (q < n2) {
+    const double a = tab[q], b = tab[n2 + q];
+    NN[q] = a * a;
+    DD[q] = b * b;
+    ND[q] = a * b;
+  }
+  __syncthreads();
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    const double *cq = coef + cell * n3 + coef_off<n>(i, j + n * k); // this thread's q-point (a,b,c) = (i,j,k) in the device (pair) layout
+    double K[3][3];
+    for (int d = 0; d < 3; ++d)
+      for (int e = 0; e < 3; ++e) K[d][e] = cq[(uint64_t)(3 * d + e) * plane_stride];
+    const double s = cq[9 * plane_stride];
+    const uint32_t gi = l2g[cell * n3 + q];
+    for (int a = 0; a < 3; ++a) {
+      double acc = 0.0;
+      for (int c = 0; c < 6; ++c) {
+        const int d = c < 3 ? c : c == 5 ? 1 : 0, e = c < 3 ? c : c == 3 ? 1 : 2; // planes 00, 11, 22, 01, 02, 12
+        S[q] = s * ((lambda + mu) * K[d][a] * K[e][a] + mu * (K[d][0] * K[e][0] + K[d][1] * K[e][1] + K[d][2] * K[e][2]));
+        __syncthreads();
+        const double *X = (c == 0) ? DD : (c == 3 || c == 4) ? ND : NN;
+        const double *Y = (c == 1) ? DD : (c == 3 || c == 5) ? ND : NN;
+        const double *Z = (c == 2) ? DD : (c == 4 || c == 5) ? ND : NN;
+        const double y = Cell3<n>::template tensor3<true>(X, Y, Z, S, t1, t2, i, j, k);
+        acc += c < 3 ? y : 2.0 * y;
+      }
+      atomic_add_f64(diag + (uint64_t)a * ld + gi, acc);
+    }
+  }
+}
+
 // Diagonal entries of the coarse DoFs a cell with hanging nodes refers to: (R^T A_e R)[s][s] with R the cell's hanging-node
 // interpolation -- R e_s is not a tensor product in general (a DoF on the edge shared by two constrained faces spreads into
 // both), so each such entry takes one application of the cell operator to R e_s.  Setup-time kernel, flagged cells only.
@@ -3847,15 +4153,17 @@ static __global__ void copy_constrained_components_kernel(const uint32_t *cdofs,
 // ---- plain CG (deal.II SolverCG, Appendix A.5): ONE kernel set for scalar vectors, block vectors and any preconditioner.
 // Component c = blockIdx.y works on the block at + c ld; its partial sums land in columns [c gridDim.x, (c + 1) gridDim.x) of the rows, so the
 // finalize pass sums block-wise partials, components in order (fixed order).  A scalar solve is one component: gridDim.y == 1, column 0.
-// diag is per scalar DoF, shared by the components.
+// diag is per scalar DoF, component c reads it at + c diag_ld: 0 (every entry point but the elasticity solve) shares it among the components,
+// ld makes it a block vector of its own (a BLOCK inverse diagonal).
 // GDG: the preconditioner is the diagonal (NULL == 1) and the kernel also forms g.Dg; false: z = P g comes from a callback, g.g alone
 // init: g = -b ; x = 0 ; partial sums of g.g   GDG: and d = b (= -D g with D = 1), partial sums of g.Dg
 template <bool GDG>
 __global__ void __launch_bounds__(VB) cg_init_kernel(const double *b, const double *diag, double *x, double *g, double *d, size_t n, size_t ld,
-                                                     double *partials)
+                                                     double *partials, size_t diag_ld)
 {
   const size_t o = blockIdx.y * ld;
   b += o; x += o; g += o; d += o;
+  if (diag) diag += blockIdx.y * diag_ld;
   double acc[GDG ? 2 : 1] = {};
   const size_t stride = (size_t)gridDim.x * VB;
   for (size_t i = (size_t)blockIdx.x * VB + threadIdx.x; i < n; i += stride) {
@@ -3920,11 +4228,12 @@ __global__ void __launch_bounds__(VB) cg_dh_kernel(const double *d, double *h, s
 // it zeroed, so this kernel stores the zeros (see cgm_update_kernel<.., ZV>)
 template <bool GDG>
 __global__ void __launch_bounds__(VB) cg_update_kernel(double *x, double *g, const double *d, double *h, const double *diag, size_t n, size_t ld,
-                                                       const double *sc, const int *st, double *partials, bool zero_h)
+                                                       const double *sc, const int *st, double *partials, bool zero_h, size_t diag_ld)
 {
   if (st[ST_DONE]) return;
   const size_t o = blockIdx.y * ld;
   x += o; g += o; d += o; h += o;
+  if (diag) diag += blockIdx.y * diag_ld;
   const double alpha = sc[SC_GH] / sc[SC_DH];
   double acc[GDG ? 2 : 1] = {};
   const size_t stride = (size_t)gridDim.x * VB * 2;
@@ -3969,10 +4278,11 @@ static __global__ void cg_control_kernel(double *sc, int *st)
 // d = beta d - D g   Z: g is the preconditioner's z = P g (diag not read): d = beta d - z   FIRST (with Z): d = -z, d not read
 template <bool Z, bool FIRST>
 __global__ void __launch_bounds__(VB) cg_direction_kernel(double *d, const double *g, const double *diag, size_t n, size_t ld, const double *sc,
-                                                          const int *st)
+                                                          const int *st, size_t diag_ld)
 {
   if (st[ST_DONE]) return;
   d += blockIdx.y * ld; g += blockIdx.y * ld;
+  if (!Z && diag) diag += blockIdx.y * diag_ld;
   const double beta = FIRST ? 0.0 : sc[SC_BETA];
   const size_t stride = (size_t)gridDim.x * VB * 2;
   for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {

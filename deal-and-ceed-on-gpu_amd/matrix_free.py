@@ -391,6 +391,72 @@ class MassOperator(PoissonOperator):
         self.distributed = comm is not None and comm.n_ranks > 1
 
 
+class ElasticityOperator:
+    """Linear elasticity on three-component block vectors (deal.II step-8 / step-18; the CEED "solids" mini-app):
+    a(v, u) = int kappa [ lam (div v)(div u) + 2 mu eps(v) : eps(u) ] as the library's native coupled kernel (bp5_elasticity_*, include/bp5.h).
+    `coef` holds the operator's TEN planes (K and kappa JxW); vectors are (3, ld) tensors; all three components are clamped on the mesh's
+    Dirichlet set.  SolverCG.solve(op, x, b, DiagonalMatrix(block inverse diagonal or None)) runs bp5_cg_solve_elasticity; SolverCGFullMerge,
+    PreconditionChebyshev and PreconditionMG refuse it (BP5Error 5).  Not a PoissonOperator: nothing scalar is offered."""
+
+    n_components = 3
+
+    def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, lam=1.0, mu=1.0, device=0, stream=None):
+        torch = _torch()
+        self.lam, self.mu = float(lam), float(mu)
+        self.mf_data = MatrixFree().reinit(mesh, quadrature, coefficient, device, stream, None)
+        n = C.c_size_t()
+        _lib.check(_lib.lib().bp5_elasticity_coef_size(self.mf_data.handle, C.byref(n)))
+        self.coef = torch.empty(max(n.value, 2), dtype=torch.float64, device=f"cuda:{device}")
+        _lib.check(_lib.lib().bp5_elasticity_compute_metric(self.mf_data.handle, _ptr(self.coef)))
+        self.n_owned_cells = mesh.n_cells
+        self.do_zero_out = True
+        self.distributed = False
+
+    def initialize_block_vector(self):
+        return self.mf_data.initialize_block_vector(3)
+
+    def _args(self, *vectors):
+        nc, ld = _block_args(self.mf_data, *vectors)
+        if nc != 3:
+            raise BP5Error(1, f"elasticity: block vectors of three components expected, got {nc}")
+        return ld
+
+    def vmult(self, dst, src):
+        """dst = [0 +] A src on (3, ld) tensors; dst_c = src_c on Dirichlet DoFs (bp5_elasticity_apply)."""
+        dst, src = _vals(dst), _vals(src)
+        ld = self._args(dst, src)
+        _lib.check(_lib.lib().bp5_elasticity_apply(self.mf_data.handle, _ptr(self.coef), self.lam, self.mu, ld, _ptr(src), _ptr(dst), 1 if self.do_zero_out else 0))
+
+    def cell_loop(self, src, dst, cell_begin=0, cell_end=None):
+        """dst += A src over the cells [cell_begin, cell_end), no Dirichlet copy (bp5_elasticity_apply_cells)."""
+        ld = self._args(dst, src)
+        cell_end = self.n_owned_cells if cell_end is None else cell_end
+        _lib.check(_lib.lib().bp5_elasticity_apply_cells(self.mf_data.handle, _ptr(self.coef), self.lam, self.mu, ld, _ptr(src), _ptr(dst), cell_begin, cell_end))
+
+    def compute_diagonal(self, invert=False):
+        """the three diagonals as a (3, ld) tensor (1 on Dirichlet DoFs); invert=True: the block Jacobi preconditioner for DiagonalMatrix"""
+        d = self.initialize_block_vector()
+        _lib.check(_lib.lib().bp5_elasticity_compute_diagonal(self.mf_data.handle, _ptr(self.coef), self.lam, self.mu, d.shape[1], _ptr(d), 1 if invert else 0))
+        return d
+
+    def assemble_rhs(self):
+        """the scalar load vector b_i = int phi_i (bp5_assemble_rhs): a body force f is b_c = f_c * assemble_rhs()"""
+        b = self.mf_data.initialize_dof_vector()
+        _lib.check(_lib.lib().bp5_assemble_rhs(self.mf_data.handle, _ptr(b)))
+        return b
+
+    def l2_norm_solution(self, u):
+        """the L2 norm of ONE component (a 1-D view of its block)"""
+        r = C.c_double()
+        _lib.check(_lib.lib().bp5_l2_norm_solution(self.mf_data.handle, _ptr(u, self.mf_data.n_local), C.byref(r)))
+        return r.value
+
+
+def _refuse_elasticity(who, A):
+    if isinstance(A, ElasticityOperator):
+        raise BP5Error(5, f"{who} does not take the elasticity operator: SolverCG with None / DiagonalMatrix does")
+
+
 class Vector:
     """The part of LinearAlgebra::distributed::Vector<double, MemorySpace::CUDA> the reference's path uses
     (bp5/solver.h:369-382,417-421,511,528; bp5/step-64.cu:349,366-367,431-432,445,449,467), over a torch CUDA
@@ -583,6 +649,7 @@ class PreconditionChebyshev:
 
     def initialize(self, A, data=None):
         self.clear()
+        _refuse_elasticity("PreconditionChebyshev", A)
         data = data if data is not None else PreconditionChebyshev.AdditionalData()
         mf = A.mf_data
         self.A, self.mf_data, self.data = A, mf, data
@@ -768,6 +835,8 @@ class PreconditionMG:
         self.clear()
         data = data if data is not None else PreconditionMG.AdditionalData()
         ops = list(operators)
+        for o in ops:
+            _refuse_elasticity("PreconditionMG", o)
         if not ops or not all(isinstance(o, PoissonOperator) for o in ops):
             raise BP5Error(1, "PreconditionMG needs a list of PoissonOperators, fine to coarse")
         self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
@@ -842,6 +911,8 @@ class _SolverBase:
         mf = A.mf_data
         x, b = _vals(x), _vals(b)
         general = preconditioner is not None and not hasattr(preconditioner, "get_vector")
+        if isinstance(A, ElasticityOperator) and (self.variant != CG_PLAIN or general):      # (one status for the class, whatever else is wrong)
+            raise BP5Error(5, "elasticity: SolverCG with None / DiagonalMatrix only")
         if general and not hasattr(preconditioner, "vmult"):
             raise BP5Error(1, "the preconditioner needs get_vector() (diagonal) or vmult(dst, src)")
         if general and self.variant != CG_PLAIN:
@@ -851,7 +922,15 @@ class _SolverBase:
         res = _lib.CGResult()
         failure = []
         native = isinstance(A, PoissonOperator)
-        if _is_block(x) or _is_block(b):
+        if isinstance(A, ElasticityOperator):
+            # the coupled three-component system: ONE Krylov space, a BLOCK inverse diagonal (bp5_cg_solve_elasticity)
+            ld = A._args(x, b)
+            diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None
+            if diag is not None and tuple(diag.shape) != tuple(x.shape):
+                raise BP5Error(1, f"elasticity: the inverse diagonal is a block vector of shape {tuple(x.shape)}, got {tuple(diag.shape)}")
+            status = _lib.lib().bp5_cg_solve_elasticity(mf.handle, _ptr(A.coef), A.lam, A.mu, ld, _ptr(diag) if diag is not None else None, _ptr(b), _ptr(x),
+                                                        C.byref(prm), C.byref(res))
+        elif _is_block(x) or _is_block(b):
             # the stacked system diag(A, ..., A) x = b: ONE Krylov space for all components (bp5_cg_solve_components[_distributed])
             if self.variant != CG_PLAIN or general or not native:
                 raise BP5Error(5, "block vectors (2-D tensors): SolverCG on a PoissonOperator with None / DiagonalMatrix only")

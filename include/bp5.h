@@ -597,6 +597,45 @@ int bp5_cg_solve_components(bp5_mf *mf, const double *coef, int n_components, si
 int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *inv_diag, const double *b,
                                         double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
 
+/* ---- Linear elasticity: a(v, u) = int kappa(x) [ lambda (div v)(div u) + 2 mu eps(v) : eps(u) ] dx, eps(u) = (grad u + grad u^T) / 2, on
+ * three-component block vectors over the handle's ONE scalar DoF layout (layout as for bp5_apply_components with n_components = 3) -- the
+ * operator that couples the components at the quadrature points (deal.II step-8 / step-18: FEEvaluation<dim, p, n_q, dim> with
+ * get_symmetric_gradient / submit_symmetric_gradient; the "solids" mini-app of CEED).  lambda, mu: constant Lame parameters, by value;
+ * kappa: the handle's BP5_COEF_* function, scaling both; Dirichlet: all three components clamped on the handle's constrained set
+ * (n_constrained == 0 is legal: the six rigid-body modes are then the null space).  With K[d][e] = d xi_d / d x_e (bp5_mf_get_data's
+ * inv_jacobian), ghat_c the reference gradient of component c and s = kappa JxW, a quadrature point computes
+ *   G[c][e] = sum_d K[d][e] ghat_c[d],  sigma[c][e] = lambda tr(G) delta_ce + mu (G[c][e] + G[e][c]),  t_c[d] = s sum_e K[d][e] sigma[c][e].
+ * The entries sit beside the handle's others and change none of them: the same handle goes on serving bp5_apply with its own array.
+ * Refused before any launch, bp5_last_error names "elasticity" -- BP5_ERR_INVALID: null pointer (coef included), odd ld, misaligned base (checked
+ * before the handle is looked at), src == dst or overlapping (bp5_cg_solve_elasticity: also inv_diag overlapping x), mu <= 0, lambda + 2/3 mu <= 0 or a non-finite parameter, ld < n_owned + n_ghost;
+ * BP5_ERR_UNSUPPORTED: BP5_QUAD_GAUSS_OVER, a Helmholtz or mass handle, hanging-node masks, BP5_GEOM_AFFINE, BP5_METRIC_F32, a handle with a
+ * communicator and neighbours (a rank-local slab with ghosts and no communicator is fine). */
+/* Doubles of the operator's metric array: TEN planes, plane-major, each n_cells * (p+1)^3 in the pair layout of the merged metric --
+ * planes 0..8 K[d][e] at 3 d + e, plane 9 kappa(x_q) JxW.  An array of its own: the handle's plane count (bp5_mf_coef_size) is not touched.
+ * (replaces MatrixFree::reinit's inverse_jacobian / JxW for the vector-valued FEEvaluation) */
+int bp5_elasticity_coef_size(const bp5_mf *mf, size_t *n_doubles);
+/* Fills it (one setup kernel; replaces MatrixFree::reinit with update_gradients | update_JxW_values and the coefficient evaluation). */
+int bp5_elasticity_compute_metric(bp5_mf *mf, double *coef);
+/* dst = [0 +] A src, dst_c = src_c on Dirichlet DoFs: per-block zero-fill, ONE kernel launch for the three components
+ * (apply_pencil_elasticity_kernel, the degree's default pencil shape, both quadratures), the Dirichlet copy.  Scatter by atomics: not
+ * bitwise reproducible.  Entries [n_owned + n_ghost, ld) are never read or written.  (replaces ElasticityOperator::vmult: cell_loop with
+ * FEEvaluation<dim, p, n_q, dim>::evaluate / submit_symmetric_gradient / integrate; CEED solids: ApplyJacobian of the linear problem) */
+int bp5_elasticity_apply(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, int zero_dst);
+/* dst += A src over the cells [cell_begin, cell_end) (any range, also ragged against the kernel's teams; empty: nothing is launched); no
+ * zero-fill, no Dirichlet copy.  (replaces one colour of MatrixFree::cell_loop) */
+int bp5_elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t cell_begin,
+                               uint32_t cell_end);
+/* The three diagonals as one block vector (they differ per component): diag_a[i] = sum_cells sum_q s [ (lambda + mu) (d_a phi_i)^2 +
+ * mu |grad phi_i|^2 ], 1 on Dirichlet DoFs; invert != 0: the reciprocals (owned entries) -- bp5_compute_diagonal's convention, block by
+ * block.  (replaces MatrixFreeOperators::Base::compute_diagonal of the vector-valued operator) */
+int bp5_elasticity_compute_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag, int invert);
+/* SolverCG on A x = b: the BP5_CG_PLAIN recurrence of bp5_cg_solve_components with the coupled application as operator step and a BLOCK
+ * inverse diagonal (inv_diag: three blocks ld apart as bp5_elasticity_compute_diagonal returns them, or NULL == identity).  One Krylov space,
+ * the stop rule on the stacked ||g||_2; check_every, breakdown status and result fields as there (dot_products_fused == 0); BP5_CG_MERGED:
+ * BP5_ERR_UNSUPPORTED.  (replaces SolverCG<BlockVector>::solve(A, x, b, PreconditionJacobi) of step-8) */
+int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, const double *b, double *x,
+                            const bp5_cg_params *params, bp5_cg_result *result_host);
+
 /* BP5_CG_MERGED on the packed block kernel (cell bricks, one rank's cells, diag == NULL): by default the operator's
  * write-out and combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311: p.v, v.v, r.v, r.r)
  * and write the Dirichlet rows, so the separate pass over p, r, v and the copy_constrained launch disappear.  Same
