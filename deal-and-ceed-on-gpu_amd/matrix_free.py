@@ -82,6 +82,7 @@ class MatrixFree:
     def __init__(self):
         self._h = None
         self.mesh = None
+        self.stream = None
 
     def reinit(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, device=0, stream=None, comm=None):
         """== mf_data.reinit(mapping, dof_handler, constraints, quad, additional_data),
@@ -91,6 +92,7 @@ class MatrixFree:
         self.mesh, self.quadrature, self.coefficient, self.device = mesh, quadrature, coefficient, device
         if stream is None:
             stream = torch.cuda.current_stream(device).cuda_stream
+        stream = int(getattr(stream, "cuda_stream", stream))          # a torch stream or a raw hipStream_t; 0: the null stream
         d = _lib.MFDesc()
         d.dim, d.degree, d.quadrature, d.coefficient = 3, mesh.degree, quadrature, coefficient
         d.n_cells, d.n_interior_cells, d.n_owned, d.n_ghost = mesh.n_cells, mesh.n_interior_cells, mesh.n_owned, mesh.n_ghost
@@ -115,6 +117,7 @@ class MatrixFree:
         h = C.c_void_p()
         _lib.check(L.bp5_mf_create(C.byref(d), C.byref(h)))
         self._h = h
+        self.stream = stream
         self.n_owned, self.n_ghost, self.n_local = mesh.n_owned, mesh.n_ghost, mesh.n_owned + mesh.n_ghost
         self.comm = comm
         if comm is not None:
@@ -141,6 +144,18 @@ class MatrixFree:
 
     def synchronize(self):
         _lib.check(_lib.lib().bp5_mf_sync(self.handle))
+
+    def set_stream(self, stream):
+        """bp5_mf_set_stream: every later call on this handle enqueues on `stream` (a torch.cuda.Stream or a raw hipStream_t as an int; 0: the
+        null stream; None is refused -- in reinit it means torch's current stream, and a handle is never moved silently).  The caller orders the new stream behind the work already enqueued on the old one.  The classes here
+        allocate and fill with torch, so `stream` should be torch's current stream whenever they are used (`with torch.cuda.stream(s):`).
+        Objects built on the handle (PreconditionChebyshev, PreconditionMG, transfers) follow it: they hold no stream of their own; the
+        levels of one PreconditionMG must be moved together."""
+        if stream is None:
+            raise BP5Error(1, "set_stream: pass a stream, or 0 for the null stream")
+        stream = int(getattr(stream, "cuda_stream", stream))
+        _lib.check(_lib.lib().bp5_mf_set_stream(self.handle, C.c_void_p(stream)))
+        self.stream = stream
 
     def set_geometry_mode(self, mode):
         """BP5_GEOM_MERGED6 (reference representation, default) or BP5_GEOM_AFFINE (affine meshes)."""
@@ -784,7 +799,7 @@ def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4, metric_precision=None):
     if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
         raise BP5Error(1, f"make_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
     mf, m = fine_op.mf_data, fine_op.mf_data.mesh
-    stream = _torch().cuda.current_stream(mf.device).cuda_stream
+    stream = mf.stream                # the levels share fine_op's stream (bp5_mg_create refuses anything else), whatever torch's current one is
 
     geometry = dict(geometry=fine_op.geometry) if fine_op.geometry else {}     # (HelmholtzOperator: six-plane geometry only)
     if metric_precision is not None:
@@ -839,6 +854,10 @@ class PreconditionMG:
             _refuse_elasticity("PreconditionMG", o)
         if not ops or not all(isinstance(o, PoissonOperator) for o in ops):
             raise BP5Error(1, "PreconditionMG needs a list of PoissonOperators, fine to coarse")
+        # bp5_mg_create checks the handles themselves, but the transfers it takes are built first, and bp5_mg_transfer_create refuses such a
+        # pair with words of its own: the same refusal here, in bp5_mg_create's words (from MatrixFree.stream, which set_stream keeps current)
+        if len({o.mf_data.stream for o in ops}) > 1:
+            raise BP5Error(1, "PreconditionMG: the levels must share one stream (MatrixFree.set_stream moves each of them)")
         self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
         self.transfers = [MGTwoLevelTransfer(f, c, geometric=f.mf_data.mesh.degree == c.mf_data.mesh.degree) for f, c in zip(ops[:-1], ops[1:])]
         ids = []
