@@ -384,7 +384,7 @@ extern "C" int bp5_mf_get_apply_variant(bp5_mf *mf, int *effective)
 template <int n>
 static int launch_geometry(bp5_mf *mf, GeomOut o)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
+  const uint32_t grid = cell_grid(mf, 65535u * 16);
   o.hang_mask = mf->has_hanging ? mf->d_hang_mask : nullptr;
   o.hang_I = mf->d_hang_I;
   if (o.coef && mf->f32_metric()) // float planes behind o.coef (affine / Data-mirror launches write no planes: the double build)
@@ -396,20 +396,12 @@ static int launch_geometry(bp5_mf *mf, GeomOut o)
   KERNEL_CHECK();
   return BP5_OK;
 }
-#define DISPATCH_N(fn, ...)                                                                                        \
-  switch (mf->n) {                                                                                                 \
-    case 2: return fn<2>(__VA_ARGS__);                                                                             \
-    case 3: return fn<3>(__VA_ARGS__);                                                                             \
-    case 4: return fn<4>(__VA_ARGS__);                                                                             \
-    case 5: return fn<5>(__VA_ARGS__);                                                                             \
-    case 6: return fn<6>(__VA_ARGS__);                                                                             \
-    case 7: return fn<7>(__VA_ARGS__);                                                                             \
-    case 8: return fn<8>(__VA_ARGS__);                                                                             \
-    case 9: return fn<9>(__VA_ARGS__);                                                                             \
-  }                                                                                                                \
-  return fail(BP5_ERR_INVALID, "unsupported degree")
 
-static int geometry_affine(bp5_mf *mf, GeomOut o) { DISPATCH_N(launch_geometry, mf, o); }
+// the geometry launch of the handle's degree (the planes, the affine scalars or the Data mirror: whatever o asks for)
+static int geometry_dispatch(bp5_mf *mf, GeomOut o)
+{
+  return for_degree(mf->degree, [&](auto P) { return launch_geometry<P() + 1>(mf, o); });
+}
 extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
 {
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
@@ -428,7 +420,7 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
     HIP_TRY(hipMalloc((void **)&dev, std::max<size_t>(mf->n_cells, 1) * sizeof(double)));
     GeomOut o{};
     o.scalar = sp; o.gcell = gc; o.deviation = dev; o.n_cells = mf->n_cells;
-    int st = geometry_affine(mf, o);
+    int st = geometry_dispatch(mf, o);
     std::vector<double> h(mf->n_cells);
     if (st == BP5_OK && hipMemcpyAsync(h.data(), dev, mf->n_cells * sizeof(double), hipMemcpyDeviceToHost, mf->stream) != hipSuccess) st = BP5_ERR_HIP;
     if (st == BP5_OK && hipStreamSynchronize(mf->stream) != hipSuccess) st = BP5_ERR_HIP;
@@ -449,13 +441,12 @@ extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
 template <int n>
 static int launch_mass_plane(bp5_mf *mf, double *coef)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
+  const uint32_t grid = cell_grid(mf, 65535u * 16);
   hipLaunchKernelGGL(mass_plane_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient, mf->n_cells, coef,
                      mf->coef_cell_stride);
   KERNEL_CHECK();
   return BP5_OK;
 }
-static int mass_plane_dispatch(bp5_mf *mf, double *coef) { DISPATCH_N(launch_mass_plane, mf, coef); }
 extern "C" int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef)
 {
   if (!mf || !coef) return fail(BP5_ERR_INVALID, "null argument");
@@ -466,7 +457,7 @@ extern "C" int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef)
   }
   if (mf->operator_kind == BP5_OP_MASS) { // one plane rho JxW (plane-major layout, conforming mesh: bp5_mf_set_operator has seen to both)
     mf->coef_planes_committed = mf->n_planes();
-    return mass_plane_dispatch(mf, coef);
+    return for_degree(mf->degree, [&](auto P) { return launch_mass_plane<P() + 1>(mf, coef); });
   }
   GeomOut o{};
   o.coef = coef;
@@ -474,7 +465,7 @@ extern "C" int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef)
   o.helmholtz = mf->operator_kind == BP5_OP_HELMHOLTZ;
   mf->coef_planes_committed = mf->n_planes();
   if (o.helmholtz && mf->coef_cell_stride != (uint64_t)mf->n3) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs the plane-major metric layout");
-  DISPATCH_N(launch_geometry, mf, o);
+  return geometry_dispatch(mf, o);
 }
 
 template <int n>
@@ -495,7 +486,7 @@ extern "C" int bp5_mf_metric_to_reference_layout(bp5_mf *mf, const double *coef,
   if (!mf || !coef || !coef_ref) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
   if (mf->overint()) return overint_to_reference_layout(mf, coef, coef_ref);
-  DISPATCH_N(launch_permute, mf, coef, coef_ref);
+  return for_degree(mf->degree, [&](auto P) { return launch_permute<P() + 1>(mf, coef, coef_ref); });
 }
 
 static uint32_t padding_length(int n)
@@ -504,7 +495,6 @@ static uint32_t padding_length(int n)
   while (p < (uint32_t)(n * n * n)) p <<= 1;
   return p;
 }
-static int geometry_data(bp5_mf *mf, GeomOut o) { DISPATCH_N(launch_geometry, mf, o); }
 
 extern "C" int bp5_mf_get_data(bp5_mf *mf, int color, bp5_mf_data *out)
 {
@@ -531,7 +521,7 @@ extern "C" int bp5_mf_get_data(bp5_mf *mf, int color, bp5_mf_data *out)
                                mf->n3 * sizeof(uint32_t), mf->n_cells, hipMemcpyDeviceToDevice, mf->stream));
     GeomOut o{};
     o.inv_jac = mf->d_inv_jac; o.JxW = mf->d_JxW; o.q_points = mf->d_qpoints; o.pad = mf->pad; o.geo_plane = gp;
-    BP5_TRY(geometry_data(mf, o));
+    BP5_TRY(geometry_dispatch(mf, o));
     HIP_TRY(hipStreamSynchronize(mf->stream));
   }
   out->local_to_global = mf->d_l2g_padded; out->inv_jacobian = mf->d_inv_jac; out->JxW = mf->d_JxW; out->q_points = mf->d_qpoints;
@@ -1182,17 +1172,7 @@ static bool variant_overwrites(const bp5_mf *mf, int ev)
 static int launch_apply(bp5_mf *mf, ApplyCall &call, const double *coef, const double *src, double *dst)
 {
   if (!call.keep_variant) call.set_variant(effective_variant(mf, call.c0, call.c1));
-  switch (mf->degree) {
-    case 1: return apply_degree_impl<1>(mf, call, coef, src, dst);
-    case 2: return apply_degree_impl<2>(mf, call, coef, src, dst);
-    case 3: return apply_degree_impl<3>(mf, call, coef, src, dst);
-    case 4: return apply_degree_impl<4>(mf, call, coef, src, dst);
-    case 5: return apply_degree_impl<5>(mf, call, coef, src, dst);
-    case 6: return apply_degree_impl<6>(mf, call, coef, src, dst);
-    case 7: return apply_degree_impl<7>(mf, call, coef, src, dst);
-    case 8: return apply_degree_impl<8>(mf, call, coef, src, dst);
-  }
-  return fail(BP5_ERR_INVALID, "unsupported degree");
+  return for_degree(mf->degree, [&](auto P) { return apply_degree_impl<P()>(mf, call, coef, src, dst); });
 }
 // ... with nothing asked for but a cell range and the overwrite mode
 static int launch_apply(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1, bool overwrite = false)
@@ -1402,26 +1382,25 @@ extern "C" int bp5_elasticity_compute_diagonal(bp5_mf *mf, const double *coef, d
 template <int n>
 static int launch_rhs(bp5_mf *mf, double *b)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
+  const uint32_t grid = cell_grid(mf, 65535u * 16);
   hipLaunchKernelGGL(rhs_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab_gauss, mf->n_cells, b,
                      mf->has_hanging ? (const uint32_t *)mf->d_hang_mask : (const uint32_t *)nullptr, (const double *)mf->d_hang_I);
   KERNEL_CHECK();
   return BP5_OK;
 }
-static int rhs_dispatch(bp5_mf *mf, double *b) { DISPATCH_N(launch_rhs, mf, b); }
 extern "C" int bp5_assemble_rhs(bp5_mf *mf, double *b)
 {
   if (!mf || !b) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
   HIP_TRY(hipMemsetAsync(b, 0, mf->n_local() * sizeof(double), mf->stream));
-  BP5_TRY(rhs_dispatch(mf, b));
+  BP5_TRY(for_degree(mf->degree, [&](auto P) { return launch_rhs<P() + 1>(mf, b); }));
   if (mf->has_neighbors()) BP5_TRY(bp5_halo_scatter_add(mf, b));
   return bp5_set_constrained(mf, 0.0, b);
 }
 template <int n>
 static int launch_diagonal(bp5_mf *mf, const double *coef, double *diag)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65536u);
+  const uint32_t grid = cell_grid(mf, 65536u);
   const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
   if (mf->operator_kind == BP5_OP_MASS) { // (conforming, one double plane: bp5_mf_set_operator refuses everything else)
     hipLaunchKernelGGL(mass_diagonal_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, coef, mf->coef_cell_stride, mf->d_tab, mf->n_cells, diag);
@@ -1444,7 +1423,10 @@ static int launch_diagonal(bp5_mf *mf, const double *coef, double *diag)
   }
   return BP5_OK;
 }
-static int diagonal_dispatch(bp5_mf *mf, const double *coef, double *diag) { DISPATCH_N(launch_diagonal, mf, coef, diag); }
+static int diagonal_dispatch(bp5_mf *mf, const double *coef, double *diag)
+{
+  return for_degree(mf->degree, [&](auto P) { return launch_diagonal<P() + 1>(mf, coef, diag); });
+}
 extern "C" int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag, int invert)
 {
   if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !diag) return fail(BP5_ERR_INVALID, "null argument");
@@ -1465,13 +1447,16 @@ extern "C" int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag
 template <int n>
 static int launch_l2(bp5_mf *mf, const double *u, double *out)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 4096u);
+  const uint32_t grid = cell_grid(mf, 4096u);
   hipLaunchKernelGGL(l2norm_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab_gauss, mf->n_cells, u,
                      out, mf->has_hanging ? (const uint32_t *)mf->d_hang_mask : (const uint32_t *)nullptr, (const double *)mf->d_hang_I);
   KERNEL_CHECK();
   return BP5_OK;
 }
-static int l2_dispatch(bp5_mf *mf, const double *u, double *out) { DISPATCH_N(launch_l2, mf, u, out); }
+static int l2_dispatch(bp5_mf *mf, const double *u, double *out)
+{
+  return for_degree(mf->degree, [&](auto P) { return launch_l2<P() + 1>(mf, u, out); });
+}
 extern "C" int bp5_l2_norm_solution(bp5_mf *mf, const double *u, double *result)
 {
   if (!mf || !u || !result) return fail(BP5_ERR_INVALID, "null argument");
@@ -3250,22 +3235,24 @@ static int mg_geo_restrict_launch(bp5_mg_transfer *t, const double *b, const dou
   KERNEL_CHECK();
   return BP5_OK;
 }
-#define MG_GEO_DISPATCH(fn, t, ...)                                                                                \
-  switch (t->pf) {                                                                                                 \
-  case 1: return fn<2>(t, __VA_ARGS__);                                                                            \
-  case 2: return fn<3>(t, __VA_ARGS__);                                                                            \
-  case 3: return fn<4>(t, __VA_ARGS__);                                                                            \
-  case 4: return fn<5>(t, __VA_ARGS__);                                                                            \
-  default: return fail(BP5_ERR_INVALID, "geometric multigrid transfer: degree must be 1..4");                      \
-  }
+// ... of the fine level's degree
+template <class F>
+static int mg_geo_dispatch(const bp5_mg_transfer *t, F &&f)
+{
+  const char *refusal = "geometric multigrid transfer: degree must be 1..4";
+  return for_degree(t->pf <= 4 ? t->pf : 0, [&](auto P) {
+    if constexpr (P() <= 4) return f(P);
+    else return fail(BP5_ERR_INVALID, refusal);
+  }, refusal);
+}
 static int mg_prolongate_dispatch(bp5_mg_transfer *t, double *dst, const double *src)
 {
-  if (t->geometric) MG_GEO_DISPATCH(mg_geo_prolongate_launch, t, dst, src);
+  if (t->geometric) return mg_geo_dispatch(t, [&](auto P) { return mg_geo_prolongate_launch<P() + 1>(t, dst, src); });
   MG_DISPATCH(mg_prolongate_launch, t, dst, src);
 }
 static int mg_restrict_dispatch(bp5_mg_transfer *t, const double *b, const double *tv)
 {
-  if (t->geometric) MG_GEO_DISPATCH(mg_geo_restrict_launch, t, b, tv);
+  if (t->geometric) return mg_geo_dispatch(t, [&](auto P) { return mg_geo_restrict_launch<P() + 1>(t, b, tv); });
   MG_DISPATCH(mg_restrict_launch, t, b, tv);
 }
 

@@ -357,6 +357,39 @@ inline int zero_dst(bp5_mf *mf, double *dst) // ahead of a launch that accumulat
   return BP5_OK;
 }
 
+// The ONE switch on the degree: f(std::integral_constant<int, P>{}) for P = 1..8.  A caller templated on n = P + 1 writes P() + 1.
+template <class F>
+inline int for_degree(int degree, F &&f, const char *unsupported = "unsupported degree")
+{
+  switch (degree) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+  return fail(BP5_ERR_INVALID, unsupported);
+}
+
+// The pencil launch shape: cells [c0, c1) in teams of CPT cells, TPB teams of TW waves per workgroup, the workgroups dealt out to the 8 XCDs
+// (the kernels undo the dealing with teams_per_xcd).  Fills the range and team counts of a; the launcher adds its own LDS size.
+struct PencilLaunch { dim3 grid, block; };
+template <int CPT, int TW, int TPB>
+inline PencilLaunch pencil_launch(ApplyArgs &a, uint32_t c0, uint32_t c1)
+{
+  a.cell_begin = c0; a.cell_end = c1;
+  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
+  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
+  a.teams_per_xcd = (nblk + 7) / 8;
+  return {dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB)};
+}
+
+// grid of a setup launch (one cell per workgroup, grid-stride beyond the cap; an empty handle still launches one)
+inline uint32_t cell_grid(const bp5_mf *mf, uint32_t cap) { return std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), cap); }
+
 // The degree's default pencil launch: p <= 3 four one-wave teams per workgroup, p >= 4 one four-wave team; n^2 lanes per cell, every plane prefetched.
 // Users: variant 0 of every operator class (interior stores at p >= 5; hanging + affine included) and the block-vector kernel
 template <int DEG>
@@ -375,15 +408,12 @@ inline int launch_apply_t(bp5_mf *mf, ApplyCall &, const double *coef, const dou
   if ((ABL & BLK_HANG) && !mf->has_hanging) return fail(BP5_ERR_INVALID, "the hanging-node build needs constraint masks");
   if (overwrite) BP5_TRY(zero_dst(mf, dst));
   ApplyArgs a = apply_args(mf, (ABL & BLK_AFFINE) != 0, coef, src, dst);
-  a.cell_begin = c0; a.cell_end = c1;
-  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
-  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
-  a.teams_per_xcd = (nblk + 7) / 8;
+  const PencilLaunch pl = pencil_launch<CPT, TW, TPB>(a, c0, c1);
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const size_t lds = (size_t)TPB * CPT * L::CS * sizeof(double);
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_kernel<%d,%s,%d,%d,%d,%s,%d>", P, COLL ? "true" : "false", TW, LPC, TPB, PF ? "true" : "false", ABL);
-  hipLaunchKernelGGL((apply_pencil_kernel<P, COLL, TW, LPC, TPB, PF, ABL>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a,
+  hipLaunchKernelGGL((apply_pencil_kernel<P, COLL, TW, LPC, TPB, PF, ABL>), pl.grid, pl.block, lds, mf->stream, a,
                      sh);
   KERNEL_CHECK();
   return BP5_OK;
@@ -398,16 +428,13 @@ inline int launch_apply_components_t(bp5_mf *mf, const double *coef, int n_compo
   constexpr int CPT = 64 * TW / LPC;
   using L = LdsLayout<n, LPC>;
   ApplyArgs a = apply_args(mf, false, coef, src, dst);
-  a.cell_begin = c0; a.cell_end = c1;
-  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
-  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
-  a.teams_per_xcd = (nblk + 7) / 8;
+  const PencilLaunch pl = pencil_launch<CPT, TW, TPB>(a, c0, c1);
   ComponentArgs ca{(uint32_t)n_components, (uint64_t)ld};
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const size_t lds = (size_t)TPB * CPT * L::CS * sizeof(double);
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_components_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", TW, LPC, TPB);
-  hipLaunchKernelGGL((apply_pencil_components_kernel<P, COLL, TW, LPC, TPB>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a, ca, sh);
+  hipLaunchKernelGGL((apply_pencil_components_kernel<P, COLL, TW, LPC, TPB>), pl.grid, pl.block, lds, mf->stream, a, ca, sh);
   KERNEL_CHECK();
   return BP5_OK;
 }
@@ -419,15 +446,12 @@ inline int launch_apply_mass_t(bp5_mf *mf, const double *coef, const double *src
   constexpr int CPT = 64 * TW / LPC;
   if (overwrite) BP5_TRY(zero_dst(mf, dst));
   ApplyArgs a = apply_args(mf, false, coef, src, dst);
-  a.cell_begin = c0; a.cell_end = c1;
-  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
-  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
-  a.teams_per_xcd = (nblk + 7) / 8;
+  const PencilLaunch pl = pencil_launch<CPT, TW, TPB>(a, c0, c1);
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const size_t lds = COLL ? 0 : (size_t)TPB * CPT * mass_tile_stride<n, LPC>() * sizeof(double); // one field per cell slot (collocation: pointwise, no tile)
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_mass_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", TW, LPC, TPB);
-  hipLaunchKernelGGL((apply_pencil_mass_kernel<P, COLL, TW, LPC, TPB>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a, sh);
+  hipLaunchKernelGGL((apply_pencil_mass_kernel<P, COLL, TW, LPC, TPB>), pl.grid, pl.block, lds, mf->stream, a, sh);
   KERNEL_CHECK();
   return BP5_OK;
 }

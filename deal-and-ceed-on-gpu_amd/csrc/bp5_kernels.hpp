@@ -3287,6 +3287,40 @@ __device__ __forceinline__ double invert3(const double (&J)[3][3], double (&K)[3
   return det;
 }
 
+// This thread's quadrature point of a cell in the generic layout, the prologue of the setup kernels: gathers the cell's node coordinates into
+// X[3][n3] (g: this thread's global index) and fills K = J^-1, x_q and jxw = |det J| w_i w_j w_k; returns det J.  hang_mask != NULL: the coordinate
+// field is an FE function, so a constrained face takes its nodes from the coarse face's.  The whole block calls it; X, t1, t2 are free again on return.
+template <int n>
+__device__ double cell_point(const uint32_t *l2g, const double *coords, const double *tab, const uint32_t *hang_mask, const double *hang_I, uint64_t cell,
+                             double *X, double *t1, double *t2, int i, int j, int k, double (&K)[3][3], double (&xq)[3], double &jxw, uint32_t &g)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  const int q = i + n * (j + n * k);
+  g = l2g[cell * n3 + q];
+  for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
+  __syncthreads();
+  if (hang_mask)
+    for (int e = 0; e < 3; ++e) hang_resolve3<n, false>(hang_mask[cell], hang_I, X + e * n3, t1, i, j, k);
+  double J[3][3];
+  cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
+  const double det = invert3(J, K);
+  const double *w = tab + 2 * n2;
+  jxw = fabs(det) * w[i] * w[j] * w[k];
+  return det;
+}
+
+// G = K K^T, planes 00, 11, 22, 01, 02, 12 (JacobianFunctor, bp5/step-64.cu:84-114).  overint_metric_kernel writes the same six out by hand: through
+// this function its n = 8 build contracted them into other fused multiply-adds and the planes moved by an ulp
+__device__ __forceinline__ void kkt6(const double (&K)[3][3], double (&G)[6])
+{
+  G[0] = K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2];
+  G[1] = K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2];
+  G[2] = K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2];
+  G[3] = K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2];
+  G[4] = K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2];
+  G[5] = K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2];
+}
+
 // == JacobianFunctor (bp5/step-64.cu:84-114) fused with the geometry part of MatrixFree::reinit
 // MT: entry type of the merged-metric planes behind o.coef (float on an FP32-metric handle: every entry is computed in double exactly as for
 // double planes and rounded ONCE, to nearest, when it is stored; strides count entries)
@@ -3299,32 +3333,21 @@ __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, 
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
   const int q = i + n * (j + n * k);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
-    const uint32_t g = l2g[cell * n3 + q];
-    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
-    __syncthreads();
-    if (o.hang_mask) // the coordinate field is an FE function: the constrained face takes its nodes from the coarse face's
-      for (int e = 0; e < 3; ++e) hang_resolve3<n, false>(o.hang_mask[cell], o.hang_I, X + e * n3, t1, i, j, k);
-    double J[3][3], K[3][3], xq[3];
-    cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
-    const double det = invert3(J, K);
-    const double *w = tab + 2 * n2;
-    const double jxw = fabs(det) * w[i] * w[j] * w[k];
+    double K[3][3], xq[3], jxw;
+    uint32_t g;
+    cell_point<n>(l2g, coords, tab, o.hang_mask, o.hang_I, cell, X, t1, t2, i, j, k, K, xq, jxw, g);
     if (o.coef) {
+      double G[6];
+      kkt6(K, G);
       const double kap = kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
       const double s = o.helmholtz ? jxw : jxw * kap;
       MT *c = reinterpret_cast<MT *>(o.coef) + cell * o.cell_stride + coef_off<n>(i, j + n * k); // pair layout (coef_off)
       if (o.helmholtz) c[6 * o.plane_stride] = (MT)(jxw * kap);
-      c[0 * o.plane_stride] = (MT)(s * (K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2]));
-      c[1 * o.plane_stride] = (MT)(s * (K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2]));
-      c[2 * o.plane_stride] = (MT)(s * (K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2]));
-      c[3 * o.plane_stride] = (MT)(s * (K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2]));
-      c[4 * o.plane_stride] = (MT)(s * (K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2]));
-      c[5 * o.plane_stride] = (MT)(s * (K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2]));
+      for (int c6 = 0; c6 < 6; ++c6) c[c6 * o.plane_stride] = (MT)(s * G[c6]);
     }
     if (o.scalar) {
-      double Gq[6] = {K[0][0] * K[0][0] + K[0][1] * K[0][1] + K[0][2] * K[0][2], K[1][0] * K[1][0] + K[1][1] * K[1][1] + K[1][2] * K[1][2],
-                      K[2][0] * K[2][0] + K[2][1] * K[2][1] + K[2][2] * K[2][2], K[0][0] * K[1][0] + K[0][1] * K[1][1] + K[0][2] * K[1][2],
-                      K[0][0] * K[2][0] + K[0][1] * K[2][1] + K[0][2] * K[2][2], K[1][0] * K[2][0] + K[1][1] * K[2][1] + K[1][2] * K[2][2]};
+      double Gq[6];
+      kkt6(K, Gq);
       o.scalar[cell * n3 + coef_off<n>(i, j + n * k)] = jxw * kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
       // reference values of the cell: q-point 0
       for (int c6 = 0; c6 < 6; ++c6) {
@@ -3354,8 +3377,7 @@ __global__ void __launch_bounds__(n *n *n) geometry_kernel(const uint32_t *l2g, 
 }
 
 // The ONE plane of a mass handle (BP5_OP_MASS): rho(x_q) JxW in the pair layout, rho = the handle's BP5_COEF_* function -- the entry geometry_kernel
-// writes as plane 6 of a Helmholtz handle, by the same expressions.  A kernel of its own so that no build of geometry_kernel changes; conforming
-// meshes only (bp5_mf_set_operator refuses hanging-node masks).
+// writes as plane 6 of a Helmholtz handle, from the same cell_point.  Conforming meshes only (bp5_mf_set_operator refuses hanging-node masks).
 template <int n>
 __global__ void __launch_bounds__(n *n *n) mass_plane_kernel(const uint32_t *l2g, const double *coords, const double *tab, int kappa_mode, uint32_t n_cells,
                                                             double *coef, uint64_t cell_stride)
@@ -3363,16 +3385,10 @@ __global__ void __launch_bounds__(n *n *n) mass_plane_kernel(const uint32_t *l2g
   constexpr int n2 = n * n, n3 = n2 * n;
   __shared__ double X[3 * n3], t1[n3], t2[n3];
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
-  const int q = i + n * (j + n * k);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
-    const uint32_t g = l2g[cell * n3 + q];
-    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
-    __syncthreads();
-    double J[3][3], K[3][3], xq[3];
-    cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
-    const double det = invert3(J, K);
-    const double *w = tab + 2 * n2;
-    const double jxw = fabs(det) * w[i] * w[j] * w[k];
+    double K[3][3], xq[3], jxw;
+    uint32_t g;
+    cell_point<n>(l2g, coords, tab, nullptr, nullptr, cell, X, t1, t2, i, j, k, K, xq, jxw, g);
     coef[cell * cell_stride + coef_off<n>(i, j + n * k)] = jxw * kappa_eval(kappa_mode, xq[0], xq[1], xq[2]);
     __syncthreads();
   }
@@ -3403,6 +3419,7 @@ __global__ void __launch_bounds__(n *n *n) rhs_kernel(const uint32_t *l2g, const
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
   const int q = i + n * (j + n * k);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    // (cell_point's prologue, written out: through the shared function assemble_rhs took 7 % longer at p = 4, 40^3 cells)
     const uint32_t g = l2g[cell * n3 + q];
     for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
     __syncthreads();
@@ -3427,6 +3444,33 @@ __global__ void __launch_bounds__(n *n *n) rhs_kernel(const uint32_t *l2g, const
   }
 }
 
+// The 1-D factors of the diagonal kernels: the entrywise products NN = N*N, DD = D*D, ND = N*D of the tables, n*n each, in LDS.  The whole block calls it.
+template <int n>
+__device__ void diag_products(const double *tab, double *NN, double *DD, double *ND)
+{
+  constexpr int n2 = n * n;
+  const int q = threadIdx.x + n * (threadIdx.y + n * threadIdx.z);
+  if (q < n2) {
+    const double a = tab[q], b = tab[n2 + q];
+    NN[q] = a * a;
+    DD[q] = b * b;
+    ND[q] = a * b;
+  }
+  __syncthreads();
+}
+// The term of plane c in this thread's diagonal entry, sum_abc S(a,b,c) X[a,i] Y[b,j] Z[c,k] (S in LDS, complete; the whole block calls it).  c: a
+// plane of a symmetric 3 x 3 form in the order 00, 11, 22, 01, 02, 12 -- the factor of a direction is DD where the plane differentiates twice in
+// it, ND once, NN not at all, and an off-diagonal plane stands for two terms -- or c == 6, a mass plane: NN in every direction (reads NN only)
+template <int n>
+__device__ double diag_plane_term(int c, const double *NN, const double *DD, const double *ND, const double *S, double *t1, double *t2, int i, int j, int k)
+{
+  const double *X = (c == 0) ? DD : (c == 3 || c == 4) ? ND : NN;
+  const double *Y = (c == 1) ? DD : (c == 3 || c == 5) ? ND : NN;
+  const double *Z = (c == 2) ? DD : (c == 4 || c == 5) ? ND : NN;
+  const double y = Cell3<n>::template tensor3<true>(X, Y, Z, S, t1, t2, i, j, k);
+  return (c < 3 || c == 6) ? y : 2.0 * y;
+}
+
 // diag(A) of the cell loop: diag_ijk += sum_abc S_de(a,b,c) X_de[a,i] Y_de[b,j] Z_de[c,k] with the entrywise products
 // N*N, D*D, N*D as 1-D factors (six transposed tensor contractions per cell).  Setup-time kernel: one block per cell,
 // one thread per local DoF.  coef: the handle's six planes (device layout, q index = a*n*n + b + n*c), or, in affine
@@ -3440,13 +3484,7 @@ __global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, 
   __shared__ double S[n3], t1[n3], t2[n3], NN[n2], DD[n2], ND[n2];
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
   const int q = i + n * (j + n * k);
-  if (q < n2) {
-    const double a = tab[q], b = tab[n2 + q];
-    NN[q] = a * a;
-    DD[q] = b * b;
-    ND[q] = a * b;
-  }
-  __syncthreads();
+  diag_products<n>(tab, NN, DD, ND);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
     double acc = 0.0;
     for (int c = 0; c < n_planes; ++c) { // (n_planes == 7: the Helmholtz operator's mass plane a JxW with the factors N*N in every direction)
@@ -3454,11 +3492,7 @@ __global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, 
       const uint64_t at = cell * (gcell ? (uint64_t)n3 : cell_stride) + coef_off<n>(i, j + n * k);
       S[q] = gcell ? coef[at] * gcell[(uint64_t)c * n_cells + cell] : coef[(uint64_t)c * plane_stride + at];
       __syncthreads();
-      const double *X = (c == 0) ? DD : (c == 3 || c == 4) ? ND : NN;
-      const double *Y = (c == 1) ? DD : (c == 3 || c == 5) ? ND : NN;
-      const double *Z = (c == 2) ? DD : (c == 4 || c == 5) ? ND : NN;
-      const double y = Cell3<n>::template tensor3<true>(X, Y, Z, S, t1, t2, i, j, k);
-      acc += (c < 3 || c == 6) ? y : 2.0 * y;
+      acc += diag_plane_term<n>(c, NN, DD, ND, S, t1, t2, i, j, k);
     }
     // entries on constrained faces / edges stand for coarse DoFs: diagonal_hanging_kernel computes theirs
     const uint32_t hm = hang_mask ? hang_mask[cell] : 0u;
@@ -3468,7 +3502,7 @@ __global__ void __launch_bounds__(n *n *n) diagonal_kernel(const uint32_t *l2g, 
 }
 
 // diag(M) of a mass handle (BP5_OP_MASS): diag_ijk += sum_abc S(a,b,c) NN[a,i] NN[b,j] NN[c,k], S = the handle's one plane rho JxW and NN = N*N
-// entrywise -- the term diagonal_kernel adds for plane 6 of a Helmholtz handle, as a kernel of its own so that no build of diagonal_kernel changes
+// entrywise -- the term diagonal_kernel adds for plane 6 of a Helmholtz handle (diag_plane_term at c = 6, which reads NN only)
 template <int n>
 __global__ void __launch_bounds__(n *n *n) mass_diagonal_kernel(const uint32_t *l2g, const double *coef, uint64_t cell_stride, const double *tab, uint32_t n_cells,
                                                                double *diag)
@@ -3482,14 +3516,14 @@ __global__ void __launch_bounds__(n *n *n) mass_diagonal_kernel(const uint32_t *
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
     S[q] = coef[cell * cell_stride + coef_off<n>(i, j + n * k)]; // this thread's q-point (a,b,c) = (i,j,k) in the device (pair) layout
     __syncthreads();
-    const double y = Cell3<n>::template tensor3<true>(NN, NN, NN, S, t1, t2, i, j, k);
+    const double y = diag_plane_term<n>(6, NN, nullptr, nullptr, S, t1, t2, i, j, k);
     atomic_add_f64(diag + l2g[cell * n3 + q], y);
   }
 }
 
 // The TEN planes of the elasticity operator (apply_pencil_elasticity_kernel): K[d][e] at plane 3 d + e and kappa(x_q) JxW at plane 9, plane-major,
-// each in the pair layout -- what geometry_kernel forms before it merges them, by the same expressions.  A kernel of its own so that no build of
-// geometry_kernel changes; conforming meshes only (the elasticity entry points refuse hanging-node masks).
+// each in the pair layout -- what geometry_kernel forms before it merges them, from the same cell_point.  Conforming meshes only (the elasticity
+// entry points refuse hanging-node masks).
 template <int n>
 __global__ void __launch_bounds__(n *n *n) elasticity_metric_kernel(const uint32_t *l2g, const double *coords, const double *tab, int kappa_mode, uint32_t n_cells,
                                                                    double *coef, uint64_t plane_stride)
@@ -3497,16 +3531,10 @@ __global__ void __launch_bounds__(n *n *n) elasticity_metric_kernel(const uint32
   constexpr int n2 = n * n, n3 = n2 * n;
   __shared__ double X[3 * n3], t1[n3], t2[n3];
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
-  const int q = i + n * (j + n * k);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
-    const uint32_t g = l2g[cell * n3 + q];
-    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
-    __syncthreads();
-    double J[3][3], K[3][3], xq[3];
-    cell_jacobian<n>(tab, X, t1, t2, i, j, k, J, xq);
-    const double det = invert3(J, K);
-    const double *w = tab + 2 * n2;
-    const double jxw = fabs(det) * w[i] * w[j] * w[k];
+    double K[3][3], xq[3], jxw;
+    uint32_t g;
+    cell_point<n>(l2g, coords, tab, nullptr, nullptr, cell, X, t1, t2, i, j, k, K, xq, jxw, g);
     double *c = coef + cell * n3 + coef_off<n>(i, j + n * k);
     for (int d = 0; d < 3; ++d)
       for (int e = 0; e < 3; ++e) c[(uint64_t)(3 * d + e) * plane_stride] = K[d][e];
@@ -3527,13 +3555,7 @@ __global__ void __launch_bounds__(n *n *n) elasticity_diagonal_kernel(const uint
   __shared__ double S[n3], t1[n3], t2[n3], NN[n2], DD[n2], ND[n2];
   const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
   const int q = i + n * (j + n * k);
-  if (q < n2) {
-    const double a = tab[q], b = tab[n2 + q];
-    NN[q] = a * a;
-    DD[q] = b * b;
-    ND[q] = a * b;
-  }
-  __syncthreads();
+  diag_products<n>(tab, NN, DD, ND);
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
     const double *cq = coef + cell * n3 + coef_off<n>(i, j + n * k); // this thread's q-point (a,b,c) = (i,j,k) in the device (pair) layout
     double K[3][3];
@@ -3547,11 +3569,7 @@ __global__ void __launch_bounds__(n *n *n) elasticity_diagonal_kernel(const uint
         const int d = c < 3 ? c : c == 5 ? 1 : 0, e = c < 3 ? c : c == 3 ? 1 : 2; // planes 00, 11, 22, 01, 02, 12
         S[q] = s * ((lambda + mu) * K[d][a] * K[e][a] + mu * (K[d][0] * K[e][0] + K[d][1] * K[e][1] + K[d][2] * K[e][2]));
         __syncthreads();
-        const double *X = (c == 0) ? DD : (c == 3 || c == 4) ? ND : NN;
-        const double *Y = (c == 1) ? DD : (c == 3 || c == 5) ? ND : NN;
-        const double *Z = (c == 2) ? DD : (c == 4 || c == 5) ? ND : NN;
-        const double y = Cell3<n>::template tensor3<true>(X, Y, Z, S, t1, t2, i, j, k);
-        acc += c < 3 ? y : 2.0 * y;
+        acc += diag_plane_term<n>(c, NN, DD, ND, S, t1, t2, i, j, k);
       }
       atomic_add_f64(diag + (uint64_t)a * ld + gi, acc);
     }
@@ -3623,22 +3641,16 @@ __global__ void __launch_bounds__(n *n *n) l2norm_kernel(const uint32_t *l2g, co
   const int q = i + n * (j + n * k);
   double acc = 0.0;
   for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
-    const uint32_t g = l2g[cell * n3 + q];
-    for (int e = 0; e < 3; ++e) X[e * n3 + q] = coords[3 * (uint64_t)g + e];
+    double K[3][3], xq[3], jxw;
+    uint32_t g;
+    const double det = cell_point<n>(l2g, coords, tab_gauss, hang_mask, hang_I, cell, X, t1, t2, i, j, k, K, xq, jxw, g);
     v[q] = u[g];
     __syncthreads();
-    if (hang_mask) {
-      const uint32_t hm = hang_mask[cell];
-      for (int e = 0; e < 3; ++e) hang_resolve3<n, false>(hm, hang_I, X + e * n3, t1, i, j, k);
-      hang_resolve3<n, false>(hm, hang_I, v, t1, i, j, k);
-    }
-    double J[3][3], K[3][3], xq[3];
-    cell_jacobian<n>(tab_gauss, X, t1, t2, i, j, k, J, xq);
-    const double det = invert3(J, K);
+    if (hang_mask) hang_resolve3<n, false>(hang_mask[cell], hang_I, v, t1, i, j, k);
     const double *w = tab_gauss + 2 * n2;
     const double *N = tab_gauss;
     const double uq = Cell3<n>::template tensor3<false>(N, N, N, v, t1, t2, i, j, k);
-    acc += uq * uq * fabs(det) * w[i] * w[j] * w[k];
+    acc += uq * uq * fabs(det) * w[i] * w[j] * w[k]; // (not uq * uq * jxw: the product is rounded in the order it always was)
     __syncthreads();
   }
   t1[q] = acc;

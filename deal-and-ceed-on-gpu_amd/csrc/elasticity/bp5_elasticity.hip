@@ -14,20 +14,15 @@ int launch_elasticity_t(bp5_mf *mf, const double *coef, double lambda, double mu
   constexpr int n = P + 1, TW = DP::TW, LPC = DP::LPC, TPB = DP::TPB;
   constexpr int CPT = 64 * TW / LPC;
   using L = LdsLayout<n, LPC>;
-  ApplyArgs a{};
-  a.l2g = mf->d_l2g; a.coef = coef; a.src = src; a.dst = dst;
+  ApplyArgs a = apply_args(mf, false, coef, src, dst);
   a.plane_stride = (uint64_t)mf->n_cells * mf->n3; a.cell_stride = (uint64_t)mf->n3; // ten planes, plane-major
-  a.n_cells_total = mf->n_cells;
-  a.cell_begin = c0; a.cell_end = c1;
-  a.n_teams = (c1 - c0 + CPT - 1) / CPT;
-  const uint32_t nblk = (a.n_teams + TPB - 1) / TPB;
-  a.teams_per_xcd = (nblk + 7) / 8;
+  const PencilLaunch pl = pencil_launch<CPT, TW, TPB>(a, c0, c1);
   ElasticityArgs ea{lambda, mu, (uint64_t)ld};
   ShapeArg<n> sh;
   fill_shape(sh, mf);
   const size_t lds = (size_t)TPB * CPT * L::CS * sizeof(double);
   snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "apply_pencil_elasticity_kernel<%d,%s,%d,%d,%d>", P, COLL ? "true" : "false", TW, LPC, TPB);
-  hipLaunchKernelGGL((apply_pencil_elasticity_kernel<P, COLL, TW, LPC, TPB>), dim3(a.teams_per_xcd * 8), dim3(64 * TW * TPB), lds, mf->stream, a, ea, sh);
+  hipLaunchKernelGGL((apply_pencil_elasticity_kernel<P, COLL, TW, LPC, TPB>), pl.grid, pl.block, lds, mf->stream, a, ea, sh);
   KERNEL_CHECK();
   return BP5_OK;
 }
@@ -41,7 +36,7 @@ int launch_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, 
 template <int n>
 int launch_metric(bp5_mf *mf, double *coef)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65535u * 16);
+  const uint32_t grid = cell_grid(mf, 65535u * 16);
   hipLaunchKernelGGL(elasticity_metric_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, mf->d_coords, mf->d_tab, mf->coefficient, mf->n_cells, coef,
                      (uint64_t)mf->n_cells * mf->n3);
   KERNEL_CHECK();
@@ -51,50 +46,29 @@ int launch_metric(bp5_mf *mf, double *coef)
 template <int n>
 int launch_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag)
 {
-  const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(mf->n_cells, 1), 65536u);
+  const uint32_t grid = cell_grid(mf, 65536u);
   hipLaunchKernelGGL(elasticity_diagonal_kernel<n>, dim3(grid), dim3(n, n, n), 0, mf->stream, mf->d_l2g, coef, (uint64_t)mf->n_cells * mf->n3, mf->d_tab, mf->n_cells,
                      lambda, mu, (uint64_t)ld, diag);
   KERNEL_CHECK();
   return BP5_OK;
 }
 
-#define ELASTICITY_DISPATCH_N(fn, ...)                                                                             \
-  switch (mf->n) {                                                                                                 \
-    case 2: return fn<2>(__VA_ARGS__);                                                                             \
-    case 3: return fn<3>(__VA_ARGS__);                                                                             \
-    case 4: return fn<4>(__VA_ARGS__);                                                                             \
-    case 5: return fn<5>(__VA_ARGS__);                                                                             \
-    case 6: return fn<6>(__VA_ARGS__);                                                                             \
-    case 7: return fn<7>(__VA_ARGS__);                                                                             \
-    case 8: return fn<8>(__VA_ARGS__);                                                                             \
-    case 9: return fn<9>(__VA_ARGS__);                                                                             \
-  }                                                                                                                \
-  return fail(BP5_ERR_INVALID, "elasticity: unsupported degree")
+const char *const UNSUPPORTED_DEGREE = "elasticity: unsupported degree";
 
 } // namespace
 
 int elasticity_compute_metric(bp5_mf *mf, double *coef)
 {
   if (!mf->n_cells) return BP5_OK;
-  ELASTICITY_DISPATCH_N(launch_metric, mf, coef);
+  return for_degree(mf->degree, [&](auto P) { return launch_metric<P() + 1>(mf, coef); }, UNSUPPORTED_DEGREE);
 }
 int elasticity_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag)
 {
   if (!mf->n_cells) return BP5_OK;
-  ELASTICITY_DISPATCH_N(launch_diagonal, mf, coef, lambda, mu, ld, diag);
+  return for_degree(mf->degree, [&](auto P) { return launch_diagonal<P() + 1>(mf, coef, lambda, mu, ld, diag); }, UNSUPPORTED_DEGREE);
 }
 int elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1)
 {
   if (c1 <= c0) return BP5_OK;
-  switch (mf->degree) {
-    case 1: return launch_elasticity<1>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 2: return launch_elasticity<2>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 3: return launch_elasticity<3>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 4: return launch_elasticity<4>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 5: return launch_elasticity<5>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 6: return launch_elasticity<6>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 7: return launch_elasticity<7>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-    case 8: return launch_elasticity<8>(mf, coef, lambda, mu, ld, src, dst, c0, c1);
-  }
-  return fail(BP5_ERR_INVALID, "elasticity: unsupported degree");
+  return for_degree(mf->degree, [&](auto P) { return launch_elasticity<P()>(mf, coef, lambda, mu, ld, src, dst, c0, c1); }, UNSUPPORTED_DEGREE);
 }
