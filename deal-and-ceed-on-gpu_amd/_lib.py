@@ -199,6 +199,11 @@ def lib():
         "bp5_elasticity_apply_cells": (i32, [vp, vp, f64, f64, sz, vp, vp, u32, u32]),
         "bp5_elasticity_compute_diagonal": (i32, [vp, vp, f64, f64, sz, vp, i32]),
         "bp5_cg_solve_elasticity": (i32, [vp, vp, f64, f64, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_cg_solve_elasticity_preconditioned": (i32, [vp, vp, f64, f64, sz, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_elasticity_chebyshev_create": (i32, [vp, vp, f64, f64, sz, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),
+        "bp5_elasticity_mg_create": (i32, [i32, vp, vp, f64, f64, sz, vp, C.POINTER(MGParams), C.POINTER(vp)]),
+        "bp5_mg_transfer_prolongate_add_components": (i32, [vp, i32, sz, vp, sz, vp]),
+        "bp5_mg_transfer_restrict_add_components": (i32, [vp, i32, sz, vp, sz, vp]),
         "bp5_cg_solve_operator": (i32, [vp, VMULT_FN, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_preconditioned": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_chebyshev_create": (i32, [vp, vp, vp, vp, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),

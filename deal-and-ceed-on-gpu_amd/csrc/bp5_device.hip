@@ -186,7 +186,7 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   hipStreamSynchronize(mf->stream);
   void *ptrs[] = {mf->d_constrained_bits, mf->d_l2g, mf->d_constrained, mf->d_send_idx, mf->d_coords, mf->d_tab, mf->d_tab_gauss, mf->d_l2g_padded,
                   mf->d_constraint_mask, mf->d_inv_jac, mf->d_JxW, mf->d_qpoints, mf->d_sendbuf, mf->d_recvbuf, mf->d_partials,
-                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->hc_base, mf->d_hc_off};
+                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->wsz_base, mf->hc_base, mf->d_hc_off};
   for (void *p : ptrs) if (p) hipFree(p);
   if (mf->h_sc) hipHostFree(mf->h_sc);
   if (mf->h_st) hipHostFree(mf->h_st);
@@ -1330,6 +1330,18 @@ static int elasticity_check(const bp5_mf *mf, const double *coef, double lambda,
   if (ld < mf->n_local()) return elasticity_refuse(BP5_ERR_INVALID, "ld < n_owned + n_ghost");
   const size_t extent = 2 * ld + mf->n_local();
   if (distinct && v < w + extent && w < v + extent) return elasticity_refuse(BP5_ERR_INVALID, "src and dst overlap");
+  return elasticity_handle_check(mf);
+}
+// ... of a call that brings no vector of its own (bp5_elasticity_chebyshev_create with inv_diag == NULL): the metric array, the stride, the
+// parameters, the handle -- in elasticity_check's order
+static int elasticity_check_no_vector(const bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld)
+{
+  if (!coef) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  if (ld & 1) return elasticity_refuse(BP5_ERR_INVALID, "ld must be even (every block 16-byte aligned)");
+  if (!aligned16(coef)) return elasticity_refuse(BP5_ERR_INVALID, "the metric array must be 16-byte aligned");
+  BP5_TRY(elasticity_parameter_check(lambda, mu));
+  if (!mf) return elasticity_refuse(BP5_ERR_INVALID, "null handle");
+  if (ld < mf->n_local()) return elasticity_refuse(BP5_ERR_INVALID, "ld < n_owned + n_ghost");
   return elasticity_handle_check(mf);
 }
 extern "C" int bp5_elasticity_coef_size(const bp5_mf *mf, size_t *n_doubles)
@@ -2562,7 +2574,8 @@ struct PlainCG {
   int n_components = 1;
   size_t ld = 0;
   double *g = nullptr, *d = nullptr, *h = nullptr;
-  // operator: the library's (coef) or the caller's callback (scalar vectors); block: the block-vector application, with the halo exchange or without
+  // operator: the library's (coef) or the caller's callback (an operator callback: scalar vectors only); block: the block-vector application, with
+  // the halo exchange or without
   const double *coef = nullptr;
   bp5_vmult_fn user = nullptr;
   void *user_ctx = nullptr;
@@ -2570,8 +2583,10 @@ struct PlainCG {
   // elasticity: the block operator is the coupled three-component one (coef: its ten planes; lambda, mu by value)
   bool elasticity = false;
   double lambda = 0.0, mu = 0.0;
-  // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g (scalar vectors).  diag_ld: doubles between the diagonals
-  // of two components -- 0: ONE scalar diagonal applied to every block; ld: a block inverse diagonal
+  // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g -- on scalar vectors (bp5_cg_solve_preconditioned) or on
+  // block vectors of the solve's n_components and ld (bp5_cg_solve_elasticity_preconditioned); z is laid out like g (scalar: ws_z; block:
+  // wsz_base, block_cg_workspace_z).  diag_ld: doubles between the diagonals of two components -- 0: ONE scalar diagonal applied to every block;
+  // ld: a block inverse diagonal
   const double *diag = nullptr;
   size_t diag_ld = 0;
   bp5_vmult_fn precond = nullptr;
@@ -2632,7 +2647,8 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
     KERNEL_CHECK();
     BP5_TRY(apply_P());
-    hipLaunchKernelGGL(dot_kernel, grid2, block, 0, s, g, z, n, mf->d_partials);
+    if (cg.block) BP5_TRY(blockvec_dot(s, grid2, g, z, n, ld, mf->d_partials)); // g.z over the owned entries of all blocks
+    else hipLaunchKernelGGL(dot_kernel, grid2, block, 0, s, g, z, n, mf->d_partials);
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, no_flag);
   } else {
     hipLaunchKernelGGL(cg_init_kernel<true>, grid1, block, 0, s, b, diag, x, g, d, n, ld, mf->d_partials, dld);
@@ -2905,6 +2921,19 @@ static int block_cg_workspace(bp5_mf *mf, int n_components, size_t ld, PlainCG &
   cg.g = mf->wsc_base; cg.d = cg.g + block; cg.h = cg.d + block;
   return BP5_OK;
 }
+// ... and z = P g of a solve with a callback preconditioner: a vector of its own, grown on demand, zero-filled (the padding of z is the callback's)
+static int block_cg_workspace_z(bp5_mf *mf, int n_components, size_t ld, PlainCG &cg)
+{
+  const size_t need = (size_t)n_components * ld;
+  if (mf->wsz_cap < need) {
+    if (mf->wsz_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsz_base)); mf->wsz_base = nullptr; mf->wsz_cap = 0; }
+    HIP_TRY(hipMalloc((void **)&mf->wsz_base, need * sizeof(double)));
+    mf->wsz_cap = need;
+  }
+  HIP_TRY(hipMemsetAsync(mf->wsz_base, 0, need * sizeof(double), mf->stream));
+  cg.z = mf->wsz_base;
+  return BP5_OK;
+}
 // cg.solve(A, x, b, DiagonalMatrix) on a block vector: the plain recurrence on the stacked system, one launch per BLAS-1 step
 // with_exchange (bp5_cg_solve_components_distributed): a handle with a communicator and neighbours is taken, every operator application carries
 // the halo exchange (components_apply_exchanged) and d.h, g.g and g.z are all-reduced where the scalar plain solver all-reduces them
@@ -2938,8 +2967,11 @@ extern "C" int bp5_cg_solve_components_distributed(bp5_mf *mf, const double *coe
 
 // cg.solve(A, x, b, DiagonalMatrix) for the elasticity operator: the plain recurrence on the stacked three-component system, the operator step the
 // coupled application and the preconditioner a BLOCK inverse diagonal (three blocks ld apart, as bp5_elasticity_compute_diagonal returns them)
-extern "C" int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, const double *b, double *x,
-                                       const bp5_cg_params *prm, bp5_cg_result *res)
+// precond != NULL (bp5_cg_solve_elasticity_preconditioned): z = P g from the callback in place of the diagonal; history != NULL: the Lanczos
+// coefficients of the solve (PlainCG::history: the estimate of bp5_elasticity_chebyshev_create)
+static int cg_solve_elasticity_impl(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, bp5_vmult_fn precond,
+                                    void *precond_ctx, const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr,
+                                    int history_cap = 0)
 {
   if (!prm || !res) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
   if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return elasticity_refuse(BP5_ERR_INVALID, "unknown CG variant");
@@ -2957,7 +2989,25 @@ extern "C" int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double la
   cg.coef = coef; cg.block = true; cg.elasticity = true; cg.lambda = lambda; cg.mu = mu;
   cg.diag = inv_diag; cg.diag_ld = ld;
   cg.allreduce = false;
+  if (precond) {
+    BP5_TRY(block_cg_workspace_z(mf, 3, ld, cg));
+    cg.precond = precond; cg.precond_ctx = precond_ctx;
+  }
+  cg.history = history; cg.history_cap = history_cap;
   return cg_solve_plain(mf, cg, b, x, prm, res);
+}
+extern "C" int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, const double *b, double *x,
+                                       const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  return cg_solve_elasticity_impl(mf, coef, lambda, mu, ld, inv_diag, nullptr, nullptr, b, x, prm, res);
+}
+// cg.solve(A, x, b, P) for the elasticity operator and a P given by its vmult on three-block vectors of the same ld: the plain recurrence with
+// z = P g in place of D g (cg_solve_plain's callback path on block vectors)
+extern "C" int bp5_cg_solve_elasticity_preconditioned(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                                                      const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  if (!precond) return elasticity_refuse(BP5_ERR_INVALID, "null argument (the preconditioner's vmult callback)");
+  return cg_solve_elasticity_impl(mf, coef, lambda, mu, ld, nullptr, precond, precond_ctx, b, x, prm, res);
 }
 
 // cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of D g
@@ -2993,11 +3043,17 @@ struct bp5_chebyshev {
   int cg_its = 0;
   std::vector<double> f1, f2; // step k = 1 .. degree-1
   double *w = nullptr, *t = nullptr; // the other iterate and t = A x_k: owned + ghost each (one allocation)
+  // bp5_elasticity_chebyshev_create: the operator is the coupled elasticity one (coef: its ten planes) and every vector three blocks ld apart --
+  // w and t too; inv_diag is then a BLOCK inverse diagonal (blocks ld apart)
+  bool elasticity = false;
+  double lambda = 0.0, mu = 0.0;
+  size_t ld = 0;
 };
 
 // t = A x in overwrite mode (zero_dst = 1 and the Dirichlet copy); the distributed apply when there are neighbours
 static int cheb_apply(bp5_chebyshev *c, double *x, double *t)
 {
+  if (c->elasticity) return bp5_elasticity_apply(c->mf, c->coef, c->lambda, c->mu, c->ld, x, t, 1);
   if (c->vmult) {
     const int st = c->vmult(c->ctx, t, x);
     return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
@@ -3017,6 +3073,8 @@ static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, co
   const dim3 grid(stream_grid_flat(mf, n, 2)), block(VB);
   const bool nt = mf->tune[BP5_TUNE_UPDATE_NT] != 0;
   const double *dg = c->inv_diag, *t = c->t;
+  if (c->elasticity) // the three blocks in one launch (chebyshev_step_components_kernel), the same streaming policy and flat launch shape
+    return blockvec_chebyshev_step(mf->stream, FORM, grid.x, 3, nt, x_new, x, x_old, src, t, dg, n, c->ld, c->ld, f1, f2);
   if (dg) {
     if (nt) hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, true>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
     else hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, false>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
@@ -3028,8 +3086,10 @@ static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, co
   return BP5_OK;
 }
 
-extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag,
-                                    const bp5_chebyshev_params *prm, bp5_chebyshev **out)
+// el_ld != 0 (bp5_elasticity_chebyshev_create, which has checked handle, layout and parameters): the elasticity operator on three-block vectors
+// el_ld apart, inv_diag a block inverse diagonal
+static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag, const bp5_chebyshev_params *prm,
+                                 bp5_chebyshev **out, size_t el_ld = 0, double lambda = 0.0, double mu = 0.0)
 {
   if (!mf || !prm || !out || (!vmult && !coef && mf->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "null argument");
   *out = nullptr;
@@ -3041,7 +3101,8 @@ extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn
   HIP_TRY(hipSetDevice(mf->device));
   std::unique_ptr<bp5_chebyshev> c(new bp5_chebyshev);
   c->mf = mf; c->coef = coef; c->vmult = vmult; c->ctx = ctx; c->inv_diag = inv_diag; c->degree = prm->degree;
-  const size_t nb = (std::max<size_t>(mf->n_local(), 2) * sizeof(double) + 4095) / 4096 * 4096;
+  c->elasticity = el_ld != 0; c->ld = el_ld; c->lambda = lambda; c->mu = mu;
+  const size_t nb = (std::max<size_t>(el_ld ? 3 * el_ld : mf->n_local(), 2) * sizeof(double) + 4095) / 4096 * 4096;
   char *base = nullptr;
   HIP_TRY(hipMalloc((void **)&base, 2 * nb));
   c->w = (double *)base;
@@ -3054,23 +3115,32 @@ extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn
   } else {
     // Jacobi-PCG on A x = v (x_0 = 0) with the alpha / beta history on the device; one copy to the host at the end
     const int m = prm->eig_cg_n_iterations;
-    std::vector<double> v(std::max<size_t>(mf->n_owned, 1), 0.0);
-    for (uint32_t i = 0; i < mf->n_owned; ++i) {
-      const uint64_t id = prm->start_ids_host ? prm->start_ids_host[i] : i;
-      v[i] = (double)(int)(id % 11u) - 5.0;
-    }
+    const int n_blocks = el_ld ? 3 : 1;
+    std::vector<double> v(std::max<size_t>(mf->n_owned, 1) * n_blocks, 0.0);
+    for (int cb = 0; cb < n_blocks; ++cb)
+      for (uint32_t i = 0; i < mf->n_owned; ++i) {
+        const uint64_t id = prm->start_ids_host ? prm->start_ids_host[i] : i;
+        // block vectors: v_c[i] = ((3 id + c) mod 11) - 5, the scalar start vector of the stacked numbering 3 id + c
+        v[(size_t)cb * mf->n_owned + i] = (double)(int)((el_ld ? 3u * (id % 11u) + (unsigned)cb : id) % 11u) - 5.0;
+      }
     double *vb = c->w, *xs = c->t, *hist = nullptr;
-    HIP_TRY(hipMemcpyAsync(vb, v.data(), mf->n_owned * sizeof(double), hipMemcpyHostToDevice, mf->stream));
-    BP5_TRY(bp5_set_constrained(mf, 0.0, vb));
     double vnorm = 0.0;
-    BP5_TRY(bp5_vec_l2_norm(mf, vb, mf->n_owned, &vnorm));
+    for (int cb = 0; cb < n_blocks; ++cb) {
+      double *vbc = vb + (size_t)cb * el_ld;
+      HIP_TRY(hipMemcpyAsync(vbc, v.data() + (size_t)cb * mf->n_owned, mf->n_owned * sizeof(double), hipMemcpyHostToDevice, mf->stream));
+      BP5_TRY(bp5_set_constrained(mf, 0.0, vbc));
+      double nb_ = 0.0;
+      BP5_TRY(bp5_vec_l2_norm(mf, vbc, mf->n_owned, &nb_));
+      vnorm = n_blocks == 1 ? nb_ : std::sqrt(vnorm * vnorm + nb_ * nb_); // (the stacked norm; one block: the value as it is)
+    }
     HIP_TRY(hipMalloc((void **)&hist, 2 * (size_t)m * sizeof(double)));
     struct FreeHist { double *h; ~FreeHist() { hipFree(h); } } hguard{hist};
     HIP_TRY(hipMemsetAsync(hist, 0, 2 * (size_t)m * sizeof(double), mf->stream));
     bp5_cg_params cp{};
     cp.variant = BP5_CG_PLAIN; cp.max_iter = m; cp.abs_tol = 1e-5 * vnorm; cp.check_every = 0; cp.profile = 0;
     bp5_cg_result cr{};
-    BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr, hist, m));
+    if (el_ld) BP5_TRY(cg_solve_elasticity_impl(mf, coef, lambda, mu, el_ld, inv_diag, nullptr, nullptr, vb, xs, &cp, &cr, hist, m));
+    else BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr, hist, m));
     std::vector<double> h(2 * (size_t)m);
     HIP_TRY(hipMemcpy(h.data(), hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int k = cr.iterations;
@@ -3101,6 +3171,23 @@ extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn
   guard.keep = true;
   *out = c.release();
   return BP5_OK;
+}
+extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag,
+                                    const bp5_chebyshev_params *prm, bp5_chebyshev **out)
+{
+  return chebyshev_create_impl(mf, coef, vmult, ctx, inv_diag, prm, out);
+}
+// PreconditionChebyshev for the elasticity operator: the same handle type, every vector three blocks ld apart, the estimate Jacobi-PCG on the
+// stacked system (one Krylov space) with the block inverse diagonal
+extern "C" int bp5_elasticity_chebyshev_create(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag,
+                                               const bp5_chebyshev_params *prm, bp5_chebyshev **out)
+{
+  if (!prm || !out) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (inv_diag && !aligned16(inv_diag)) return elasticity_refuse(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  if (inv_diag) BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, inv_diag, nullptr, false));
+  else BP5_TRY(elasticity_check_no_vector(mf, coef, lambda, mu, ld));
+  return chebyshev_create_impl(mf, coef, nullptr, nullptr, inv_diag, prm, out, ld, lambda, mu);
 }
 
 extern "C" int bp5_chebyshev_eigenvalues(const bp5_chebyshev *c, double *min_est, double *max_est, double *min_used, double *max_used, int *cg_its)
@@ -3143,7 +3230,8 @@ extern "C" int bp5_chebyshev_step(bp5_chebyshev *c, double *dst, double *src)
   bp5_mf *mf = c->mf;
   double *a = dst, *b = c->w; // a: x_0, x_2, ...   b: x_1, x_3, ...
   if (c->degree & 1) {
-    HIP_TRY(hipMemcpyAsync(c->w, dst, mf->n_owned * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
+    for (int cb = 0; cb < (c->elasticity ? 3 : 1); ++cb) // (block by block: the padding of dst is not read)
+      HIP_TRY(hipMemcpyAsync(c->w + (size_t)cb * c->ld, dst + (size_t)cb * c->ld, mf->n_owned * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
     a = c->w; b = dst;
   }
   BP5_TRY(cheb_apply(c, a, c->t));
@@ -3175,7 +3263,12 @@ struct bp5_mg_transfer {
   uint32_t *d_cidx = nullptr, *d_wmask = nullptr;             // coarse indices per cell (MG_NO_DOF: Dirichlet; geometric: per COARSE cell), writer masks per fine cell
   uint32_t *d_coff = nullptr, *d_cslot = nullptr;             // per coarse local DoF: its slots, ascending
   uint32_t *d_pcode = nullptr;                                 // geometric: per fine cell parent << 3 | child
-  std::vector<void *> device_arrays() const { return {d_M, d_w, d_slots, d_cidx, d_wmask, d_coff, d_cslot, d_pcode}; }
+  // block vectors (bp5_mg_transfer_*_components): slots [component][cell][(pc+1)^3] for slots_components > 1 components, an array of its own that
+  // bp5_elasticity_mg_create reserves at setup (the entry points grow it when a call brings more components than any before)
+  double *d_slots_c = nullptr;
+  int slots_components = 0;
+  size_t slot_stride() const { return (size_t)fine->n_cells * coarse->n3; }
+  std::vector<void *> device_arrays() const { return {d_M, d_w, d_slots, d_cidx, d_wmask, d_coff, d_cslot, d_pcode, d_slots_c}; }
 };
 
 // the instantiated degree pairs (pf -> max(1, pf / 2))
@@ -3501,6 +3594,65 @@ extern "C" int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst, dou
   return mg_restrict(t, dst, src, nullptr, true);
 }
 
+// ---- the same transfers on block vectors (blockvec/bp5_blockvec.hip): the lists are per scalar DoF and shared by all components
+static MgComponentsArgs mg_components_args(const bp5_mg_transfer *t)
+{
+  MgComponentsArgs a;
+  a.pf = t->pf; a.geometric = t->geometric;
+  a.M = t->d_M; a.w = t->d_w; a.cidx = t->d_cidx; a.pcode = t->d_pcode; a.fidx = t->fine->d_l2g; a.wmask = t->d_wmask; a.coff = t->d_coff; a.cslot = t->d_cslot;
+  a.n_cells = t->fine->n_cells; a.stream = t->fine->stream;
+  return a;
+}
+// slots for n_components blocks: one component uses the scalar array
+static int mg_reserve_slots(bp5_mg_transfer *t, int n_components, double **slots)
+{
+  if (n_components == 1) { *slots = t->d_slots; return BP5_OK; }
+  if (t->slots_components < n_components) {
+    HIP_TRY(hipSetDevice(t->fine->device));
+    if (t->d_slots_c) { HIP_TRY(hipStreamSynchronize(t->fine->stream)); HIP_TRY(hipFree(t->d_slots_c)); t->d_slots_c = nullptr; t->slots_components = 0; }
+    HIP_TRY(hipMalloc((void **)&t->d_slots_c, std::max<size_t>((size_t)n_components * t->slot_stride(), 1) * sizeof(double)));
+    t->slots_components = n_components;
+  }
+  *slots = t->d_slots_c;
+  return BP5_OK;
+}
+static int mg_components_check(const bp5_mg_transfer *t, int n_components, size_t ld_f, const double *vf, size_t ld_c, const double *vc)
+{
+  if (!t) return fail(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(components_layout_check(n_components, ld_f, vf, vc));
+  if (ld_c & 1) return fail(BP5_ERR_INVALID, "block vectors: ld must be even (every block 16-byte aligned)");
+  if (ld_f < t->fine->n_local() || ld_c < t->coarse->n_local()) return fail(BP5_ERR_INVALID, "block vectors: ld < n_owned + n_ghost");
+  if (t->fine->has_neighbors() || t->coarse->has_neighbors())
+    return fail(BP5_ERR_UNSUPPORTED, "multigrid transfer on block vectors: no halo exchange (handles with a communicator and neighbours)");
+  return BP5_OK;
+}
+// dst_f += P src_c on validated arguments
+static int mg_prolongate_components(bp5_mg_transfer *t, int n_components, size_t ld_f, double *dst, size_t ld_c, const double *src)
+{
+  return blockvec_mg_prolongate(mg_components_args(t), n_components, ld_c, src, ld_f, dst);
+}
+// dst_c (+)= P^T (w (.) (b - tv)) on validated arguments, tv == NULL: P^T (w (.) b)
+static int mg_restrict_components(bp5_mg_transfer *t, int n_components, size_t ld_c, double *dst, size_t ld_f, const double *b, const double *tv, bool add)
+{
+  double *slots = nullptr;
+  BP5_TRY(mg_reserve_slots(t, n_components, &slots));
+  const MgComponentsArgs a = mg_components_args(t);
+  BP5_TRY(blockvec_mg_restrict(a, n_components, ld_f, b, tv, t->slot_stride(), slots));
+  return blockvec_mg_combine(a, n_components, slots, t->slot_stride(), t->coarse->n_owned, (uint32_t)t->coarse->n_local(), ld_c, dst, add);
+}
+extern "C" int bp5_mg_transfer_prolongate_add_components(bp5_mg_transfer *t, int n_components, size_t ld_fine, double *dst_fine, size_t ld_coarse, double *src_coarse)
+{
+  BP5_TRY(mg_components_check(t, n_components, ld_fine, dst_fine, ld_coarse, src_coarse));
+  HIP_TRY(hipSetDevice(t->fine->device));
+  return mg_prolongate_components(t, n_components, ld_fine, dst_fine, ld_coarse, src_coarse);
+}
+extern "C" int bp5_mg_transfer_restrict_add_components(bp5_mg_transfer *t, int n_components, size_t ld_coarse, double *dst_coarse, size_t ld_fine, double *src_fine)
+{
+  BP5_TRY(mg_components_check(t, n_components, ld_fine, src_fine, ld_coarse, dst_coarse));
+  HIP_TRY(hipSetDevice(t->fine->device));
+  return mg_restrict_components(t, n_components, ld_coarse, dst_coarse, ld_fine, src_fine, nullptr, true);
+}
+
 extern "C" int bp5_mg_transfer_destroy(bp5_mg_transfer *t)
 {
   if (!t) return BP5_OK;
@@ -3521,6 +3673,11 @@ struct bp5_mg {
   std::vector<bp5_chebyshev *> cheb;          // [l]: the smoother; [n_levels - 1]: the coarse solver
   std::vector<double *> inv_diag, x, b, t;    // per level; x, b of levels >= 1 (level 0: the caller's dst, src); t of levels < n_levels - 1
   std::vector<void *> allocs;
+  // bp5_elasticity_mg_create: every level's operator is the elasticity one with (lambda, mu), coef its ten planes, every vector three blocks
+  // ld[l] apart (ld[0]: the caller's; below: the level's n_local rounded up to even)
+  bool elasticity = false;
+  double lambda = 0.0, mu = 0.0;
+  std::vector<size_t> ld;
 };
 
 extern "C" void bp5_mg_params_default(bp5_mg_params *p)
@@ -3600,8 +3757,95 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   return BP5_OK;
 }
 
+// The elasticity V-cycle (bp5_elasticity_mg_create): exactly mg_level's steps, on three-block vectors
+static int elasticity_mg_create_check(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
+                                      bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
+{
+  if (n_levels < 1 || !mfs || !coefs || !prm || !out || (n_levels > 1 && !transfers)) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: null argument or n_levels < 1");
+  *out = nullptr;
+  if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
+  if (ld & 1) return elasticity_refuse(BP5_ERR_INVALID, "ld must be even (every block 16-byte aligned)");
+  BP5_TRY(elasticity_parameter_check(lambda, mu));
+  for (int l = 0; l < n_levels; ++l) {
+    if (!mfs[l] || !coefs[l]) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: null level handle or metric");
+    if (!aligned16(coefs[l])) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: the metric arrays must be 16-byte aligned");
+  }
+  if (ld < mfs[0]->n_local()) return elasticity_refuse(BP5_ERR_INVALID, "ld < n_owned + n_ghost");
+  for (int l = 0; l < n_levels; ++l) {
+    BP5_TRY(elasticity_handle_check(mfs[l]));
+    if (mfs[l]->stream != mfs[0]->stream || mfs[l]->device != mfs[0]->device) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
+    // the coarse polynomial is no solver for a singular level (the rigid-body modes), and a smoother's estimate has no meaning on one
+    if (!mfs[l]->n_constrained) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "multigrid: a level without Dirichlet DoFs is singular (rigid-body modes)");
+  }
+  for (int l = 0; l + 1 < n_levels; ++l)
+    if (!transfers[l] || transfers[l]->fine != mfs[l] || transfers[l]->coarse != mfs[l + 1])
+      return elasticity_refuse(BP5_ERR_INVALID, "multigrid: transfers[l] must connect mfs[l] (fine) and mfs[l + 1] (coarse)");
+  return BP5_OK;
+}
+extern "C" int bp5_elasticity_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
+                                        bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
+{
+  BP5_TRY(elasticity_mg_create_check(n_levels, mfs, coefs, lambda, mu, ld, transfers, prm, out));
+  HIP_TRY(hipSetDevice(mfs[0]->device));
+  std::unique_ptr<bp5_mg, int (*)(bp5_mg *)> mg(new bp5_mg, bp5_mg_destroy);
+  mg->n_levels = n_levels;
+  mg->elasticity = true; mg->lambda = lambda; mg->mu = mu;
+  mg->mf.assign(mfs, mfs + n_levels);
+  mg->coef.assign(coefs, coefs + n_levels);
+  mg->tr.assign(transfers, transfers + (n_levels - 1));
+  mg->inv_diag.assign(n_levels, nullptr);
+  mg->x.assign(n_levels, nullptr);
+  mg->b.assign(n_levels, nullptr);
+  mg->t.assign(n_levels, nullptr);
+  mg->ld.assign(n_levels, 0);
+  auto alloc = [&](double **p, size_t n) -> int {
+    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 2) * sizeof(double)));
+    mg->allocs.push_back(*p);
+    HIP_TRY(hipMemsetAsync(*p, 0, std::max<size_t>(n, 2) * sizeof(double), mfs[0]->stream));
+    return BP5_OK;
+  };
+  for (int l = 0; l < n_levels; ++l) {
+    bp5_mf *m = mfs[l];
+    const size_t ldl = l == 0 ? ld : std::max<size_t>((m->n_local() + 1) & ~(size_t)1, 2);
+    mg->ld[l] = ldl;
+    BP5_TRY(alloc(&mg->inv_diag[l], 3 * ldl));
+    if (l > 0) { BP5_TRY(alloc(&mg->x[l], 3 * ldl)); BP5_TRY(alloc(&mg->b[l], 3 * ldl)); }
+    if (l + 1 < n_levels) {
+      BP5_TRY(alloc(&mg->t[l], 3 * ldl));
+      double *slots = nullptr;
+      BP5_TRY(mg_reserve_slots(mg->tr[l], 3, &slots)); // at setup: nothing allocates inside vmult
+    }
+    BP5_TRY(bp5_elasticity_compute_diagonal(m, coefs[l], lambda, mu, ldl, mg->inv_diag[l], 1));
+    const bool coarsest = l + 1 == n_levels;
+    bp5_chebyshev_params cp{};
+    cp.degree = coarsest ? prm->coarse_degree : prm->smoother_degree;
+    cp.smoothing_range = coarsest ? prm->coarse_range : prm->smoothing_range;
+    cp.eig_cg_n_iterations = coarsest ? prm->coarse_eig_cg_n_iterations : prm->eig_cg_n_iterations;
+    cp.start_ids_host = prm->start_ids_host ? prm->start_ids_host[l] : nullptr;
+    bp5_chebyshev *c = nullptr;
+    BP5_TRY(bp5_elasticity_chebyshev_create(m, coefs[l], lambda, mu, ldl, mg->inv_diag[l], &cp, &c));
+    mg->cheb.push_back(c);
+  }
+  HIP_TRY(hipStreamSynchronize(mfs[0]->stream));
+  *out = mg.release();
+  return BP5_OK;
+}
+static int mg_level_elasticity(bp5_mg *mg, int l, double *x, double *b)
+{
+  if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
+  bp5_mf *mf = mg->mf[l];
+  const size_t ld = mg->ld[l], ldc = mg->ld[l + 1];
+  BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                                                   // pre-smoothing from zero
+  BP5_TRY(bp5_elasticity_apply(mf, mg->coef[l], mg->lambda, mg->mu, ld, x, mg->t[l], 1));             // t = A x
+  BP5_TRY(mg_restrict_components(mg->tr[l], 3, ldc, mg->b[l + 1], ld, b, mg->t[l], false));          // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
+  BP5_TRY(mg_level_elasticity(mg, l + 1, mg->x[l + 1], mg->b[l + 1]));
+  BP5_TRY(mg_prolongate_components(mg->tr[l], 3, ld, x, ldc, mg->x[l + 1]));                          // x += P x_c
+  return bp5_chebyshev_step(mg->cheb[l], x, b);                                                      // post-smoothing
+}
+
 static int mg_level(bp5_mg *mg, int l, double *x, double *b)
 {
+  if (mg->elasticity) return mg_level_elasticity(mg, l, x, b);
   if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
   bp5_mf *mf = mg->mf[l];
   BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                      // pre-smoothing from zero

@@ -119,6 +119,8 @@ struct bp5_mf {
   double *ws_z = nullptr;     // preconditioner output of bp5_cg_solve_preconditioned (allocated on first use)
   double *wsc_base = nullptr; // bp5_cg_solve_components: g, d, h as block vectors (3 n_components ld doubles), grown on demand
   size_t wsc_cap = 0;         // ... doubles allocated
+  double *wsz_base = nullptr; // bp5_cg_solve_elasticity_preconditioned: z = P g as a block vector (n_components ld doubles), grown on demand
+  size_t wsz_cap = 0;
   // halo exchange of block vectors: four staging buffers in one allocation, grown on demand -- gather send / scatter receive (n_components
   // send_off.back() doubles each), gather receive / scatter send (n_components n_ghost each); a neighbour's message is contiguous and holds
   // all components, [neighbour][component][entry].  d_hc_off: send_off, then recv_off, for the kernels that place an entry in its message
@@ -340,6 +342,26 @@ inline int overint_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED, s
 int elasticity_compute_metric(bp5_mf *mf, double *coef);
 int elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1);
 int elasticity_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag);
+
+// Block-vector forms of the pointwise and transfer kernels (the elasticity preconditioners), defined in blockvec/bp5_blockvec.hip -- a translation
+// unit of its own.  n_components blocks ld apart; the callers have validated handles and layouts.
+struct MgComponentsArgs { // the device tables of one transfer (bp5_mg_transfer), by value
+  int pf = 0;
+  bool geometric = false;
+  const double *M = nullptr, *w = nullptr;
+  const uint32_t *cidx = nullptr, *pcode = nullptr, *fidx = nullptr, *wmask = nullptr, *coff = nullptr, *cslot = nullptr;
+  uint32_t n_cells = 0;
+  hipStream_t stream = nullptr;
+};
+// partial sums of x.y, component = grid.y, in the columns cg_dh_kernel uses
+int blockvec_dot(hipStream_t s, dim3 grid, const double *x, const double *y, size_t n, size_t ld, double *partials);
+// one Chebyshev step (form 0..3 of chebyshev_step_kernel) on all blocks in one launch; diag == NULL: identity; diag_ld: 0 shared, ld block diagonal
+int blockvec_chebyshev_step(hipStream_t s, int form, unsigned grid_x, int n_components, bool nt, double *x_new, const double *x, const double *x_old, const double *src,
+                            const double *t, const double *diag, size_t n, size_t ld, size_t diag_ld, double f1, double f2);
+// dst_f += P src_c ; slots = per-cell shares of P^T (w (.) (b - tv)) (tv == NULL: of w (.) b), [component][cell][NC^3] ; the combine pass
+int blockvec_mg_prolongate(const MgComponentsArgs &a, int n_components, size_t ld_c, const double *src, size_t ld_f, double *dst);
+int blockvec_mg_restrict(const MgComponentsArgs &a, int n_components, size_t ld_f, const double *b, const double *tv, size_t slot_stride, double *slots);
+int blockvec_mg_combine(const MgComponentsArgs &a, int n_components, const double *slots, size_t slot_stride, uint32_t n_owned, uint32_t n, size_t ld, double *dst, bool add);
 
 // What every operator launch takes from the handle (affine builds read ONE scalar plane, cells n^3 entries apart); the launcher adds range and team counts
 inline ApplyArgs apply_args(const bp5_mf *mf, bool affine, const double *coef, const double *src, double *dst)

@@ -411,7 +411,8 @@ class ElasticityOperator:
     a(v, u) = int kappa [ lam (div v)(div u) + 2 mu eps(v) : eps(u) ] as the library's native coupled kernel (bp5_elasticity_*, include/bp5.h).
     `coef` holds the operator's TEN planes (K and kappa JxW); vectors are (3, ld) tensors; all three components are clamped on the mesh's
     Dirichlet set.  SolverCG.solve(op, x, b, DiagonalMatrix(block inverse diagonal or None)) runs bp5_cg_solve_elasticity; SolverCGFullMerge,
-    PreconditionChebyshev and PreconditionMG refuse it (BP5Error 5).  Not a PoissonOperator: nothing scalar is offered."""
+    PreconditionChebyshev and PreconditionMG refuse it (BP5Error 5): its preconditioners are ElasticityPreconditionChebyshev and
+    ElasticityPreconditionMG, which SolverCG.solve takes.  Not a PoissonOperator: nothing scalar is offered."""
 
     n_components = 3
 
@@ -763,6 +764,23 @@ class MGTwoLevelTransfer:
         _lib.check(_lib.lib().bp5_mg_transfer_restrict_add(self.handle, _ptr(_vals(dst), self.coarse.mf_data.n_local),
                                                            _ptr(_vals(src), self.fine.mf_data.n_local)))
 
+    def _components(self, fine_v, coarse_v):
+        fine_v, coarse_v = _vals(fine_v), _vals(coarse_v)
+        (ncf, ldf), (ncc, ldc) = _block_args(self.fine.mf_data, fine_v), _block_args(self.coarse.mf_data, coarse_v)
+        if ncf != ncc:
+            raise BP5Error(1, f"block vectors of one component count expected, got {ncf} (fine) and {ncc} (coarse)")
+        return ncf, ldf, _ptr(fine_v), ldc, _ptr(coarse_v)
+
+    def prolongate_and_add_components(self, dst, src):
+        """dst_f += P src_c block by block on (n_components, ld) tensors, one launch (bp5_mg_transfer_prolongate_add_components)"""
+        nc, ldf, pf, ldc, pc = self._components(dst, src)
+        _lib.check(_lib.lib().bp5_mg_transfer_prolongate_add_components(self.handle, nc, ldf, pf, ldc, pc))
+
+    def restrict_and_add_components(self, dst, src):
+        """dst_c += P^T src_f block by block on (n_components, ld) tensors (bp5_mg_transfer_restrict_add_components)"""
+        nc, ldf, pf, ldc, pc = self._components(src, dst)
+        _lib.check(_lib.lib().bp5_mg_transfer_restrict_add_components(self.handle, nc, ldc, pc, ldf, pf))
+
     def clear(self):
         if self._h:
             _lib.lib().bp5_mg_transfer_destroy(self._h)
@@ -915,6 +933,183 @@ class PreconditionMG:
             pass
 
 
+def _even_ld(mf):
+    return mf.n_local + (mf.n_local & 1)
+
+
+def _global_ids(mf):
+    ids = getattr(mf.mesh, "global_ids", None)
+    return np.ascontiguousarray(ids[:mf.n_owned], dtype=np.uint64) if ids is not None else None
+
+
+class ElasticityPreconditionChebyshev:
+    """== PreconditionChebyshev<ElasticityOperator, BlockVector, DiagonalMatrix>: the Chebyshev polynomial of PreconditionChebyshev for an
+    ElasticityOperator on (3, ld) tensors (bp5_elasticity_chebyshev_create, include/bp5.h).  AdditionalData: PreconditionChebyshev's, its
+    preconditioner a DiagonalMatrix holding the BLOCK inverse diagonal (ElasticityOperator.compute_diagonal(invert=True)) or None = identity.
+    ld: the row length of the vectors vmult / step will see -- default: the inverse diagonal's, else n_local rounded up to even (what
+    initialize_block_vector gives).  SolverCG.solve(op, x, b, this) runs bp5_cg_solve_elasticity_preconditioned with bp5_chebyshev_vmult."""
+
+    AdditionalData = PreconditionChebyshev.AdditionalData
+
+    def __init__(self):
+        self._h = None
+        self._keep = []
+
+    def initialize(self, A, data=None, ld=None):
+        self.clear()
+        if not isinstance(A, ElasticityOperator):
+            raise BP5Error(1, "ElasticityPreconditionChebyshev needs an ElasticityOperator (PreconditionChebyshev takes the scalar operators)")
+        data = data if data is not None else PreconditionChebyshev.AdditionalData()
+        mf = A.mf_data
+        inv = _vals(data.preconditioner.get_vector()) if data.preconditioner is not None else None
+        if inv is not None and not (_is_block(inv) and inv.shape[0] == 3):
+            raise BP5Error(1, f"elasticity: the inverse diagonal is a block vector of shape (3, ld), got {tuple(inv.shape)}")
+        self.ld = int(ld) if ld is not None else (int(inv.shape[1]) if inv is not None else _even_ld(mf))
+        if inv is not None and int(inv.shape[1]) != self.ld:
+            raise BP5Error(1, f"elasticity: the inverse diagonal has ld = {inv.shape[1]}, the preconditioner ld = {self.ld}")
+        self.A, self.mf_data, self.data = A, mf, data
+        ids = _global_ids(mf)
+        prm = _lib.ChebyshevParams(data.degree, data.smoothing_range, data.eig_cg_n_iterations, data.max_eigenvalue, data.min_eigenvalue,
+                                   ids.ctypes.data if ids is not None else None)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp5_elasticity_chebyshev_create(mf.handle, _ptr(A.coef), A.lam, A.mu, self.ld, _ptr(inv), C.byref(prm), C.byref(h)))
+        self._h = h
+        self._keep = [inv]               # the inverse diagonal lives as long as the handle
+        return self
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, "ElasticityPreconditionChebyshev.initialize has not been called")
+        return self._h
+
+    def _run(self, fn, dst, src):
+        dst, src = _vals(dst), _vals(src)
+        if self.A._args(dst, src) != self.ld:
+            raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {self.ld}, the vectors have {dst.shape[1]}")
+        _lib.check(fn(self.handle, _ptr(dst), _ptr(src)))
+
+    def vmult(self, dst, src):
+        """dst = P src on (3, ld) tensors (dst's prior content ignored); enqueued on the handle's stream."""
+        self._run(_lib.lib().bp5_chebyshev_vmult, dst, src)
+
+    def step(self, dst, src):
+        """Smoother: dst improved from its current value by `degree` Chebyshev steps on A dst = src."""
+        self._run(_lib.lib().bp5_chebyshev_step, dst, src)
+
+    estimated_eigenvalues = PreconditionChebyshev.estimated_eigenvalues
+
+    def clear(self):
+        if self._h:
+            _lib.lib().bp5_chebyshev_destroy(self._h)
+            self._h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
+def make_elasticity_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
+    """The ElasticityOperators of the multigrid levels below fine_op (on a BrickMesh): the same lam, mu, quadrature, coefficient, device and
+    stream at degrees p // 2, ..., 1 on the same cells, then at the last degree up to h_levels geometric levels (an int, or "max") on
+    BrickMesh.coarsen(min_cells) of the one above -- make_mg_hierarchy's rule.  Returns [fine_op, ...] for ElasticityPreconditionMG."""
+    from .mesh import BrickMesh
+    if not isinstance(fine_op, ElasticityOperator):
+        raise BP5Error(1, "make_elasticity_mg_hierarchy needs an ElasticityOperator")
+    if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
+        raise BP5Error(1, f"make_elasticity_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
+    mf, m = fine_op.mf_data, fine_op.mf_data.mesh
+
+    def level(mesh):
+        return ElasticityOperator(mesh, mf.quadrature, mf.coefficient, lam=fine_op.lam, mu=fine_op.mu, device=mf.device, stream=mf.stream)
+
+    ops = [fine_op]
+    for p in mg_coarse_degrees(m.degree)[1:]:
+        ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
+                                   dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)))
+    n_h = 0
+    while h_levels == "max" or n_h < h_levels:
+        coarse = ops[-1].mf_data.mesh.coarsen(min_cells)
+        if coarse is None:
+            break
+        ops.append(level(coarse))
+        n_h += 1
+    return ops
+
+
+class ElasticityPreconditionMG:
+    """== PreconditionMG<dim, BlockVector, MGTransferMatrixFree> for ElasticityOperators, fine to coarse (make_elasticity_mg_hierarchy builds
+    them): PreconditionMG's V-cycle -- Chebyshev smoothers on the block inverse diagonals, the fused residual restriction, the scalar transfer
+    handles on all three blocks, the coarse polynomial -- on (3, ld) tensors (bp5_elasticity_mg_create, include/bp5.h).  ld: the row length of
+    the vectors vmult will see (default: n_local of the fine level rounded up to even).  SolverCG.solve(op, x, b, this) runs
+    bp5_cg_solve_elasticity_preconditioned with bp5_mg_vmult."""
+
+    AdditionalData = PreconditionMG.AdditionalData
+
+    def __init__(self, operators, data=None, ld=None):
+        self._h = None
+        self.transfers = []
+        self.initialize(operators, data, ld)
+
+    def initialize(self, operators, data=None, ld=None):
+        self.clear()
+        data = data if data is not None else PreconditionMG.AdditionalData()
+        ops = list(operators)
+        if not ops or not all(isinstance(o, ElasticityOperator) for o in ops):
+            raise BP5Error(1, "ElasticityPreconditionMG needs a list of ElasticityOperators, fine to coarse")
+        if len({o.mf_data.stream for o in ops}) > 1:
+            raise BP5Error(1, "ElasticityPreconditionMG: the levels must share one stream (MatrixFree.set_stream moves each of them)")
+        if len({(o.lam, o.mu) for o in ops}) > 1:
+            raise BP5Error(1, "ElasticityPreconditionMG: the levels must share lam and mu")
+        self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
+        self.ld = int(ld) if ld is not None else _even_ld(self.mf_data)
+        self.transfers = [MGTwoLevelTransfer(f, c, geometric=f.mf_data.mesh.degree == c.mf_data.mesh.degree) for f, c in zip(ops[:-1], ops[1:])]
+        ids = [_global_ids(o.mf_data) for o in ops]
+        id_ptrs = (C.c_void_p * len(ops))(*[a.ctypes.data if a is not None else None for a in ids])
+        prm = _lib.MGParams(data.smoother_degree, data.smoothing_range, data.eig_cg_n_iterations, data.coarse_degree, data.coarse_range,
+                            data.coarse_eig_cg_n_iterations, C.cast(id_ptrs, C.c_void_p))
+        n = len(ops)
+        mfs = (C.c_void_p * n)(*[o.mf_data.handle.value for o in ops])
+        coefs = (C.c_void_p * n)(*[o.coef.data_ptr() for o in ops])
+        trs = (C.c_void_p * max(n - 1, 1))(*[t.handle.value for t in self.transfers])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().bp5_elasticity_mg_create(n, mfs, coefs, ops[0].lam, ops[0].mu, self.ld, trs, C.byref(prm), C.byref(h)))
+        self._h = h
+        return self
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, "ElasticityPreconditionMG has been cleared")
+        return self._h
+
+    def vmult(self, dst, src):
+        """dst = V src on (3, ld) tensors: one V-cycle (dst's prior content ignored); enqueued on the operators' stream."""
+        dst, src = _vals(dst), _vals(src)
+        if self.operators[0]._args(dst, src) != self.ld:
+            raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {self.ld}, the vectors have {dst.shape[1]}")
+        _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(dst), _ptr(src)))
+
+    level_info = PreconditionMG.level_info
+
+    def clear(self):
+        if self._h:
+            _lib.lib().bp5_mg_destroy(self._h)
+            self._h = None
+        for t in self.transfers:
+            t.clear()
+        self.transfers = []
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
 class _SolverBase:
     variant = CG_PLAIN
 
@@ -926,11 +1121,16 @@ class _SolverBase:
         A PoissonOperator runs entirely inside bp5_cg_solve; any other object with `mf_data` (vector layout, stream) and
         `vmult(dst, src)` is solved through bp5_cg_solve_operator -- the solvers need nothing of A but vmult
         (bp5/solver.h:25-30,377,475).  The preconditioner: None / DiagonalMatrix (the solvers' diag), a PreconditionChebyshev (native:
-        bp5_cg_solve_preconditioned with bp5_chebyshev_vmult), a PreconditionMG (native: bp5_mg_vmult), or any other object with vmult(dst, src) (through a callback; SolverCG only)."""
+        bp5_cg_solve_preconditioned with bp5_chebyshev_vmult), a PreconditionMG (native: bp5_mg_vmult), or any other object with vmult(dst, src) (through a callback; SolverCG only).
+        An ElasticityOperator: None / DiagonalMatrix (bp5_cg_solve_elasticity), or an ElasticityPreconditionChebyshev / ElasticityPreconditionMG
+        (bp5_cg_solve_elasticity_preconditioned with their native vmult; SolverCG only); anything else is refused (BP5Error 5)."""
         mf = A.mf_data
         x, b = _vals(x), _vals(b)
         general = preconditioner is not None and not hasattr(preconditioner, "get_vector")
-        if isinstance(A, ElasticityOperator) and (self.variant != CG_PLAIN or general):      # (one status for the class, whatever else is wrong)
+        # the elasticity preconditioners (SolverCG): bp5_cg_solve_elasticity_preconditioned with their native vmult
+        el_precond = (isinstance(A, ElasticityOperator) and self.variant == CG_PLAIN
+                      and isinstance(preconditioner, (ElasticityPreconditionChebyshev, ElasticityPreconditionMG)))
+        if isinstance(A, ElasticityOperator) and (self.variant != CG_PLAIN or general) and not el_precond:      # (one status for the class, whatever else is wrong)
             raise BP5Error(5, "elasticity: SolverCG with None / DiagonalMatrix only")
         if general and not hasattr(preconditioner, "vmult"):
             raise BP5Error(1, "the preconditioner needs get_vector() (diagonal) or vmult(dst, src)")
@@ -941,7 +1141,14 @@ class _SolverBase:
         res = _lib.CGResult()
         failure = []
         native = isinstance(A, PoissonOperator)
-        if isinstance(A, ElasticityOperator):
+        if el_precond:
+            ld = A._args(x, b)
+            if ld != preconditioner.ld:
+                raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {preconditioner.ld}, the vectors have {ld}")
+            fn = _lib.lib().bp5_mg_vmult if isinstance(preconditioner, ElasticityPreconditionMG) else _lib.lib().bp5_chebyshev_vmult
+            status = _lib.lib().bp5_cg_solve_elasticity_preconditioned(mf.handle, _ptr(A.coef), A.lam, A.mu, ld, C.cast(fn, C.c_void_p), preconditioner.handle,
+                                                                       _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
+        elif isinstance(A, ElasticityOperator):
             # the coupled three-component system: ONE Krylov space, a BLOCK inverse diagonal (bp5_cg_solve_elasticity)
             ld = A._args(x, b)
             diag = _vals(preconditioner.get_vector()) if preconditioner is not None else None

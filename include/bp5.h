@@ -636,6 +636,17 @@ int bp5_elasticity_compute_diagonal(bp5_mf *mf, const double *coef, double lambd
 int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag, const double *b, double *x,
                             const bp5_cg_params *params, bp5_cg_result *result_host);
 
+/* SolverCG on A x = b with ANY preconditioner: the BP5_CG_PLAIN recurrence of bp5_cg_solve_preconditioned on the stacked three-component system.
+ * precond (bp5_vmult_fn shape) enqueues z = P g on three-block vectors of the same ld on the handle's stream: bp5_chebyshev_vmult with a handle of
+ * bp5_elasticity_chebyshev_create, bp5_mg_vmult with a handle of bp5_elasticity_mg_create (both created with this ld), or any callback; it defines
+ * the owned entries of every block of z and never touches [n_owned + n_ghost, ld).  One Krylov space; g.g and g.z run over the owned entries of all
+ * blocks in a fixed order; stop rule, check_every (0: the host's lagged look at the stop flag, as bp5_cg_solve_preconditioned), breakdown status and
+ * result fields as bp5_cg_solve_elasticity.  z (3 ld doubles) belongs to the handle, beside g, d, h.  Refusals: those of bp5_cg_solve_elasticity
+ * (BP5_CG_MERGED: BP5_ERR_UNSUPPORTED), a null precond BP5_ERR_INVALID.
+ * (replaces SolverCG<BlockVector>::solve(A, x, b, PreconditionChebyshev / PreconditionMG) of step-8 with step-37's preconditioners) */
+int bp5_cg_solve_elasticity_preconditioned(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                                           const double *b, double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
+
 /* BP5_CG_MERGED on the packed block kernel (cell bricks, one rank's cells, diag == NULL): by default the operator's
  * write-out and combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311: p.v, v.v, r.v, r.r)
  * and write the Dirichlet rows, so the separate pass over p, r, v and the copy_constrained launch disappear.  Same
@@ -691,6 +702,17 @@ int bp5_chebyshev_eigenvalues(const bp5_chebyshev *c, double *min_est, double *m
 int bp5_chebyshev_vmult(void *c, double *dst, double *src);          /* bp5_vmult_fn shape: dst = P src, dst's prior content ignored */
 int bp5_chebyshev_step(bp5_chebyshev *c, double *dst, double *src);  /* smoother: dst improved from its current value              */
 int bp5_chebyshev_destroy(bp5_chebyshev *c);
+/* PreconditionChebyshev<ElasticityOperator, BlockVector, DiagonalMatrix> (deal.II step-8's operator under step-37's smoother): the same polynomial
+ * for the elasticity operator of bp5_elasticity_apply (coef: its ten planes; lambda, mu by value) on three-block vectors ld apart.  inv_diag: a
+ * BLOCK inverse diagonal as bp5_elasticity_compute_diagonal(..., invert = 1) returns it (three blocks ld apart), or NULL = identity; it must stay
+ * valid for the life of the handle.  The result is an ordinary bp5_chebyshev: bp5_chebyshev_vmult, _step, _eigenvalues and _destroy take it, its
+ * vectors are then three-block vectors of the ld given here (entries [n_owned + n_ghost, ld) never read, never written); each step is ONE launch of
+ * the block form of the pointwise kernel (chebyshev_step_components_kernel: the component is the second grid dimension) and one
+ * bp5_elasticity_apply.  The estimate is Jacobi-PCG on the stacked system (one Krylov space, the block diagonal) from the start vector
+ * v_c[i] = ((3 id_i + c) mod 11) - 5, 0 on Dirichlet DoFs, id from params->start_ids_host (NULL: the local index).  Refusals: those of
+ * bp5_elasticity_apply (bp5_last_error names "elasticity"), and bp5_chebyshev_create's on params. */
+int bp5_elasticity_chebyshev_create(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *inv_diag,
+                                    const bp5_chebyshev_params *params, bp5_chebyshev **out);
 /* all eigenvalues of the symmetric tridiagonal matrix (diag[n], offdiag[n-1]), ascending; Sturm-sequence bisection on the host
  * (no LAPACK, no GPU) */
 int bp5_tridiagonal_eigenvalues(int n, const double *diag, const double *offdiag, double *eig_ascending_host);
@@ -717,6 +739,19 @@ int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_transfer **out);
 int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst_fine, double *src_coarse);
 int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst_coarse, double *src_fine);
 int bp5_mg_transfer_destroy(bp5_mg_transfer *t);
+/* The same transfers on block vectors (MGTwoLevelTransfer<dim, BlockVector>: prolongate_and_add / restrict_and_add block by block), on the SAME
+ * scalar transfer handles, p-transfers and geometric ones: index lists, writer masks and weights are per scalar DoF and shared by all components.
+ * Component c of the fine vector at v + c * ld_fine, of the coarse vector at v + c * ld_coarse (layout as for bp5_apply_components: each ld even and
+ * >= n_owned + n_ghost of its level, bases 16-byte aligned, entries [n_owned + n_ghost, ld) never read, never written).  ONE launch per direction
+ * serves all components (mg_prolongate_components_kernel, mg_restrict_components_kernel + mg_combine_components_kernel): a thread reads its index,
+ * writer-mask bit and weight once and runs the components one after the other through the same LDS tile; per component the floating-point
+ * operations are the scalar kernel's in the scalar kernel's order, so every block holds the bits bp5_mg_transfer_prolongate_add / _restrict_add
+ * give on that block alone.  Slots are [component][cell][(pc+1)^3]; a call with more components than any before it on the handle grows them
+ * (bp5_elasticity_mg_create reserves three).  n_components: 1 .. BP5_MAX_COMPONENTS.  Refused before any launch -- BP5_ERR_INVALID: null pointer,
+ * n_components out of range, an odd or too small ld, a misaligned base; BP5_ERR_UNSUPPORTED: a transfer whose handles have a communicator and
+ * neighbours (no block halo exchange here). */
+int bp5_mg_transfer_prolongate_add_components(bp5_mg_transfer *t, int n_components, size_t ld_fine, double *dst_fine, size_t ld_coarse, double *src_coarse);
+int bp5_mg_transfer_restrict_add_components(bp5_mg_transfer *t, int n_components, size_t ld_coarse, double *dst_coarse, size_t ld_fine, double *src_fine);
 
 /* Geometric (h) transfer at one degree p in 1..4 (deal.II MGTwoLevelTransfer::reinit_geometric_transfer, step-75's h-levels): the
  * coarse handle's cells are the parents of the fine handle's, 8 children each (bp5_mesh_parent_cells gives the map: parent_cell_host[k],
@@ -766,6 +801,17 @@ typedef struct bp5_mg bp5_mg;
 void bp5_mg_params_default(bp5_mg_params *params);
 int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, bp5_mg_transfer *const *transfers, const bp5_mg_params *params,
                   bp5_mg **out);
+/* PreconditionMG for the elasticity operator (deal.II step-8's operator under step-37 / step-75's hybrid multigrid): the V-cycle above, step for
+ * step, on three-block vectors.  mfs[l] / coefs[l]: the level's handle and its TEN elasticity planes (bp5_elasticity_compute_metric); lambda, mu the
+ * same on every level; transfers[l]: the scalar transfer handles between the levels (p-transfers and geometric ones in any mix), used through
+ * bp5_mg_transfer_*_components; ld: the stride of the level-0 vectors bp5_mg_vmult will see (level vectors below have their own even ld).  Every
+ * level gets its three inverse diagonals (bp5_elasticity_compute_diagonal) and a polynomial of bp5_elasticity_chebyshev_create; the residual
+ * restriction is fused (b - A x is never stored); nothing allocates inside vmult.  The result is an ordinary bp5_mg for bp5_mg_vmult (three-block
+ * vectors of this ld), bp5_mg_level_info and bp5_mg_destroy.  Refused before any launch, bp5_last_error names "elasticity": everything
+ * bp5_elasticity_apply refuses, for every level; levels on different streams (BP5_ERR_INVALID, "stream"); a level without Dirichlet DoFs
+ * (BP5_ERR_UNSUPPORTED, "Dirichlet": the coarse polynomial is no solver for a singular level). */
+int bp5_elasticity_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
+                             bp5_mg_transfer *const *transfers, const bp5_mg_params *params, bp5_mg **out);
 int bp5_mg_vmult(void *mg, double *dst, double *src); /* bp5_vmult_fn shape: plugs into bp5_cg_solve_preconditioned */
 int bp5_mg_level_info(const bp5_mg *mg, int level, bp5_mg_level *out);
 int bp5_mg_destroy(bp5_mg *mg);
