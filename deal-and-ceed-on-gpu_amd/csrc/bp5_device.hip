@@ -3063,27 +3063,17 @@ static int cheb_apply(bp5_chebyshev *c, double *x, double *t)
   return bp5_apply(mf, c->coef, x, t, 1);
 }
 
-// one Chebyshev step kernel: FORM as chebyshev_step_kernel; diag present / absent and the streaming policy (BP5_TUNE_UPDATE_NT) resolved here
+// one Chebyshev step kernel (blockvec/bp5_blockvec.hip): FORM as chebyshev_step_kernel, the streaming policy (BP5_TUNE_UPDATE_NT) and the flat launch
+// shape from the handle.  Elasticity: the three blocks, and those of the block inverse diagonal, ld apart in one launch
 template <int FORM>
 static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, const double *x_old, const double *src, double f1, double f2)
 {
   bp5_mf *mf = c->mf;
   const size_t n = mf->n_owned;
   if (!n) return BP5_OK;
-  const dim3 grid(stream_grid_flat(mf, n, 2)), block(VB);
-  const bool nt = mf->tune[BP5_TUNE_UPDATE_NT] != 0;
-  const double *dg = c->inv_diag, *t = c->t;
-  if (c->elasticity) // the three blocks in one launch (chebyshev_step_components_kernel), the same streaming policy and flat launch shape
-    return blockvec_chebyshev_step(mf->stream, FORM, grid.x, 3, nt, x_new, x, x_old, src, t, dg, n, c->ld, c->ld, f1, f2);
-  if (dg) {
-    if (nt) hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, true>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
-    else hipLaunchKernelGGL((chebyshev_step_kernel<FORM, true, false>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
-  } else {
-    if (nt) hipLaunchKernelGGL((chebyshev_step_kernel<FORM, false, true>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
-    else hipLaunchKernelGGL((chebyshev_step_kernel<FORM, false, false>), grid, block, 0, mf->stream, x_new, x, x_old, src, t, dg, n, f1, f2);
-  }
-  KERNEL_CHECK();
-  return BP5_OK;
+  const unsigned grid_x = stream_grid_flat(mf, n, 2);
+  return blockvec_chebyshev_step(mf->stream, FORM, grid_x, c->elasticity ? 3 : 1, mf->tune[BP5_TUNE_UPDATE_NT] != 0, x_new, x, x_old, src, c->t, c->inv_diag, n, c->ld,
+                                 c->ld, f1, f2);
 }
 
 // el_ld != 0 (bp5_elasticity_chebyshev_create, which has checked handle, layout and parameters): the elasticity operator on three-block vectors
@@ -3270,96 +3260,6 @@ struct bp5_mg_transfer {
   size_t slot_stride() const { return (size_t)fine->n_cells * coarse->n3; }
   std::vector<void *> device_arrays() const { return {d_M, d_w, d_slots, d_cidx, d_wmask, d_coff, d_cslot, d_pcode, d_slots_c}; }
 };
-
-// the instantiated degree pairs (pf -> max(1, pf / 2))
-template <int NF, int NC>
-static int mg_prolongate_launch(bp5_mg_transfer *t, double *dst, const double *src)
-{
-  using S = MgShape<NF, NC>;
-  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
-  if (grid) hipLaunchKernelGGL((mg_prolongate_kernel<NF, NC>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_cidx, t->fine->d_l2g, t->d_wmask,
-                              nc, src, dst);
-  KERNEL_CHECK();
-  return BP5_OK;
-}
-template <int NF, int NC>
-static int mg_restrict_launch(bp5_mg_transfer *t, const double *b, const double *tv)
-{
-  using S = MgShape<NF, NC>;
-  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
-  if (!grid) return BP5_OK;
-  if (tv) hipLaunchKernelGGL((mg_restrict_kernel<NF, NC, true>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->fine->d_l2g, nc, t->d_w, b, tv, t->d_slots);
-  else hipLaunchKernelGGL((mg_restrict_kernel<NF, NC, false>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->fine->d_l2g, nc, t->d_w, b, tv, t->d_slots);
-  KERNEL_CHECK();
-  return BP5_OK;
-}
-#define MG_DISPATCH(fn, t, ...)                                                                                    \
-  switch (t->pf) {                                                                                                 \
-  case 2: return fn<3, 2>(t, __VA_ARGS__);                                                                         \
-  case 3: return fn<4, 2>(t, __VA_ARGS__);                                                                         \
-  case 4: return fn<5, 3>(t, __VA_ARGS__);                                                                         \
-  case 5: return fn<6, 3>(t, __VA_ARGS__);                                                                         \
-  case 6: return fn<7, 4>(t, __VA_ARGS__);                                                                         \
-  case 7: return fn<8, 4>(t, __VA_ARGS__);                                                                         \
-  case 8: return fn<9, 5>(t, __VA_ARGS__);                                                                         \
-  default: return fail(BP5_ERR_INVALID, "multigrid transfer: fine degree must be 2..8");                           \
-  }
-// geometric transfers, p = 1..4
-template <int N>
-static int mg_geo_prolongate_launch(bp5_mg_transfer *t, double *dst, const double *src)
-{
-  using S = MgShape<N, N>;
-  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
-  if (grid) hipLaunchKernelGGL((mg_geo_prolongate_kernel<N>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_cidx, t->d_pcode, t->fine->d_l2g,
-                              t->d_wmask, nc, src, dst);
-  KERNEL_CHECK();
-  return BP5_OK;
-}
-template <int N>
-static int mg_geo_restrict_launch(bp5_mg_transfer *t, const double *b, const double *tv)
-{
-  using S = MgShape<N, N>;
-  const uint32_t nc = t->fine->n_cells, grid = (nc + S::CPB - 1) / S::CPB;
-  if (!grid) return BP5_OK;
-  if (tv) hipLaunchKernelGGL((mg_geo_restrict_kernel<N, true>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_pcode, t->fine->d_l2g, nc, t->d_w, b, tv,
-                             t->d_slots);
-  else hipLaunchKernelGGL((mg_geo_restrict_kernel<N, false>), dim3(grid), dim3(256), 0, t->fine->stream, t->d_M, t->d_pcode, t->fine->d_l2g, nc, t->d_w, b, tv,
-                          t->d_slots);
-  KERNEL_CHECK();
-  return BP5_OK;
-}
-// ... of the fine level's degree
-template <class F>
-static int mg_geo_dispatch(const bp5_mg_transfer *t, F &&f)
-{
-  const char *refusal = "geometric multigrid transfer: degree must be 1..4";
-  return for_degree(t->pf <= 4 ? t->pf : 0, [&](auto P) {
-    if constexpr (P() <= 4) return f(P);
-    else return fail(BP5_ERR_INVALID, refusal);
-  }, refusal);
-}
-static int mg_prolongate_dispatch(bp5_mg_transfer *t, double *dst, const double *src)
-{
-  if (t->geometric) return mg_geo_dispatch(t, [&](auto P) { return mg_geo_prolongate_launch<P() + 1>(t, dst, src); });
-  MG_DISPATCH(mg_prolongate_launch, t, dst, src);
-}
-static int mg_restrict_dispatch(bp5_mg_transfer *t, const double *b, const double *tv)
-{
-  if (t->geometric) return mg_geo_dispatch(t, [&](auto P) { return mg_geo_restrict_launch<P() + 1>(t, b, tv); });
-  MG_DISPATCH(mg_restrict_launch, t, b, tv);
-}
-
-static int mg_combine(bp5_mg_transfer *t, double *dst, bool add)
-{
-  bp5_mf *c = t->coarse;
-  const uint32_t n = (uint32_t)c->n_local();
-  if (!n) return BP5_OK;
-  const uint32_t grid = std::min<uint32_t>((n + 255) / 256, 65536u);
-  if (add) hipLaunchKernelGGL(mg_combine_kernel<true>, dim3(grid), dim3(256), 0, c->stream, t->d_coff, t->d_cslot, t->d_slots, c->n_owned, n, dst);
-  else hipLaunchKernelGGL(mg_combine_kernel<false>, dim3(grid), dim3(256), 0, c->stream, t->d_coff, t->d_cslot, t->d_slots, c->n_owned, n, dst);
-  KERNEL_CHECK();
-  return BP5_OK;
-}
 
 // the CSR of each coarse local DoF's slots, ascending (= cell order): slot_dof[s] the coarse DoF slot s adds to (MG_NO_DOF: none)
 static int mg_upload_slot_csr(bp5_mg_transfer *t, const std::vector<uint32_t> &slot_dof)
@@ -3566,35 +3466,9 @@ extern "C" int bp5_mg_transfer_create_geometric(bp5_mf *fine, bp5_mf *coarse, co
   return BP5_OK;
 }
 
-extern "C" int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst, double *src)
-{
-  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(t->fine->device));
-  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_gather(t->coarse, src));
-  return mg_prolongate_dispatch(t, dst, src);
-}
-
-// dst_c (+)= P^T (w (.) (b - tv)), tv == NULL: P^T (w (.) b); with neighbours the fine ghosts of b (and tv) are gathered first and the
-// coarse ghost rows are sent to their owners
-static int mg_restrict(bp5_mg_transfer *t, double *dst, double *b, double *tv, bool add)
-{
-  HIP_TRY(hipSetDevice(t->fine->device));
-  if (t->fine->has_neighbors()) {
-    BP5_TRY(bp5_halo_gather(t->fine, b));
-    if (tv) BP5_TRY(bp5_halo_gather(t->fine, tv));
-  }
-  BP5_TRY(mg_restrict_dispatch(t, b, tv));
-  BP5_TRY(mg_combine(t, dst, add));
-  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_scatter_add(t->coarse, dst));
-  return BP5_OK;
-}
-extern "C" int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst, double *src)
-{
-  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
-  return mg_restrict(t, dst, src, nullptr, true);
-}
-
-// ---- the same transfers on block vectors (blockvec/bp5_blockvec.hip): the lists are per scalar DoF and shared by all components
+// ---- the transfers on validated arguments, scalar vectors as n_components = 1 (blockvec/bp5_blockvec.hip): the lists are per scalar DoF and shared by
+// all components.  The halo gather / scatter-add of handles with neighbours is reachable from the scalar entries only: mg_components_check refuses
+// neighbours on the block entries
 static MgComponentsArgs mg_components_args(const bp5_mg_transfer *t)
 {
   MgComponentsArgs a;
@@ -3626,31 +3500,50 @@ static int mg_components_check(const bp5_mg_transfer *t, int n_components, size_
     return fail(BP5_ERR_UNSUPPORTED, "multigrid transfer on block vectors: no halo exchange (handles with a communicator and neighbours)");
   return BP5_OK;
 }
-// dst_f += P src_c on validated arguments
-static int mg_prolongate_components(bp5_mg_transfer *t, int n_components, size_t ld_f, double *dst, size_t ld_c, const double *src)
+// dst_f += P src_c; with neighbours the coarse ghosts of src are gathered first
+static int mg_prolongate(bp5_mg_transfer *t, int n_components, size_t ld_f, double *dst, size_t ld_c, double *src)
 {
+  HIP_TRY(hipSetDevice(t->fine->device));
+  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_gather(t->coarse, src));
   return blockvec_mg_prolongate(mg_components_args(t), n_components, ld_c, src, ld_f, dst);
 }
-// dst_c (+)= P^T (w (.) (b - tv)) on validated arguments, tv == NULL: P^T (w (.) b)
-static int mg_restrict_components(bp5_mg_transfer *t, int n_components, size_t ld_c, double *dst, size_t ld_f, const double *b, const double *tv, bool add)
+// dst_c (+)= P^T (w (.) (b - tv)), tv == NULL: P^T (w (.) b); with neighbours the fine ghosts of b (and tv) are gathered first and the
+// coarse ghost rows are sent to their owners
+static int mg_restrict(bp5_mg_transfer *t, int n_components, size_t ld_c, double *dst, size_t ld_f, double *b, double *tv, bool add)
 {
+  HIP_TRY(hipSetDevice(t->fine->device));
+  if (t->fine->has_neighbors()) {
+    BP5_TRY(bp5_halo_gather(t->fine, b));
+    if (tv) BP5_TRY(bp5_halo_gather(t->fine, tv));
+  }
   double *slots = nullptr;
   BP5_TRY(mg_reserve_slots(t, n_components, &slots));
   const MgComponentsArgs a = mg_components_args(t);
   BP5_TRY(blockvec_mg_restrict(a, n_components, ld_f, b, tv, t->slot_stride(), slots));
-  return blockvec_mg_combine(a, n_components, slots, t->slot_stride(), t->coarse->n_owned, (uint32_t)t->coarse->n_local(), ld_c, dst, add);
+  BP5_TRY(blockvec_mg_combine(a, n_components, slots, t->slot_stride(), t->coarse->n_owned, (uint32_t)t->coarse->n_local(), ld_c, dst, add));
+  if (t->coarse->has_neighbors()) BP5_TRY(bp5_halo_scatter_add(t->coarse, dst));
+  return BP5_OK;
+}
+
+extern "C" int bp5_mg_transfer_prolongate_add(bp5_mg_transfer *t, double *dst, double *src)
+{
+  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  return mg_prolongate(t, 1, 0, dst, 0, src);
+}
+extern "C" int bp5_mg_transfer_restrict_add(bp5_mg_transfer *t, double *dst, double *src)
+{
+  if (!t || !dst || !src) return fail(BP5_ERR_INVALID, "null argument");
+  return mg_restrict(t, 1, 0, dst, 0, src, nullptr, true);
 }
 extern "C" int bp5_mg_transfer_prolongate_add_components(bp5_mg_transfer *t, int n_components, size_t ld_fine, double *dst_fine, size_t ld_coarse, double *src_coarse)
 {
   BP5_TRY(mg_components_check(t, n_components, ld_fine, dst_fine, ld_coarse, src_coarse));
-  HIP_TRY(hipSetDevice(t->fine->device));
-  return mg_prolongate_components(t, n_components, ld_fine, dst_fine, ld_coarse, src_coarse);
+  return mg_prolongate(t, n_components, ld_fine, dst_fine, ld_coarse, src_coarse);
 }
 extern "C" int bp5_mg_transfer_restrict_add_components(bp5_mg_transfer *t, int n_components, size_t ld_coarse, double *dst_coarse, size_t ld_fine, double *src_fine)
 {
   BP5_TRY(mg_components_check(t, n_components, ld_fine, src_fine, ld_coarse, dst_coarse));
-  HIP_TRY(hipSetDevice(t->fine->device));
-  return mg_restrict_components(t, n_components, ld_coarse, dst_coarse, ld_fine, src_fine, nullptr, true);
+  return mg_restrict(t, n_components, ld_coarse, dst_coarse, ld_fine, src_fine, nullptr, true);
 }
 
 extern "C" int bp5_mg_transfer_destroy(bp5_mg_transfer *t)
@@ -3757,7 +3650,7 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   return BP5_OK;
 }
 
-// The elasticity V-cycle (bp5_elasticity_mg_create): exactly mg_level's steps, on three-block vectors
+// The elasticity V-cycle (bp5_elasticity_mg_create): mg_level on three-block vectors
 static int elasticity_mg_create_check(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
                                       bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
 {
@@ -3830,31 +3723,19 @@ extern "C" int bp5_elasticity_mg_create(int n_levels, bp5_mf *const *mfs, const 
   *out = mg.release();
   return BP5_OK;
 }
-static int mg_level_elasticity(bp5_mg *mg, int l, double *x, double *b)
-{
-  if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
-  bp5_mf *mf = mg->mf[l];
-  const size_t ld = mg->ld[l], ldc = mg->ld[l + 1];
-  BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                                                   // pre-smoothing from zero
-  BP5_TRY(bp5_elasticity_apply(mf, mg->coef[l], mg->lambda, mg->mu, ld, x, mg->t[l], 1));             // t = A x
-  BP5_TRY(mg_restrict_components(mg->tr[l], 3, ldc, mg->b[l + 1], ld, b, mg->t[l], false));          // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
-  BP5_TRY(mg_level_elasticity(mg, l + 1, mg->x[l + 1], mg->b[l + 1]));
-  BP5_TRY(mg_prolongate_components(mg->tr[l], 3, ld, x, ldc, mg->x[l + 1]));                          // x += P x_c
-  return bp5_chebyshev_step(mg->cheb[l], x, b);                                                      // post-smoothing
-}
-
+// one level of the V-cycle.  The scalar and the elasticity cycle are the same steps: the level's Chebyshev handle knows its operator (elasticity,
+// distributed or plain apply on the level's own metric), and the vectors are 1 block or 3 blocks ld[l] apart
 static int mg_level(bp5_mg *mg, int l, double *x, double *b)
 {
-  if (mg->elasticity) return mg_level_elasticity(mg, l, x, b);
   if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
-  bp5_mf *mf = mg->mf[l];
-  BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                      // pre-smoothing from zero
-  if (mf->has_neighbors()) BP5_TRY(bp5_apply_distributed(mf, mg->coef[l], x, mg->t[l], 1));
-  else BP5_TRY(bp5_apply(mf, mg->coef[l], x, mg->t[l], 1));             // t = A x
-  BP5_TRY(mg_restrict(mg->tr[l], mg->b[l + 1], b, mg->t[l], false));   // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
+  const int nc = mg->elasticity ? 3 : 1;
+  const size_t ld = mg->elasticity ? mg->ld[l] : 0, ldc = mg->elasticity ? mg->ld[l + 1] : 0;
+  BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                                   // pre-smoothing from zero
+  BP5_TRY(cheb_apply(mg->cheb[l], x, mg->t[l]));                                     // t = A x
+  BP5_TRY(mg_restrict(mg->tr[l], nc, ldc, mg->b[l + 1], ld, b, mg->t[l], false));    // b_c = P^T (w (.) (b - t)), Dirichlet rows 0
   BP5_TRY(mg_level(mg, l + 1, mg->x[l + 1], mg->b[l + 1]));
-  BP5_TRY(bp5_mg_transfer_prolongate_add(mg->tr[l], x, mg->x[l + 1]));  // x += P x_c
-  return bp5_chebyshev_step(mg->cheb[l], x, b);                        // post-smoothing
+  BP5_TRY(mg_prolongate(mg->tr[l], nc, ld, x, ldc, mg->x[l + 1]));                   // x += P x_c
+  return bp5_chebyshev_step(mg->cheb[l], x, b);                                      // post-smoothing
 }
 
 extern "C" int bp5_mg_vmult(void *mgv, double *dst, double *src)

@@ -343,8 +343,9 @@ int elasticity_compute_metric(bp5_mf *mf, double *coef);
 int elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1);
 int elasticity_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag);
 
-// Block-vector forms of the pointwise and transfer kernels (the elasticity preconditioners), defined in blockvec/bp5_blockvec.hip -- a translation
-// unit of its own.  n_components blocks ld apart; the callers have validated handles and layouts.
+// The pointwise and transfer kernels of every vector shape (the Chebyshev step and the multigrid transfers of scalar and of block vectors, the dot
+// product of block vectors), defined in blockvec/bp5_blockvec.hip -- a translation unit of its own, the only one that instantiates them.
+// n_components blocks ld apart, a scalar vector n_components = 1 (ld is then not read); the callers have validated handles and layouts.
 struct MgComponentsArgs { // the device tables of one transfer (bp5_mg_transfer), by value
   int pf = 0;
   bool geometric = false;

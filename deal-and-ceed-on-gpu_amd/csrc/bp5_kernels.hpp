@@ -4623,6 +4623,32 @@ static __global__ void cg_record_kernel(const double *sc, const int *st, double 
   hist[2 * k - 1] = st[ST_DONE] ? 0.0 : sc[SC_BETA];
 }
 
+// ---- pointwise and transfer kernels of every vector shape (PreconditionChebyshev and the multigrid transfers, scalar and block vectors;
+// instantiated in blockvec/bp5_blockvec.hip only).  A vector is n_components blocks ld apart, padding entries [n, ld) of a block never touched; a
+// scalar vector is n_components = 1.  Per component every kernel performs the same floating-point operations in the same order, whatever the
+// component count: a block holds the bits that a scalar call on that block gives.
+
+// partial sums of x.y over the owned entries of all blocks: dot_kernel with the component as second grid dimension, columns as cg_dh_kernel
+// UnitTag: an empty tag type of the translation unit that launches the kernel (blockvec/bp5_blockvec.hip: BlockvecUnit); it selects nothing.  It
+// makes the kernel a template, so that only that unit instantiates it: a plain static kernel of this header lands in the code object of EVERY
+// unit that includes it (DESIGN 7j)
+struct BlockvecUnit {};
+template <class UnitTag>
+__global__ void __launch_bounds__(VB) dot_components_kernel(const double *x, const double *y, size_t n, size_t ld, double *partials)
+{
+  x += blockIdx.y * ld; y += blockIdx.y * ld;
+  double acc[1] = {0.0};
+  const size_t stride = (size_t)gridDim.x * VB * 2;
+  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
+    if (i + 1 < n) {
+      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
+      acc[0] += a.x * b.x + a.y * b.y;
+    } else
+      acc[0] += x[i] * y[i];
+  }
+  block_reduce_store<1>(acc, partials + blockIdx.y * gridDim.x);
+}
+
 // ---- PreconditionChebyshev: one launch per Chebyshev step, pointwise over the owned entries, t = A x_k written just before by the operator:
 //   FORM 0  x_1     = f2 D^-1 src                                  (first step of vmult, f2 = 1/theta: reads src, diag)
 //   FORM 1  x_{k+1} = x_k + f1 (x_k - x_{k-1}) + f2 D^-1 (src - t) (reads x, x_old, src, t, diag: 48 B/DoF, 40 without diag)
@@ -4630,10 +4656,18 @@ static __global__ void cg_record_kernel(const double *sc, const int *st, double 
 //   FORM 3  x_1     = x_0 + f2 D^-1 (src - t)                       (first step of step(): dst improved from its value)
 // x_new goes to x_old's buffer (pointer rotation by the host; FORM 0 / 3: a separate buffer).  NT: t and x_old are read for the last
 // time here -- non-temporal loads under the handle's streaming policy for once-used data (BP5_TUNE_UPDATE_NT, as cgm_update_kernel).
+// n_components = gridDim.y blocks in ONE launch (a scalar vector: gridDim.y = 1); all vectors ld apart, the inverse diagonal diag_ld apart: ld = a
+// block inverse diagonal, 0 = one scalar diagonal shared by all blocks
 template <int FORM, bool DIAG, bool NT>
-__global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const double *x, const double *x_old, const double *src, const double *t,
-                                                            const double *diag, size_t n, double f1, double f2)
+__global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const double *x, const double *x_old, const double *src,
+                                                            const double *t, const double *diag, size_t n, size_t ld, size_t diag_ld,
+                                                            double f1, double f2)
 {
+  const size_t o = blockIdx.y * ld;
+  x_new += o; src += o;
+  if constexpr (FORM != 0) { x += o; t += o; }
+  if constexpr (FORM == 1) x_old += o;
+  if constexpr (DIAG) diag += blockIdx.y * diag_ld;
   auto load = [](const double *p, bool nt) -> double2 {
     if (nt) { const bp5_d2u v = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(p)); return double2{v.x, v.y}; }
     return *reinterpret_cast<const double2 *>(p);
@@ -4655,7 +4689,7 @@ __global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const
         r.y = xv.y + f1x.y + f2 * (dg.y * (s.y - tv.y));
       }
       *reinterpret_cast<double2 *>(x_new + i) = r;
-    } else {
+    } else { // the odd tail entry
       const double dg = DIAG ? diag[i] : 1.0;
       if constexpr (FORM == 0) x_new[i] = f2 * (dg * src[i]);
       else {
@@ -4670,8 +4704,6 @@ __global__ void __launch_bounds__(VB) chebyshev_step_kernel(double *x_new, const
 // M[a][b] = phi_b^pc(xi_a^pf), (NF = pf+1) x (NC = pc+1), row-major.  One workgroup takes CPB cells; the tensor product M x M x M is
 // applied direction by direction through LDS (sum factorisation), one output entry per thread and stage.  Cell-local index
 // i + n (j + n k), x fastest, as local_to_global.
-// TWINS: every transfer kernel below (p and geometric, prolongate / restrict / combine) has a block-vector twin further down
-// (mg_*_components_kernel), stage for stage the same code, whose tests demand the same bits per block: a fix here has to be repeated there.
 template <int NF, int NC>
 struct MgShape {
   static constexpr int F3 = NF * NF * NF, C3 = NC * NC * NC;
@@ -4683,66 +4715,91 @@ constexpr uint32_t MG_NO_DOF = 0xffffffffu; // a coarse Dirichlet DoF in the tra
 
 // x_f += P e_c: the cell's coarse values (Dirichlet as 0), interpolated to its fine nodes; a fine DoF is written by the one cell whose
 // writer-mask bit is set (the first cell in handle order that holds it; owned DoFs only): plain read-modify-write, no atomics
+// A thread reads its coarse index and, per output entry, its writer-mask bit and fine index ONCE, then runs the components one after the other
+// through the SAME LDS tile.  MG_NO_DOF in gf: not this cell's to write
 template <int NF, int NC>
 __global__ void __launch_bounds__(256) mg_prolongate_kernel(const double *__restrict__ M, const uint32_t *__restrict__ cidx,
                                                             const uint32_t *__restrict__ fidx, const uint32_t *__restrict__ wmask,
-                                                            uint32_t n_cells, const double *__restrict__ src_c, double *__restrict__ dst_f)
+                                                            uint32_t n_cells, int n_components, size_t ld_c, const double *__restrict__ src_c,
+                                                            size_t ld_f, double *__restrict__ dst_f)
 {
   using S = MgShape<NF, NC>;
   constexpr int F3 = S::F3, C3 = S::C3, CPB = S::CPB;
+  constexpr int TIN = (CPB * C3 + 255) / 256, TOUT = (CPB * F3 + 255) / 256;
   __shared__ double sM[NF * NC];
   __shared__ double buf[CPB][S::LDS];
   const int t = threadIdx.x;
   const uint32_t c0 = blockIdx.x * CPB;
   for (int i = t; i < NF * NC; i += 256) sM[i] = M[i];
-  for (int e = t; e < CPB * C3; e += 256) {
-    const int cl = e / C3, r = e % C3;
-    const uint32_t c = c0 + cl;
-    double v = 0.0;
-    if (c < n_cells) {
-      const uint32_t g = cidx[(size_t)c * C3 + r];
-      v = g == MG_NO_DOF ? 0.0 : src_c[g];
+  uint32_t gc[TIN], gf[TOUT];
+#pragma unroll
+  for (int q = 0; q < TIN; ++q) {
+    const int e = t + 256 * q;
+    gc[q] = MG_NO_DOF;
+    if (e < CPB * C3 && c0 + e / C3 < n_cells) gc[q] = cidx[(size_t)(c0 + e / C3) * C3 + e % C3];
+  }
+#pragma unroll
+  for (int q = 0; q < TOUT; ++q) {
+    const int e = t + 256 * q;
+    gf[q] = MG_NO_DOF;
+    if (e < CPB * F3) {
+      const int r = e % F3;
+      const uint32_t c = c0 + e / F3;
+      if (c < n_cells && ((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) gf[q] = fidx[(size_t)c * F3 + r];
     }
-    buf[cl][r] = v;
   }
-  __syncthreads();
-  // x: s1[k][j][a] = sum_b M[a][b] s0[k][j][b]            (k, j < NC)
-  for (int e = t; e < CPB * NC * NC * NF; e += 256) {
-    const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), a = r % NF, kj = r / NF;
-    const double *s0 = buf[cl] + kj * NC;
-    double acc = 0.0;
+  for (int comp = 0; comp < n_components; ++comp) {
+    const double *src = src_c + (size_t)comp * ld_c;
+    double *dst = dst_f + (size_t)comp * ld_f;
 #pragma unroll
-    for (int b = 0; b < NC; ++b) acc += sM[a * NC + b] * s0[b];
-    buf[cl][C3 + r] = acc;
-  }
-  __syncthreads();
-  // y: s2[k][b][a] = sum_j M[b][j] s1[k][j][a]             (k < NC)
-  for (int e = t; e < CPB * NC * NF * NF; e += 256) {
-    const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), a = r % NF, b = (r / NF) % NF, k = r / (NF * NF);
-    const double *s1 = buf[cl] + C3;
-    double acc = 0.0;
+    for (int q = 0; q < TIN; ++q) {
+      const int e = t + 256 * q;
+      if (e < CPB * C3) buf[e / C3][e % C3] = gc[q] == MG_NO_DOF ? 0.0 : src[gc[q]];
+    }
+    __syncthreads();
+    // x: s1[k][j][a] = sum_b M[a][b] s0[k][j][b]            (k, j < NC)
+    for (int e = t; e < CPB * NC * NC * NF; e += 256) {
+      const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), a = r % NF, kj = r / NF;
+      const double *s0 = buf[cl] + kj * NC;
+      double acc = 0.0;
 #pragma unroll
-    for (int j = 0; j < NC; ++j) acc += sM[b * NC + j] * s1[(k * NC + j) * NF + a];
-    buf[cl][C3 + NC * NC * NF + r] = acc;
-  }
-  __syncthreads();
-  // z and write-out: x_f[l2g] += sum_k M[kk][k] s2[k][b][a] where this cell is the DoF's writer
-  for (int e = t; e < CPB * F3; e += 256) {
-    const int cl = e / F3, r = e % F3, ab = r % (NF * NF), kk = r / (NF * NF);
-    const uint32_t c = c0 + cl;
-    if (c >= n_cells || !((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) continue;
-    const double *s2 = buf[cl] + C3 + NC * NC * NF;
-    double acc = 0.0;
+      for (int b = 0; b < NC; ++b) acc += sM[a * NC + b] * s0[b];
+      buf[cl][C3 + r] = acc;
+    }
+    __syncthreads();
+    // y: s2[k][b][a] = sum_j M[b][j] s1[k][j][a]             (k < NC)
+    for (int e = t; e < CPB * NC * NF * NF; e += 256) {
+      const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), a = r % NF, b = (r / NF) % NF, k = r / (NF * NF);
+      const double *s1 = buf[cl] + C3;
+      double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < NC; ++k) acc += sM[kk * NC + k] * s2[k * NF * NF + ab];
-    const uint32_t g = fidx[(size_t)c * F3 + r];
-    dst_f[g] += acc;
+      for (int j = 0; j < NC; ++j) acc += sM[b * NC + j] * s1[(k * NC + j) * NF + a];
+      buf[cl][C3 + NC * NC * NF + r] = acc;
+    }
+    __syncthreads();
+    // z and write-out: x_f[l2g] += sum_k M[kk][k] s2[k][b][a] where this cell is the DoF's writer
+#pragma unroll
+    for (int q = 0; q < TOUT; ++q) {
+      const int e = t + 256 * q;
+      if (e >= CPB * F3 || gf[q] == MG_NO_DOF) continue;
+      const int cl = e / F3, r = e % F3, ab = r % (NF * NF), kk = r / (NF * NF);
+      const double *s2 = buf[cl] + C3 + NC * NC * NF;
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc += sM[kk * NC + k] * s2[k * NF * NF + ab];
+      dst[gf[q]] += acc;
+    }
+    __syncthreads(); // the tile is the next component's
   }
 }
 
 // the cell's share of P^T v:  slots[c][i] = (M^T x M^T x M^T)(w (b - t))|_cell, i < NC^3   (RESIDUAL false: w b, t not read).  w = 1 /
 // (number of cells that hold the DoF, all ranks): the slots of a coarse DoF summed give exactly (P^T v)_c.  No atomics: mg_combine_kernel
-// sums the slots in ascending order
+// sums the slots in ascending order.
+// The restriction alone keeps TWO bodies, this one for one component and mg_restrict_components_kernel below for more: as the n_components = 1
+// launch of the block form, and again as a build of it with the component loop folded away at compile time, the plain form <5, 3, false> ran
+// 3 % slower on a scalar vector than this kernel (profiles/transfer_unify/README.md, section 4).  Stage for stage the same code, whose tests
+// demand the same bits per block: a fix here has to be repeated there.
 template <int NF, int NC, bool RESIDUAL>
 __global__ void __launch_bounds__(256) mg_restrict_kernel(const double *__restrict__ M, const uint32_t *__restrict__ fidx, uint32_t n_cells,
                                                           const double *__restrict__ w, const double *__restrict__ b,
@@ -4799,295 +4856,8 @@ __global__ void __launch_bounds__(256) mg_restrict_kernel(const double *__restri
   }
 }
 
-// coarse DoF g: s = sum of its slots in ascending slot (= cell) order (Dirichlet DoFs have none: s = 0); ADD: owned rows dst += s, else
-// and on ghost rows dst = s (the ghost rows then travel to their owners by the scatter-add)
-template <bool ADD>
-__global__ void __launch_bounds__(256) mg_combine_kernel(const uint32_t *__restrict__ off, const uint32_t *__restrict__ slot_of,
-                                                         const double *__restrict__ slots, uint32_t n_owned, uint32_t n, double *__restrict__ dst)
-{
-  const uint32_t stride = gridDim.x * 256;
-  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n; g += stride) {
-    double s = 0.0;
-    for (uint32_t q = off[g]; q < off[g + 1]; ++q) s += slots[slot_of[q]];
-    if (ADD && g < n_owned) dst[g] += s;
-    else dst[g] = s;
-  }
-}
-
-// ---- geometric (h) transfer at one degree between a coarse parent and its 8 children (bp5_mg_transfer_create_geometric; deal.II
-// MGTwoLevelTransfer::reinit_geometric_transfer).  M[s][a][b] = phi_b(xi_a / 2 + s / 2), s = 0, 1, N x N each (N = p + 1).  pcode[c] =
-// parent << 3 | child of fine cell c (child = cx | cy << 1 | cz << 2); pidx: the Dirichlet-masked coarse index list of every coarse cell
-// (MG_NO_DOF: value 0).  The same sum factorisation, writer masks and slots as the p-transfer (MgShape<N, N>); every cell applies
-// M[cx] x M[cy] x M[cz]
-template <int N>
-__global__ void __launch_bounds__(256) mg_geo_prolongate_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pidx,
-                                                                const uint32_t *__restrict__ pcode, const uint32_t *__restrict__ fidx,
-                                                                const uint32_t *__restrict__ wmask, uint32_t n_cells,
-                                                                const double *__restrict__ src_c, double *__restrict__ dst_f)
-{
-  using S = MgShape<N, N>;
-  constexpr int N3 = S::F3, CPB = S::CPB;
-  __shared__ double sM[2 * N * N];
-  __shared__ double buf[CPB][S::LDS];
-  __shared__ uint32_t sch[CPB];
-  const int t = threadIdx.x;
-  const uint32_t c0 = blockIdx.x * CPB;
-  for (int i = t; i < 2 * N * N; i += 256) sM[i] = M[i];
-  for (int cl = t; cl < CPB; cl += 256) sch[cl] = c0 + cl < n_cells ? pcode[c0 + cl] & 7u : 0u;
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3;
-    const uint32_t c = c0 + cl;
-    double v = 0.0;
-    if (c < n_cells) {
-      const uint32_t g = pidx[(size_t)(pcode[c] >> 3) * N3 + r];
-      v = g == MG_NO_DOF ? 0.0 : src_c[g];
-    }
-    buf[cl][r] = v;
-  }
-  __syncthreads();
-  // x: s1[k][j][a] = sum_b Mx[a][b] s0[k][j][b]
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, a = r % N, kj = r / N;
-    const double *Mx = sM + (sch[cl] & 1u) * N * N, *s0 = buf[cl] + kj * N;
-    double acc = 0.0;
-#pragma unroll
-    for (int b = 0; b < N; ++b) acc += Mx[a * N + b] * s0[b];
-    buf[cl][N3 + r] = acc;
-  }
-  __syncthreads();
-  // y: s2[k][b][a] = sum_j My[b][j] s1[k][j][a]
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, a = r % N, b = (r / N) % N, k = r / (N * N);
-    const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) acc += My[b * N + j] * s1[(k * N + j) * N + a];
-    buf[cl][2 * N3 + r] = acc;
-  }
-  __syncthreads();
-  // z and write-out where this cell is the DoF's writer
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, ab = r % (N * N), kk = r / (N * N);
-    const uint32_t c = c0 + cl;
-    if (c >= n_cells || !((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) continue;
-    const double *Mz = sM + ((sch[cl] >> 2) & 1u) * N * N, *s2 = buf[cl] + 2 * N3;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc += Mz[kk * N + k] * s2[k * N * N + ab];
-    dst_f[fidx[(size_t)c * N3 + r]] += acc;
-  }
-}
-
-// the fine cell's share of P^T v in its slots: slots[c][i] = (Mx^T x My^T x Mz^T)(w (b - t))|_cell, i < N^3 (RESIDUAL false: w b);
-// mg_combine_kernel sums them per coarse DoF in cell order
-template <int N, bool RESIDUAL>
-__global__ void __launch_bounds__(256) mg_geo_restrict_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pcode,
-                                                              const uint32_t *__restrict__ fidx, uint32_t n_cells, const double *__restrict__ w,
-                                                              const double *__restrict__ b, const double *__restrict__ tv,
-                                                              double *__restrict__ slots)
-{
-  using S = MgShape<N, N>;
-  constexpr int N3 = S::F3, CPB = S::CPB;
-  __shared__ double sM[2 * N * N];
-  __shared__ double buf[CPB][S::LDS];
-  __shared__ uint32_t sch[CPB];
-  const int t = threadIdx.x;
-  const uint32_t c0 = blockIdx.x * CPB;
-  for (int i = t; i < 2 * N * N; i += 256) sM[i] = M[i];
-  for (int cl = t; cl < CPB; cl += 256) sch[cl] = c0 + cl < n_cells ? pcode[c0 + cl] & 7u : 0u;
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3;
-    const uint32_t c = c0 + cl;
-    double v = 0.0;
-    if (c < n_cells) {
-      const uint32_t g = fidx[(size_t)c * N3 + r];
-      v = w[g] * (RESIDUAL ? b[g] - tv[g] : b[g]);
-    }
-    buf[cl][r] = v;
-  }
-  __syncthreads();
-  // z: s1[k][j][i] = sum_kk Mz[kk][k] s0[kk][j][i]
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, ji = r % (N * N), k = r / (N * N);
-    const double *Mz = sM + ((sch[cl] >> 2) & 1u) * N * N, *s0 = buf[cl];
-    double acc = 0.0;
-#pragma unroll
-    for (int kk = 0; kk < N; ++kk) acc += Mz[kk * N + k] * s0[kk * N * N + ji];
-    buf[cl][N3 + r] = acc;
-  }
-  __syncthreads();
-  // y: s2[k][j][i] = sum_jj My[jj][j] s1[k][jj][i]
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, i = r % N, j = (r / N) % N, k = r / (N * N);
-    const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
-    double acc = 0.0;
-#pragma unroll
-    for (int jj = 0; jj < N; ++jj) acc += My[jj * N + j] * s1[(k * N + jj) * N + i];
-    buf[cl][2 * N3 + r] = acc;
-  }
-  __syncthreads();
-  // x: slot = sum_ii Mx[ii][i] s2[k][j][ii]
-  for (int e = t; e < CPB * N3; e += 256) {
-    const int cl = e / N3, r = e % N3, i = r % N, kj = r / N;
-    const uint32_t c = c0 + cl;
-    if (c >= n_cells) continue;
-    const double *Mx = sM + (sch[cl] & 1u) * N * N, *s2 = buf[cl] + 2 * N3;
-    double acc = 0.0;
-#pragma unroll
-    for (int ii = 0; ii < N; ++ii) acc += Mx[ii * N + i] * s2[kj * N + ii];
-    slots[(size_t)c * N3 + r] = acc;
-  }
-}
-
-// ---- block-vector forms of the pointwise and transfer kernels (the elasticity preconditioners: bp5_elasticity_chebyshev_create,
-// bp5_elasticity_mg_create, bp5_mg_transfer_*_components; instantiated in blockvec/bp5_blockvec.hip).  n_components blocks ld apart, padding
-// entries [n, ld) of a block never touched.  Per component every kernel performs exactly the floating-point operations of its scalar twin,
-// in the same order: the same bits as the scalar kernel on that block.
-// TWINS: these are copies of chebyshev_step_kernel, mg_prolongate_kernel, mg_restrict_kernel, mg_combine_kernel, mg_geo_prolongate_kernel and
-// mg_geo_restrict_kernel (kept beside them, not folded into them, so that the scalar kernels' code objects stay what they were): a fix to a scalar
-// kernel has to be repeated in its twin here, and the other way round.  (Follow-up: the scalar kernel as the n_components = 1 build.)
-
-// partial sums of x.y over the owned entries of all blocks: dot_kernel with the component as second grid dimension, columns as cg_dh_kernel
-// UnitTag: an empty tag type of the translation unit that launches the kernel (blockvec/bp5_blockvec.hip: BlockvecUnit); it selects nothing.  It
-// makes the kernel a template, so that only that unit instantiates it: a plain static kernel of this header lands in the code object of EVERY
-// unit that includes it (DESIGN 7j)
-struct BlockvecUnit {};
-template <class UnitTag>
-__global__ void __launch_bounds__(VB) dot_components_kernel(const double *x, const double *y, size_t n, size_t ld, double *partials)
-{
-  x += blockIdx.y * ld; y += blockIdx.y * ld;
-  double acc[1] = {0.0};
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      const double2 a = *reinterpret_cast<const double2 *>(x + i), b = *reinterpret_cast<const double2 *>(y + i);
-      acc[0] += a.x * b.x + a.y * b.y;
-    } else
-      acc[0] += x[i] * y[i];
-  }
-  block_reduce_store<1>(acc, partials + blockIdx.y * gridDim.x);
-}
-
-// chebyshev_step_kernel (its four FORMs, DIAG, NT) on n_components = gridDim.y blocks in ONE launch; all vectors ld apart, the inverse diagonal
-// diag_ld apart: ld = a block inverse diagonal, 0 = one scalar diagonal shared by all blocks
-template <int FORM, bool DIAG, bool NT>
-__global__ void __launch_bounds__(VB) chebyshev_step_components_kernel(double *x_new, const double *x, const double *x_old, const double *src,
-                                                                       const double *t, const double *diag, size_t n, size_t ld, size_t diag_ld,
-                                                                       double f1, double f2)
-{
-  const size_t o = blockIdx.y * ld;
-  x_new += o; src += o;
-  if constexpr (FORM != 0) { x += o; t += o; }
-  if constexpr (FORM == 1) x_old += o;
-  if constexpr (DIAG) diag += blockIdx.y * diag_ld;
-  auto load = [](const double *p, bool nt) -> double2 {
-    if (nt) { const bp5_d2u v = __builtin_nontemporal_load(reinterpret_cast<const bp5_d2u *>(p)); return double2{v.x, v.y}; }
-    return *reinterpret_cast<const double2 *>(p);
-  };
-  const size_t stride = (size_t)gridDim.x * VB * 2;
-  for (size_t i = ((size_t)blockIdx.x * VB + threadIdx.x) * 2; i < n; i += stride) {
-    if (i + 1 < n) {
-      const double2 s = load(src + i, false);
-      const double2 dg = DIAG ? load(diag + i, false) : double2{1.0, 1.0};
-      double2 r;
-      if constexpr (FORM == 0) {
-        r.x = f2 * (dg.x * s.x);
-        r.y = f2 * (dg.y * s.y);
-      } else {
-        const double2 tv = load(t + i, NT), xv = load(x + i, false);
-        const double2 xo = FORM == 1 ? load(x_old + i, NT) : double2{0.0, 0.0};
-        const double2 f1x = FORM == 3 ? double2{0.0, 0.0} : double2{f1 * (xv.x - xo.x), f1 * (xv.y - xo.y)};
-        r.x = xv.x + f1x.x + f2 * (dg.x * (s.x - tv.x));
-        r.y = xv.y + f1x.y + f2 * (dg.y * (s.y - tv.y));
-      }
-      *reinterpret_cast<double2 *>(x_new + i) = r;
-    } else { // the odd tail entry
-      const double dg = DIAG ? diag[i] : 1.0;
-      if constexpr (FORM == 0) x_new[i] = f2 * (dg * src[i]);
-      else {
-        const double xv = x[i], xo = FORM == 1 ? x_old[i] : 0.0;
-        x_new[i] = xv + (FORM == 3 ? 0.0 : f1 * (xv - xo)) + f2 * (dg * (src[i] - t[i]));
-      }
-    }
-  }
-}
-
-// mg_prolongate_kernel on block vectors: a thread reads its coarse index and, per output entry, its writer-mask bit and fine index ONCE, then
-// runs the components one after the other through the SAME LDS tile (the footprint of the scalar kernel).  MG_NO_DOF in gf: not this cell's to write
-template <int NF, int NC>
-__global__ void __launch_bounds__(256) mg_prolongate_components_kernel(const double *__restrict__ M, const uint32_t *__restrict__ cidx,
-                                                                       const uint32_t *__restrict__ fidx, const uint32_t *__restrict__ wmask,
-                                                                       uint32_t n_cells, int n_components, size_t ld_c, const double *__restrict__ src_c,
-                                                                       size_t ld_f, double *__restrict__ dst_f)
-{
-  using S = MgShape<NF, NC>;
-  constexpr int F3 = S::F3, C3 = S::C3, CPB = S::CPB;
-  constexpr int TIN = (CPB * C3 + 255) / 256, TOUT = (CPB * F3 + 255) / 256;
-  __shared__ double sM[NF * NC];
-  __shared__ double buf[CPB][S::LDS];
-  const int t = threadIdx.x;
-  const uint32_t c0 = blockIdx.x * CPB;
-  for (int i = t; i < NF * NC; i += 256) sM[i] = M[i];
-  uint32_t gc[TIN], gf[TOUT];
-#pragma unroll
-  for (int q = 0; q < TIN; ++q) {
-    const int e = t + 256 * q;
-    gc[q] = MG_NO_DOF;
-    if (e < CPB * C3 && c0 + e / C3 < n_cells) gc[q] = cidx[(size_t)(c0 + e / C3) * C3 + e % C3];
-  }
-#pragma unroll
-  for (int q = 0; q < TOUT; ++q) {
-    const int e = t + 256 * q;
-    gf[q] = MG_NO_DOF;
-    if (e < CPB * F3) {
-      const int r = e % F3;
-      const uint32_t c = c0 + e / F3;
-      if (c < n_cells && ((wmask[(size_t)c * S::WORDS + r / 32] >> (r & 31)) & 1u)) gf[q] = fidx[(size_t)c * F3 + r];
-    }
-  }
-  for (int comp = 0; comp < n_components; ++comp) {
-    const double *src = src_c + (size_t)comp * ld_c;
-    double *dst = dst_f + (size_t)comp * ld_f;
-#pragma unroll
-    for (int q = 0; q < TIN; ++q) {
-      const int e = t + 256 * q;
-      if (e < CPB * C3) buf[e / C3][e % C3] = gc[q] == MG_NO_DOF ? 0.0 : src[gc[q]];
-    }
-    __syncthreads();
-    for (int e = t; e < CPB * NC * NC * NF; e += 256) {
-      const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), a = r % NF, kj = r / NF;
-      const double *s0 = buf[cl] + kj * NC;
-      double acc = 0.0;
-#pragma unroll
-      for (int b = 0; b < NC; ++b) acc += sM[a * NC + b] * s0[b];
-      buf[cl][C3 + r] = acc;
-    }
-    __syncthreads();
-    for (int e = t; e < CPB * NC * NF * NF; e += 256) {
-      const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), a = r % NF, b = (r / NF) % NF, k = r / (NF * NF);
-      const double *s1 = buf[cl] + C3;
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < NC; ++j) acc += sM[b * NC + j] * s1[(k * NC + j) * NF + a];
-      buf[cl][C3 + NC * NC * NF + r] = acc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < TOUT; ++q) {
-      const int e = t + 256 * q;
-      if (e >= CPB * F3 || gf[q] == MG_NO_DOF) continue;
-      const int cl = e / F3, r = e % F3, ab = r % (NF * NF), kk = r / (NF * NF);
-      const double *s2 = buf[cl] + C3 + NC * NC * NF;
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) acc += sM[kk * NC + k] * s2[k * NF * NF + ab];
-      dst[gf[q]] += acc;
-    }
-    __syncthreads(); // the tile is the next component's
-  }
-}
-
-// mg_restrict_kernel on block vectors: fine index and weight read once per entry; slots [component][cell][NC^3] (slot_stride between components)
+// ... on block vectors: fine index and weight read once per entry, the components one after the other through the SAME LDS tile; slots
+// [component][cell][NC^3] (slot_stride between components)
 template <int NF, int NC, bool RESIDUAL>
 __global__ void __launch_bounds__(256) mg_restrict_components_kernel(const double *__restrict__ M, const uint32_t *__restrict__ fidx, uint32_t n_cells,
                                                                      const double *__restrict__ w, int n_components, size_t ld_f,
@@ -5119,6 +4889,7 @@ __global__ void __launch_bounds__(256) mg_restrict_components_kernel(const doubl
       if (e < CPB * F3) buf[e / F3][e % F3] = gf[q] == MG_NO_DOF ? 0.0 : wf[q] * (RESIDUAL ? bc[gf[q]] - tc[gf[q]] : bc[gf[q]]);
     }
     __syncthreads();
+    // z: s1[k][j][i] = sum_kk M[kk][k] s0[kk][j][i]          (k < NC)
     for (int e = t; e < CPB * NC * NF * NF; e += 256) {
       const int cl = e / (NC * NF * NF), r = e % (NC * NF * NF), ji = r % (NF * NF), k = r / (NF * NF);
       const double *s0 = buf[cl];
@@ -5128,6 +4899,7 @@ __global__ void __launch_bounds__(256) mg_restrict_components_kernel(const doubl
       buf[cl][F3 + r] = acc;
     }
     __syncthreads();
+    // y: s2[k][j][i] = sum_jj M[jj][j] s1[k][jj][i]          (k, j < NC)
     for (int e = t; e < CPB * NC * NC * NF; e += 256) {
       const int cl = e / (NC * NC * NF), r = e % (NC * NC * NF), i = r % NF, j = (r / NF) % NC, k = r / (NF * NC);
       const double *s1 = buf[cl] + F3;
@@ -5137,6 +4909,7 @@ __global__ void __launch_bounds__(256) mg_restrict_components_kernel(const doubl
       buf[cl][F3 + NC * NF * NF + r] = acc;
     }
     __syncthreads();
+    // x: slot = sum_ii M[ii][i] s2[k][j][ii]
     for (int e = t; e < CPB * C3; e += 256) {
       const int cl = e / C3, r = e % C3, i = r % NC, kj = r / NC;
       const uint32_t c = c0 + cl;
@@ -5151,11 +4924,12 @@ __global__ void __launch_bounds__(256) mg_restrict_components_kernel(const doubl
   }
 }
 
-// mg_combine_kernel on block vectors: the slot list of a coarse DoF is walked once per component, in the same ascending order
+// coarse DoF g: s = sum of its slots in ascending slot (= cell) order (Dirichlet DoFs have none: s = 0), the slot list walked once per component;
+// ADD: owned rows dst += s, else and on ghost rows dst = s (the ghost rows then travel to their owners by the scatter-add)
 template <bool ADD>
-__global__ void __launch_bounds__(256) mg_combine_components_kernel(const uint32_t *__restrict__ off, const uint32_t *__restrict__ slot_of,
-                                                                    const double *__restrict__ slots, size_t slot_stride, int n_components,
-                                                                    uint32_t n_owned, uint32_t n, size_t ld, double *__restrict__ dst)
+__global__ void __launch_bounds__(256) mg_combine_kernel(const uint32_t *__restrict__ off, const uint32_t *__restrict__ slot_of,
+                                                         const double *__restrict__ slots, size_t slot_stride, int n_components,
+                                                         uint32_t n_owned, uint32_t n, size_t ld, double *__restrict__ dst)
 {
   const uint32_t stride = gridDim.x * 256;
   for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n; g += stride) {
@@ -5171,13 +4945,17 @@ __global__ void __launch_bounds__(256) mg_combine_components_kernel(const uint32
   }
 }
 
-// the geometric twins (MgShape<N, N>): mg_geo_prolongate_kernel / mg_geo_restrict_kernel on block vectors, the same scheme
+// ---- geometric (h) transfer at one degree between a coarse parent and its 8 children (bp5_mg_transfer_create_geometric; deal.II
+// MGTwoLevelTransfer::reinit_geometric_transfer).  M[s][a][b] = phi_b(xi_a / 2 + s / 2), s = 0, 1, N x N each (N = p + 1).  pcode[c] =
+// parent << 3 | child of fine cell c (child = cx | cy << 1 | cz << 2); pidx: the Dirichlet-masked coarse index list of every coarse cell
+// (MG_NO_DOF: value 0).  The same sum factorisation, writer masks and slots as the p-transfer (MgShape<N, N>); every cell applies
+// M[cx] x M[cy] x M[cz]
 template <int N>
-__global__ void __launch_bounds__(256) mg_geo_prolongate_components_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pidx,
-                                                                           const uint32_t *__restrict__ pcode, const uint32_t *__restrict__ fidx,
-                                                                           const uint32_t *__restrict__ wmask, uint32_t n_cells, int n_components,
-                                                                           size_t ld_c, const double *__restrict__ src_c, size_t ld_f,
-                                                                           double *__restrict__ dst_f)
+__global__ void __launch_bounds__(256) mg_geo_prolongate_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pidx,
+                                                                const uint32_t *__restrict__ pcode, const uint32_t *__restrict__ fidx,
+                                                                const uint32_t *__restrict__ wmask, uint32_t n_cells, int n_components,
+                                                                size_t ld_c, const double *__restrict__ src_c, size_t ld_f,
+                                                                double *__restrict__ dst_f)
 {
   using S = MgShape<N, N>;
   constexpr int N3 = S::F3, CPB = S::CPB;
@@ -5210,6 +4988,7 @@ __global__ void __launch_bounds__(256) mg_geo_prolongate_components_kernel(const
       if (e < CPB * N3) buf[e / N3][e % N3] = gc[q] == MG_NO_DOF ? 0.0 : src[gc[q]];
     }
     __syncthreads();
+    // x: s1[k][j][a] = sum_b Mx[a][b] s0[k][j][b]
     for (int e = t; e < CPB * N3; e += 256) {
       const int cl = e / N3, r = e % N3, a = r % N, kj = r / N;
       const double *Mx = sM + (sch[cl] & 1u) * N * N, *s0 = buf[cl] + kj * N;
@@ -5219,6 +4998,7 @@ __global__ void __launch_bounds__(256) mg_geo_prolongate_components_kernel(const
       buf[cl][N3 + r] = acc;
     }
     __syncthreads();
+    // y: s2[k][b][a] = sum_j My[b][j] s1[k][j][a]
     for (int e = t; e < CPB * N3; e += 256) {
       const int cl = e / N3, r = e % N3, a = r % N, b = (r / N) % N, k = r / (N * N);
       const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
@@ -5228,6 +5008,7 @@ __global__ void __launch_bounds__(256) mg_geo_prolongate_components_kernel(const
       buf[cl][2 * N3 + r] = acc;
     }
     __syncthreads();
+    // z and write-out where this cell is the DoF's writer
 #pragma unroll
     for (int q = 0; q < TT; ++q) {
       const int e = t + 256 * q;
@@ -5243,11 +5024,13 @@ __global__ void __launch_bounds__(256) mg_geo_prolongate_components_kernel(const
   }
 }
 
+// the fine cell's share of P^T v in its slots: slots[c][i] = (Mx^T x My^T x Mz^T)(w (b - t))|_cell, i < N^3 (RESIDUAL false: w b);
+// mg_combine_kernel sums them per coarse DoF in cell order
 template <int N, bool RESIDUAL>
-__global__ void __launch_bounds__(256) mg_geo_restrict_components_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pcode,
-                                                                         const uint32_t *__restrict__ fidx, uint32_t n_cells, const double *__restrict__ w,
-                                                                         int n_components, size_t ld_f, const double *__restrict__ b,
-                                                                         const double *__restrict__ tv, size_t slot_stride, double *__restrict__ slots)
+__global__ void __launch_bounds__(256) mg_geo_restrict_kernel(const double *__restrict__ M, const uint32_t *__restrict__ pcode,
+                                                              const uint32_t *__restrict__ fidx, uint32_t n_cells, const double *__restrict__ w,
+                                                              int n_components, size_t ld_f, const double *__restrict__ b,
+                                                              const double *__restrict__ tv, size_t slot_stride, double *__restrict__ slots)
 {
   using S = MgShape<N, N>;
   constexpr int N3 = S::F3, CPB = S::CPB;
@@ -5276,6 +5059,7 @@ __global__ void __launch_bounds__(256) mg_geo_restrict_components_kernel(const d
       if (e < CPB * N3) buf[e / N3][e % N3] = gf[q] == MG_NO_DOF ? 0.0 : wf[q] * (RESIDUAL ? bc[gf[q]] - tc[gf[q]] : bc[gf[q]]);
     }
     __syncthreads();
+    // z: s1[k][j][i] = sum_kk Mz[kk][k] s0[kk][j][i]
     for (int e = t; e < CPB * N3; e += 256) {
       const int cl = e / N3, r = e % N3, ji = r % (N * N), k = r / (N * N);
       const double *Mz = sM + ((sch[cl] >> 2) & 1u) * N * N, *s0 = buf[cl];
@@ -5285,6 +5069,7 @@ __global__ void __launch_bounds__(256) mg_geo_restrict_components_kernel(const d
       buf[cl][N3 + r] = acc;
     }
     __syncthreads();
+    // y: s2[k][j][i] = sum_jj My[jj][j] s1[k][jj][i]
     for (int e = t; e < CPB * N3; e += 256) {
       const int cl = e / N3, r = e % N3, i = r % N, j = (r / N) % N, k = r / (N * N);
       const double *My = sM + ((sch[cl] >> 1) & 1u) * N * N, *s1 = buf[cl] + N3;
@@ -5294,6 +5079,7 @@ __global__ void __launch_bounds__(256) mg_geo_restrict_components_kernel(const d
       buf[cl][2 * N3 + r] = acc;
     }
     __syncthreads();
+    // x: slot = sum_ii Mx[ii][i] s2[k][j][ii]
     for (int e = t; e < CPB * N3; e += 256) {
       const int cl = e / N3, r = e % N3, i = r % N, kj = r / N;
       const uint32_t c = c0 + cl;

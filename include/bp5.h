@@ -707,7 +707,7 @@ int bp5_chebyshev_destroy(bp5_chebyshev *c);
  * BLOCK inverse diagonal as bp5_elasticity_compute_diagonal(..., invert = 1) returns it (three blocks ld apart), or NULL = identity; it must stay
  * valid for the life of the handle.  The result is an ordinary bp5_chebyshev: bp5_chebyshev_vmult, _step, _eigenvalues and _destroy take it, its
  * vectors are then three-block vectors of the ld given here (entries [n_owned + n_ghost, ld) never read, never written); each step is ONE launch of
- * the block form of the pointwise kernel (chebyshev_step_components_kernel: the component is the second grid dimension) and one
+ * the pointwise kernel (chebyshev_step_kernel: the component is the second grid dimension; a scalar handle launches it with one) and one
  * bp5_elasticity_apply.  The estimate is Jacobi-PCG on the stacked system (one Krylov space, the block diagonal) from the start vector
  * v_c[i] = ((3 id_i + c) mod 11) - 5, 0 on Dirichlet DoFs, id from params->start_ids_host (NULL: the local index).  Refusals: those of
  * bp5_elasticity_apply (bp5_last_error names "elasticity"), and bp5_chebyshev_create's on params. */
@@ -743,10 +743,11 @@ int bp5_mg_transfer_destroy(bp5_mg_transfer *t);
  * scalar transfer handles, p-transfers and geometric ones: index lists, writer masks and weights are per scalar DoF and shared by all components.
  * Component c of the fine vector at v + c * ld_fine, of the coarse vector at v + c * ld_coarse (layout as for bp5_apply_components: each ld even and
  * >= n_owned + n_ghost of its level, bases 16-byte aligned, entries [n_owned + n_ghost, ld) never read, never written).  ONE launch per direction
- * serves all components (mg_prolongate_components_kernel, mg_restrict_components_kernel + mg_combine_components_kernel): a thread reads its index,
- * writer-mask bit and weight once and runs the components one after the other through the same LDS tile; per component the floating-point
- * operations are the scalar kernel's in the scalar kernel's order, so every block holds the bits bp5_mg_transfer_prolongate_add / _restrict_add
- * give on that block alone.  Slots are [component][cell][(pc+1)^3]; a call with more components than any before it on the handle grows them
+ * serves all components (mg_prolongate_kernel and mg_combine_kernel, the kernels of the scalar entries, which launch them with one component;
+ * mg_restrict_components_kernel, the block form of the scalar entries' mg_restrict_kernel): a thread reads its index, writer-mask bit and weight
+ * once and runs the components one after the other through the same LDS tile; per component the floating-point operations and their order do not
+ * depend on the component count, and are those of the scalar restriction kernel, so every block holds the bits
+ * bp5_mg_transfer_prolongate_add / _restrict_add give on that block alone.  Slots are [component][cell][(pc+1)^3]; a call with more components than any before it on the handle grows them
  * (bp5_elasticity_mg_create reserves three).  n_components: 1 .. BP5_MAX_COMPONENTS.  Refused before any launch -- BP5_ERR_INVALID: null pointer,
  * n_components out of range, an odd or too small ld, a misaligned base; BP5_ERR_UNSUPPORTED: a transfer whose handles have a communicator and
  * neighbours (no block halo exchange here). */

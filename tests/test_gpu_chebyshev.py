@@ -50,16 +50,18 @@ class _PyOperator:
         self.op.vmult(dst, src)
 
 
-def _vmult_and_step_parity(op, A, n, seed):
+def _vmult_and_step_parity(op, A, n, seed, diagonal=True, bounds=(0.15, 2.1)):
+    """diagonal False: no preconditioner (AdditionalData.preconditioner None = identity; the step kernel's builds without a diagonal)"""
     torch = _t()
     dev = "cuda:0"
     inv = op.compute_diagonal(invert=True)
-    inv_np = inv.cpu().numpy()[:n]
+    inv_np = inv.cpu().numpy()[:n] if diagonal else np.ones(n)
     src = O.deterministic_src(n, seed=seed)
     x0 = O.deterministic_src(n, seed=seed + 100)
-    lo, hi = 0.15, 2.1
+    lo, hi = bounds
     for degree in (1, 2, 4, 6):
-        ch = Cheb().initialize(op, Cheb.AdditionalData(degree=degree, max_eigenvalue=hi, min_eigenvalue=lo, preconditioner=pkg.DiagonalMatrix(inv)))
+        ch = Cheb().initialize(op, Cheb.AdditionalData(degree=degree, max_eigenvalue=hi, min_eigenvalue=lo,
+                                                       preconditioner=pkg.DiagonalMatrix(inv) if diagonal else None))
         assert ch.estimated_eigenvalues()["max_used"] == hi and ch.estimated_eigenvalues()["min_used"] == lo
         dst = torch.full((op.mf_data.n_local,), 7.0, dtype=torch.float64, device=dev)       # prior content is ignored
         s = op.initialize_dof_vector()
@@ -85,6 +87,21 @@ def test_vmult_and_step_match_numpy_pencil_kernel(p, cells, quad):
     mesh = pkg.BrickMesh(p, cells, deform_amp=0.04)
     op = pkg.PoissonOperator(mesh, quad, pkg.COEF_STEP64)
     _vmult_and_step_parity(op, pr.vmult, mesh.n_owned, seed=p)
+
+
+def test_vmult_and_step_without_a_diagonal_on_an_odd_length():
+    """The step kernel's four forms (vmult: 0, 2, 1; step: 3, 1) in the builds without a diagonal, on a vector of odd length (n_owned = 9 * 7 * 7:
+    the kernel's scalar tail entry); with a diagonal the even-degree meshes above are odd lengths already.  The bounds are those of the UNSCALED
+    operator (20 numpy power iterations), in the ratio of the other tests, so that the polynomial is as well conditioned as theirs: 1e-12."""
+    p, cells = 2, (4, 3, 3)
+    pr = O.Problem(p, cells, 0, deform_amp=0.04, kappa=O.kappa_step64)
+    mesh = pkg.BrickMesh(p, cells, deform_amp=0.04)
+    assert mesh.n_owned % 2 == 1
+    v = O.deterministic_src(mesh.n_owned, seed=3)
+    for _ in range(20):
+        v = pr.vmult(v / np.linalg.norm(v))
+    hi = 1.2 * np.linalg.norm(v)
+    _vmult_and_step_parity(pkg.PoissonOperator(mesh, 0, pkg.COEF_STEP64), pr.vmult, mesh.n_owned, seed=11, diagonal=False, bounds=(hi / 14.0, hi))
 
 
 @pytest.mark.parametrize("quad", [0, 1])

@@ -79,7 +79,8 @@ def _inverse_diagonal(op, pad=float("nan")):
 
 
 # ------------------------------------------------------------------ 1. transfers on block vectors
-TRANSFERS = [("p", p, (3, 2, 2) if p <= 4 else (2, 2, 2)) for p in range(2, 9)] + [("h", 1, (4, 4, 4)), ("h", 2, (4, 4, 4))]
+TRANSFERS = ([("p", p, (3, 2, 2) if p <= 4 else (2, 2, 2)) for p in range(2, 9)] + [("h", 1, (4, 4, 4)), ("h", 2, (4, 4, 4))]
+             + [("h", 3, (2, 2, 2)), ("h", 4, (2, 2, 2))])        # (one coarse cell: 8 and 27 interior coarse DoFs)
 
 
 def _transfer(kind, p, cells):
@@ -89,12 +90,15 @@ def _transfer(kind, p, cells):
         coarse = pkg.PoissonOperator(pkg.BrickMesh(G.coarse_degree(p), cells, deform_amp=AMP), pkg.QUAD_GAUSS)
         return fine, coarse, pkg.MGTwoLevelTransfer(fine, coarse), G.Transfer(cells, p)
     mesh = pkg.BrickMesh(p, cells, deform_amp=AMP)
-    fine, coarse = pkg.PoissonOperator(mesh, pkg.QUAD_GAUSS), pkg.PoissonOperator(mesh.coarsen(2), pkg.QUAD_GAUSS)
+    fine, coarse = pkg.PoissonOperator(mesh, pkg.QUAD_GAUSS), pkg.PoissonOperator(mesh.coarsen(1), pkg.QUAD_GAUSS)    # (min_cells = 1: a one-cell coarse mesh is fine)
     return fine, coarse, pkg.MGTwoLevelTransfer(fine, coarse, geometric=True), H.GeometricTransfer(tuple(c // 2 for c in cells), p)
 
 
 @pytest.mark.parametrize("kind,p,cells", TRANSFERS)
 def test_block_transfers_give_the_bits_of_the_scalar_entries(kind, p, cells):
+    """The scalar and the block entries launch ONE kernel set (a scalar call is n_components = 1), so the ncomp = 1 leg compares a kernel with itself:
+    it pins the entry points' plumbing (slots, leading dimensions, padding).  What the test proves about the kernels is the ncomp = 3 leg -- the
+    component loop gives every block the bits of a one-component launch on it -- and the numpy, Dirichlet-row and adjointness assertions."""
     torch = _t()
     fine, coarse, tr, T = _transfer(kind, p, cells)
     nf, nc = fine.mf_data.n_local, coarse.mf_data.n_local
@@ -132,6 +136,55 @@ def test_block_transfers_give_the_bits_of_the_scalar_entries(kind, p, cells):
     assert rel(got_r[:, ~bc] - b0[:, ~bc], BT.restrict(rf)[:, ~bc]) < 1e-13
     lhs, rhs = np.sum((got_r - b0) * np.where(bc, 0.0, ec)), np.sum(rf * got_p)
     assert abs(lhs - rhs) <= 1e-13 * np.abs(rf).sum() * np.abs(ec).max() * 8
+    tr.clear()
+
+
+# p-transfer meshes whose cell count is no multiple of the cells per workgroup (MgShape::CPB = 9 / 4 / 2 at p = 2 / 3 / 4): (3, 1, 1) is three cells
+# in a workgroup with room for nine, for four, and a second half-empty one -- the `c < n_cells` guards of the preloaded-index kernels, with one
+# component and with three.  On (3, 1, 1) every coarse DoF of p = 2, 3 (coarse degree 1) lies on the boundary, so P e and the free rows of R r are
+# empty there and those cases can only show exact zeros; (3, 3, 2) at p = 3 (18 cells, the fifth workgroup half empty) adds a partial
+# workgroup with interior coarse DoFs.  p = 2 has one in TRANSFERS already ((3, 2, 2): 12 cells), p = 4 has 5 interior coarse DoFs on (3, 1, 1).
+PARTIAL = [(2, (3, 1, 1)), (3, (3, 1, 1)), (4, (3, 1, 1)), (3, (3, 3, 2))]
+
+
+@pytest.mark.parametrize("p,cells", PARTIAL)
+def test_transfers_on_a_partly_empty_last_workgroup_match_numpy(p, cells):
+    torch = _t()
+    fine, coarse, tr, T = _transfer("p", p, cells)
+    nf, nc = fine.mf_data.n_local, coarse.mf_data.n_local
+    assert fine.mf_data.mesh.n_cells == int(np.prod(cells)) and int(np.prod(cells)) % {2: 9, 3: 4, 4: 2}[p] != 0
+    rng = np.random.default_rng(300 + p)
+    ec, x0, rf, b0 = rng.uniform(-1, 1, (3, nc)), rng.uniform(-1, 1, (3, nf)), rng.uniform(-1, 1, (3, nf)), rng.uniform(-1, 1, (3, nc))
+    bc = T.boundary_c
+    BT = M.BlockTransfer(T)
+    ref_p, ref_r = BT.prolongate(ec), BT.restrict(rf)
+
+    def check(got_x, got_b, rows):
+        """1e-13 relative to the numpy transfer as in the test above; where the reference is empty or exactly zero, exactly that"""
+        got_p, free = got_x - x0[rows], got_b[:, ~bc] - b0[rows][:, ~bc]
+        if np.any(ref_p[rows]):
+            assert rel(got_p, ref_p[rows]) < 1e-13
+        else:
+            assert not np.any(got_p)
+        if np.any(ref_r[rows][:, ~bc]):
+            assert rel(free, ref_r[rows][:, ~bc]) < 1e-13
+        else:
+            assert not np.any(free)
+        assert np.array_equal(got_b[:, bc], b0[rows][:, bc])
+
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to("cuda:0")
+    for c in range(3):                                         # the scalar entries
+        x, b = dev(x0[c]), dev(b0[c])
+        tr.prolongate_and_add(x, dev(ec[c]))
+        tr.restrict_and_add(b, dev(rf[c]))
+        check(x.cpu().numpy()[None], b.cpu().numpy()[None], slice(c, c + 1))
+    for ncomp in (1, 3):                                       # the block entries
+        x, e, b, r = block(x0[:ncomp], nf), block(ec[:ncomp], nc), block(b0[:ncomp], nc), block(rf[:ncomp], nf)
+        tr.prolongate_and_add_components(x, e)
+        tr.restrict_and_add_components(b, r)
+        check(x[:, :nf].cpu().numpy(), b[:, :nc].cpu().numpy(), slice(0, ncomp))
+        for t, n in ((x, nf), (e, nc), (b, nc), (r, nf)):
+            assert padding_is(t, n), "padding touched"
     tr.clear()
 
 

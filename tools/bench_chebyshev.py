@@ -11,7 +11,7 @@
 
 Driver (default): runs every leg in a fresh child process under `timeout -k 10 <limit>` and stops at the first leg that fails; one JSON
 line per leg on stdout, all of them in <out>/bench_chebyshev.json.
-  python tools/bench_chebyshev.py [--cells 116 116 120] [--out bench_out]
+  python tools/bench_chebyshev.py [--cells 116 116 120] [--legs vmult] [--out bench_out]
 """
 import argparse
 import json
@@ -116,6 +116,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--leg", choices=sorted(LEGS), help="run one leg in this process (the driver's child)")
     ap.add_argument("--cells", type=int, nargs=3, default=[116, 116, 120])
+    ap.add_argument("--legs", nargs="+", choices=sorted(LEGS), default=list(LEGS), help="the driver's legs (default: all)")
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out"))
     args = ap.parse_args()
     if args.leg:
@@ -124,7 +125,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     results = []
     prof_dir = os.path.join(os.path.abspath(args.out), "bench_chebyshev_prof")
-    for name, limit in LEGS.items():
+    for name, limit in ((k, v) for k, v in LEGS.items() if k in args.legs):
         leg_cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--cells"] + [str(c) for c in args.cells]
         profiled = name == "vmult" and shutil.which("rocprofv3") is not None
         if profiled:   # kernel statistics only: no counter collection, no other tracing

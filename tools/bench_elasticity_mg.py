@@ -5,8 +5,8 @@
   solves      per mesh: iterations and solve time of (a) SolverCG + the block inverse diagonal, (b) SolverCG + one V-cycle per iteration over
               make_elasticity_mg_hierarchy(op, h_levels="max"); and the ms of one preconditioner application by level: the V-cycle that starts
               at level l (torch events around --reps applications) minus the one that starts at level l + 1
-  step kernel chebyshev_step_components_kernel (three blocks in one launch) against chebyshev_step_kernel on a scalar vector of about the same
-              total length: a degree-1 polynomial with given bounds is ONE launch of the step kernel (x = D^-1 src / theta: 24 bytes per entry) and
+  step kernel chebyshev_step_kernel on three blocks in one launch (gridDim.y = 3) against the same kernel on a scalar vector (gridDim.y = 1) of about
+              the same total length: a degree-1 polynomial with given bounds is ONE launch of the step kernel (x = D^-1 src / theta: 24 bytes per entry) and
               no operator application; alternating legs, GB/s of each and their ratio
 
 usage: python tools/bench_elasticity_mg.py                    # p = 4 on 16^3 and 32^3, p = 2 on 32^3 and 64^3 (8e5 ... 6.4e6 three-component DoFs)
