@@ -3352,6 +3352,27 @@ extern "C" int bp5_mg_transfer_create(bp5_mf *fine, bp5_mf *coarse, bp5_mg_trans
           }
   }
   HIP_TRY(hipSetDevice(fine->device));
+  // ... in the same local frame: a consistent pairing does not say so (a column of cells turned about its axis in one handle pairs up too), the
+  // geometry does -- corner (i, j, k) of every cell has the same coordinates in both handles (to 1e-12 of the cell's size)
+  {
+    std::vector<double> xf(nlf * 3), xc(nlc * 3);
+    HIP_TRY(hipStreamSynchronize(fine->stream));
+    if (!xf.empty()) HIP_TRY(hipMemcpy(xf.data(), fine->d_coords, xf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (!xc.empty()) HIP_TRY(hipMemcpy(xc.data(), coarse->d_coords, xc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (uint32_t c = 0; c < ncell; ++c) {
+      const uint32_t *lf = &fine->h_l2g[(size_t)c * f3], *lc = &coarse->h_l2g[(size_t)c * c3];
+      const double *a = &xc[3 * (size_t)lc[0]], *z = &xc[3 * (size_t)lc[c3 - 1]];
+      const double size = std::sqrt((z[0] - a[0]) * (z[0] - a[0]) + (z[1] - a[1]) * (z[1] - a[1]) + (z[2] - a[2]) * (z[2] - a[2]));
+      for (int q = 0; q < 8; ++q) {
+        const int i = q & 1, j = (q >> 1) & 1, k = q >> 2;
+        const double *Xf = &xf[3 * (size_t)lf[i * (nf - 1) + nf * (j * (nf - 1) + nf * k * (nf - 1))]];
+        const double *Xc = &xc[3 * (size_t)lc[i * (nc - 1) + nc * (j * (nc - 1) + nc * k * (nc - 1))]];
+        for (int e = 0; e < 3; ++e)
+          if (!(std::fabs(Xf[e] - Xc[e]) <= 1e-12 * size))
+            return fail(BP5_ERR_INVALID, "multigrid transfer: cell " + std::to_string(c) + " does not sit in the same local frame in the two handles (the coordinates of its corners differ)");
+      }
+    }
+  }
   std::unique_ptr<bp5_mg_transfer> t(new bp5_mg_transfer);
   MgTransferGuard guard{t.get()};
   t->fine = fine; t->coarse = coarse; t->pf = fine->degree; t->pc = coarse->degree;

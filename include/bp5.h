@@ -722,8 +722,11 @@ int bp5_tridiagonal_eigenvalues(int n, const double *diag, const double *offdiag
  * smoothers (step-37), coarsening in the polynomial degree on the same cells.
  *
  * Transfer between a fine handle of degree pf >= 2 and a coarse handle of degree pc = max(1, pf / 2) on the SAME cells in the same
- * order (two bp5_mesh_create_brick meshes that differ only in degree; checked through the cells' corner DoFs), the same communicator
- * and stream.  M[a][b] = phi_b^pc(xi_a^pf) (FE_Q nodes of bp5_shape_tables; its end rows exact unit vectors); P = M x M x M cell by cell,
+ * order AND the same local frames (two bp5_mesh_create_brick meshes that differ only in degree, or two user meshes whose cell c lists
+ * its entries along the same three axes in both), the same communicator and stream.  Checked at create (BP5_ERR_INVALID, the reason
+ * names the first offending cell): the cells' corner DoFs pair up one to one, and corner (i, j, k) of every cell has the same coordinates
+ * in both handles to 1e-12 of the cell's size -- the pairing alone cannot tell a column of cells that one handle lists turned about its
+ * axis.  M[a][b] = phi_b^pc(xi_a^pf) (FE_Q nodes of bp5_shape_tables; its end rows exact unit vectors); P = M x M x M cell by cell,
  * with the coarse Dirichlet DoFs taken as 0:
  *   prolongate_add  dst_f += P src_c: each cell interpolates its coarse values to its fine nodes; every owned fine DoF is written by ONE
  *                   cell (the first in handle order that holds it): no atomics, no race.  With neighbours the coarse ghosts are gathered
