@@ -13,7 +13,7 @@ _LIB = None
 QUAD_GAUSS, QUAD_GLL, QUAD_GAUSS_OVER = 0, 1, 2     # bp5.h: BP5_QUAD_*; GAUSS_OVER: Gauss(p+2), CEED BP1 - BP4
 COEF_ONE, COEF_STEP64 = 0, 1
 CG_PLAIN, CG_MERGED = 0, 1
-GEOM_MERGED6, GEOM_AFFINE = 0, 1
+GEOM_MERGED6, GEOM_AFFINE, GEOM_TRILINEAR = 0, 1, 2
 OP_POISSON, OP_HELMHOLTZ, OP_MASS = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 MAX_COMPONENTS = 8          # bp5.h: BP5_MAX_COMPONENTS

@@ -186,7 +186,7 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   hipStreamSynchronize(mf->stream);
   void *ptrs[] = {mf->d_constrained_bits, mf->d_l2g, mf->d_constrained, mf->d_send_idx, mf->d_coords, mf->d_tab, mf->d_tab_gauss, mf->d_l2g_padded,
                   mf->d_constraint_mask, mf->d_inv_jac, mf->d_JxW, mf->d_qpoints, mf->d_sendbuf, mf->d_recvbuf, mf->d_partials,
-                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->wsz_base, mf->hc_base, mf->d_hc_off};
+                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_vertices, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->wsz_base, mf->hc_base, mf->d_hc_off};
   for (void *p : ptrs) if (p) hipFree(p);
   if (mf->h_sc) hipHostFree(mf->h_sc);
   if (mf->h_st) hipHostFree(mf->h_st);
@@ -245,6 +245,7 @@ extern "C" int bp5_mf_set_metric_precision(bp5_mf *mf, int precision)
     if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: meshes with hanging nodes keep double planes");
     if (mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the Helmholtz operator keeps double planes");
     if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the mass operator keeps its double plane");
+    if (mf->trilinear()) return trilinear_refuse("FP32 metric planes are not supported (the mode reads no plane)");
     if (mf->geometry_mode == BP5_GEOM_AFFINE) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes: the affine geometry mode has no six-plane stream to shrink");
     if (mf->apply_variant != 0 && mf->apply_variant != 56) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes run apply variants 0 (pencil kernel) and 56 (block kernel)");
   }
@@ -261,6 +262,8 @@ extern "C" int bp5_mf_get_metric_precision(const bp5_mf *mf, int *precision)
 extern "C" int bp5_mf_set_operator(bp5_mf *mf, int op)
 {
   if (!mf || (op != BP5_OP_POISSON && op != BP5_OP_HELMHOLTZ && op != BP5_OP_MASS)) return fail(BP5_ERR_INVALID, "unknown operator");
+  if (op == BP5_OP_HELMHOLTZ && mf->trilinear()) return trilinear_refuse("the Helmholtz operator is not supported (Poisson operator only)");
+  if (op == BP5_OP_MASS && mf->trilinear()) return trilinear_refuse("the mass operator is not supported (Poisson operator only)");
   if (op == BP5_OP_HELMHOLTZ && mf->overint()) return overint_refuse("the Helmholtz operator is not supported (Poisson and mass operator only)");
   if (op == BP5_OP_HELMHOLTZ && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator keeps double metric planes (bp5_mf_set_metric_precision)");
   if (op == BP5_OP_HELMHOLTZ && (mf->has_hanging || mf->geometry_mode == BP5_GEOM_AFFINE))
@@ -301,6 +304,7 @@ static bool product_variant(int degree, int v)
 extern "C" int bp5_mf_set_apply_variant(bp5_mf *mf, int v)
 {
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
+  if (mf->trilinear() && v != 0) return trilinear_refuse("only apply variant 0, the pencil kernel apply_pencil_trilinear_kernel (no block, team or march build)");
   if (mf->overint() && v != 0) return overint_refuse("only apply variant 0, the pencil kernel apply_pencil_q_kernel / apply_pencil_mass_q_kernel (no block, team or march build)");
   if (mf->has_hanging) { // 0: the library decides; 56: block kernel (deterministic; needs cell blocks); 90: pencil kernel with atomics (any mesh)
     if (v != 0 && v != 90 && !(v == 56 && block_lpc(mf->degree) != 0)) return fail(BP5_ERR_UNSUPPORTED, "meshes with hanging nodes run apply variants 90 (pencil kernel) and 56 (block kernel)");
@@ -405,8 +409,36 @@ static int geometry_dispatch(bp5_mf *mf, GeomOut o)
 extern "C" int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode)
 {
   if (!mf) return fail(BP5_ERR_INVALID, "null handle");
-  if (mode != BP5_GEOM_MERGED6 && mode != BP5_GEOM_AFFINE) return fail(BP5_ERR_INVALID, "unknown geometry mode");
+  if (mode != BP5_GEOM_MERGED6 && mode != BP5_GEOM_AFFINE && mode != BP5_GEOM_TRILINEAR) return fail(BP5_ERR_INVALID, "unknown geometry mode");
   HIP_TRY(hipSetDevice(mf->device));
+  if (mode == BP5_GEOM_TRILINEAR) {
+    if (mf->overint()) return trilinear_refuse("Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER) is not supported");
+    if (mf->operator_kind == BP5_OP_HELMHOLTZ) return trilinear_refuse("the Helmholtz operator is not supported (Poisson operator only)");
+    if (mf->operator_kind == BP5_OP_MASS) return trilinear_refuse("the mass operator is not supported (Poisson operator only)");
+    if (mf->has_hanging) return trilinear_refuse("meshes with hanging nodes are not supported");
+    if (mf->f32_metric()) return trilinear_refuse("FP32 metric planes are not supported (the mode reads no plane)");
+    if (mf->apply_variant != 0) return trilinear_refuse("only apply variant 0, the pencil kernel apply_pencil_trilinear_kernel (no block, team or march build)");
+    if (!mf->d_vertices) { // the cells' corners, and the check that every node is the trilinear image of its reference position
+      double *vx = nullptr, *dev = nullptr;
+      HIP_TRY(hipMalloc((void **)&vx, std::max<size_t>(24 * (size_t)mf->n_cells, 1) * sizeof(double)));
+      HIP_TRY(hipMalloc((void **)&dev, std::max<size_t>(mf->n_cells, 1) * sizeof(double)));
+      int st = trilinear_setup(mf, vx, dev);
+      std::vector<double> h(mf->n_cells);
+      if (st == BP5_OK && hipMemcpyAsync(h.data(), dev, mf->n_cells * sizeof(double), hipMemcpyDeviceToHost, mf->stream) != hipSuccess) st = BP5_ERR_HIP;
+      if (st == BP5_OK && hipStreamSynchronize(mf->stream) != hipSuccess) st = BP5_ERR_HIP;
+      hipFree(dev);
+      double worst = 0.0;
+      for (double v : h) worst = std::max(worst, v);
+      if (st != BP5_OK || !(worst <= 1e-10)) { // (the affine mode's threshold: rounding noise is ~eps |x| / h, real curvature orders larger)
+        hipFree(vx);
+        if (st != BP5_OK) return fail(st, "trilinear geometry setup failed");
+        return fail(BP5_ERR_UNSUPPORTED, "mesh is not trilinear (a node is off the trilinear image of its cell's vertices): use BP5_GEOM_MERGED6");
+      }
+      mf->d_vertices = vx;
+    }
+    mf->geometry_mode = mode;
+    return BP5_OK;
+  }
   if (mode == BP5_GEOM_AFFINE && mf->overint()) return overint_refuse("the affine geometry mode is not supported");
   if (mode == BP5_GEOM_AFFINE && mf->f32_metric()) return fail(BP5_ERR_UNSUPPORTED, "FP32 metric planes need the six-plane geometry (the affine mode has no six-plane stream to shrink)");
   if (mode == BP5_GEOM_AFFINE && mf->operator_kind == BP5_OP_HELMHOLTZ) return fail(BP5_ERR_UNSUPPORTED, "the Helmholtz operator needs the six-plane geometry");
@@ -500,6 +532,7 @@ extern "C" int bp5_mf_get_data(bp5_mf *mf, int color, bp5_mf_data *out)
 {
   if (!mf || !out) return fail(BP5_ERR_INVALID, "null argument");
   if (color != 0) return fail(BP5_ERR_INVALID, "this build keeps all cells in one colour");
+  if (mf->trilinear()) return trilinear_refuse("bp5_mf_get_data (the unmerged geometry at the quadrature points) is not supported");
   if (mf->overint()) return overint_refuse("bp5_mf_get_data (the unmerged geometry at the quadrature points) is not supported");
   HIP_TRY(hipSetDevice(mf->device));
   if (!mf->d_inv_jac) {
@@ -1124,6 +1157,7 @@ static int effective_variant(bp5_mf *mf, uint32_t c0, uint32_t c1)
 {
   const int v = mf->apply_variant;
   if (v != 0) return v;
+  if (mf->trilinear()) return 0; // the trilinear pencil kernel whatever the mesh, brick-ordered ones included: no block, team or march build computes the metric
   if (mf->overint()) return 0; // the pencil kernel whatever the mesh: no block, team or march build reads Q^3 points (so no fused dot products either)
   if (mf->has_hanging && mf->geometry_mode == BP5_GEOM_AFFINE) return 90;
   uint32_t b0, b1;
@@ -1184,7 +1218,7 @@ static int launch_apply(bp5_mf *mf, const double *coef, const double *src, doubl
 
 extern "C" int bp5_apply_cells(bp5_mf *mf, const double *coef, const double *src, double *dst, uint32_t c0, uint32_t c1)
 {
-  if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
   if (c1 > mf->n_cells || c0 > c1) return fail(BP5_ERR_INVALID, "cell range out of bounds");
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst must differ");
   HIP_TRY(hipSetDevice(mf->device));
@@ -1210,7 +1244,7 @@ extern "C" int bp5_set_constrained(bp5_mf *mf, double value, double *dst)
 }
 extern "C" int bp5_apply(bp5_mf *mf, const double *coef, const double *src, double *dst, int zero_dst)
 {
-  if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst must differ");
   HIP_TRY(hipSetDevice(mf->device));
   BP5_TRY(launch_apply(mf, coef, src, dst, 0, mf->n_cells, zero_dst != 0));
@@ -1244,6 +1278,7 @@ static int components_check(const bp5_mf *mf, const double *coef, int n_componen
   if (mf->operator_kind == BP5_OP_MASS) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the mass operator is not supported");
   if (mf->operator_kind != BP5_OP_POISSON) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the Helmholtz operator is not supported");
   if (mf->has_hanging) return fail(BP5_ERR_UNSUPPORTED, "block vectors: meshes with hanging nodes are not supported");
+  if (mf->trilinear()) return trilinear_refuse("block vectors are not supported");
   if (mf->geometry_mode != BP5_GEOM_MERGED6) return fail(BP5_ERR_UNSUPPORTED, "block vectors: the affine geometry mode is not supported");
   if (!with_exchange && mf->has_neighbors()) return fail(BP5_ERR_UNSUPPORTED, "block vectors: no halo exchange (a handle with a communicator and neighbours)");
   if (!coef) return fail(BP5_ERR_INVALID, "null argument");
@@ -1313,6 +1348,7 @@ static int elasticity_handle_check(const bp5_mf *mf)
   if (mf->overint()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER) is not supported");
   if (mf->operator_kind != BP5_OP_POISSON) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "a handle of the Helmholtz or mass operator class is not supported (Poisson class only)");
   if (mf->has_hanging) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "meshes with hanging nodes are not supported");
+  if (mf->trilinear()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "the trilinear geometry mode (BP5_GEOM_TRILINEAR) is not supported");
   if (mf->geometry_mode != BP5_GEOM_MERGED6) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "the affine geometry mode is not supported");
   if (mf->f32_metric()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "FP32 metric planes are not supported");
   if (mf->has_neighbors()) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "no halo exchange (a handle with a communicator and neighbours)");
@@ -1441,10 +1477,10 @@ static int diagonal_dispatch(bp5_mf *mf, const double *coef, double *diag)
 }
 extern "C" int bp5_compute_diagonal(bp5_mf *mf, const double *coef, double *diag, int invert)
 {
-  if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !diag) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !diag) return fail(BP5_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(mf->device));
   HIP_TRY(hipMemsetAsync(diag, 0, mf->n_local() * sizeof(double), mf->stream));
-  if (mf->n_cells) BP5_TRY(mf->overint() ? overint_diagonal(mf, coef, diag) : diagonal_dispatch(mf, coef, diag));
+  if (mf->n_cells) BP5_TRY(mf->trilinear() ? trilinear_diagonal(mf, diag) : mf->overint() ? overint_diagonal(mf, coef, diag) : diagonal_dispatch(mf, coef, diag));
   if (mf->has_neighbors()) { // ghost contributions to their owners
     BP5_TRY(bp5_halo_scatter_add(mf, diag));
     BP5_TRY(bp5_halo_zero_ghosts(mf, diag));
@@ -1958,7 +1994,7 @@ static int apply_overlapped(bp5_mf *mf, ApplyCall &call, const double *coef, dou
 }
 extern "C" int bp5_apply_distributed(bp5_mf *mf, const double *coef, double *src, double *dst, int zero_dst)
 {
-  if (!mf || (!coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !src || !dst) return fail(BP5_ERR_INVALID, "null argument");
   if (src == dst) return fail(BP5_ERR_INVALID, "src and dst must differ");
   HIP_TRY(hipSetDevice(mf->device));
   if (mf->has_neighbors()) {
@@ -2879,7 +2915,7 @@ static int cg_solve_merged(bp5_mf *mf, const double *coef, bp5_vmult_fn user, vo
 static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void *user_ctx, const double *diag, const double *b, double *x,
                          const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr, int history_cap = 0)
 {
-  if (!mf || (!user && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!user && !coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
   if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
   if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return fail(BP5_ERR_INVALID, "unknown CG variant");
   if (!aligned16(b) || !aligned16(x) || (diag && !aligned16(diag))) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
@@ -3014,7 +3050,7 @@ extern "C" int bp5_cg_solve_elasticity_preconditioned(bp5_mf *mf, const double *
 extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, bp5_vmult_fn precond, void *precond_ctx,
                                            const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
-  if (!mf || (!vmult && !coef && mf->geometry_mode != BP5_GEOM_AFFINE) || !precond || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || (!vmult && !coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !precond || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
   if (prm->variant != BP5_CG_PLAIN) return fail(BP5_ERR_INVALID, "a general preconditioner needs BP5_CG_PLAIN (SolverCGFullMerge takes a diagonal only)");
   if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
   if (!aligned16(b) || !aligned16(x)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
@@ -3081,7 +3117,7 @@ static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, co
 static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag, const bp5_chebyshev_params *prm,
                                  bp5_chebyshev **out, size_t el_ld = 0, double lambda = 0.0, double mu = 0.0)
 {
-  if (!mf || !prm || !out || (!vmult && !coef && mf->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "null argument");
+  if (!mf || !prm || !out || (!vmult && !coef && mf->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "null argument");
   *out = nullptr;
   if (prm->degree < 1) return fail(BP5_ERR_INVALID, "Chebyshev degree < 1");
   const bool given = prm->max_eigenvalue > 0.0 && prm->min_eigenvalue > 0.0;
@@ -3626,7 +3662,7 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   *out = nullptr;
   if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return fail(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
   for (int l = 0; l < n_levels; ++l) {
-    if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode != BP5_GEOM_AFFINE)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
+    if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
     if (mfs[l]->stream != mfs[0]->stream) return fail(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
     if (mfs[l]->overint()) return overint_refuse("multigrid levels are not supported");
   }

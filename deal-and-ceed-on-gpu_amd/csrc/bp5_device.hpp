@@ -73,6 +73,8 @@ struct bp5_mf {
   int auto_team = -1;  // -1 not decided; 1: the x-row team plan could be built (p = 1, 3 default)
   int auto_block = -1; // -1 not decided; 1: the caller's cell blocks fit three block-kernel workgroups per CU
   double *d_scalar_plane = nullptr, *d_gcell = nullptr;
+  double *d_vertices = nullptr; // BP5_GEOM_TRILINEAR: [n_cells][24], each cell's eight corners (bp5_mf_set_geometry_mode allocates it on first use)
+  bool trilinear() const { return geometry_mode == BP5_GEOM_TRILINEAR; }
   hipStream_t stream = nullptr;
   bool own_stream = false;
   Tables tab, tab_gauss;
@@ -334,6 +336,16 @@ int overint_diagonal(bp5_mf *mf, const double *coef, double *diag);
 int overint_to_reference_layout(bp5_mf *mf, const double *coef, double *coef_ref);
 // the reason an over-integrated handle refuses something with (BP5_ERR_UNSUPPORTED)
 inline int overint_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED, std::string("Gauss(p+2) quadrature (BP5_QUAD_GAUSS_OVER): ") + what); }
+
+// The trilinear handle (BP5_GEOM_TRILINEAR), defined in trilinear/bp5_trilinear.hip -- a translation unit of its own, off the per-degree units, in a
+// directory of its own (its ISA is kept beside it): the operator (refuses every variant but the pencil kernel and every class but Poisson; reads no
+// metric array), the setup launch (the cells' corners and the per-cell deviation from their trilinear image) and the diagonal (contributions of the
+// cells; the caller has zeroed diag)
+int trilinear_apply(bp5_mf *mf, ApplyCall &call, const double *src, double *dst);
+int trilinear_setup(bp5_mf *mf, double *vertices, double *deviation);
+int trilinear_diagonal(bp5_mf *mf, double *diag);
+// the reason a trilinear handle refuses something with (BP5_ERR_UNSUPPORTED)
+inline int trilinear_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED, std::string("trilinear geometry mode (BP5_GEOM_TRILINEAR): ") + what); }
 
 // Linear elasticity (bp5_elasticity_*), defined in elasticity/bp5_elasticity.hip -- a translation unit of its own, off the per-degree units, in a
 // directory of its own (its ISA is kept beside it): the ten planes, the coupled three-component operator over the cells [c0, c1) (accumulates;
@@ -905,6 +917,7 @@ int apply_degree_impl(bp5_mf *mf, ApplyCall &call, const double *coef, const dou
   const bool coll = mf->quadrature == BP5_QUAD_GLL;
   const bool affine = mf->geometry_mode == BP5_GEOM_AFFINE;
   if (c1 <= c0) return overwrite ? zero_dst(mf, dst) : BP5_OK; // the empty range, for every operator and variant
+  if (mf->trilinear()) return trilinear_apply(mf, call, src, dst); // the metric from the cells' vertices: kernels of its own, Poisson class, coef is not read
   if (mf->overint()) return overint_apply(mf, call, coef, src, dst); // Gauss(p+2) points: kernels, tables and planes of its own, Poisson and mass class
   if (mf->f32_metric()) {
     // FP32 metric planes (bp5_mf_set_metric_precision): the BLK_F32M builds of what the dispatch picks for an unfused application of the Poisson

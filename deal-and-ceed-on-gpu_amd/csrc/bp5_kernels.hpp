@@ -5527,4 +5527,332 @@ __global__ void __launch_bounds__((n + 1) * (n + 1) * (n + 1)) overint_diagonal_
   }
 }
 
+// ------------------------------------------------------------------------------------ trilinear geometry (BP5_GEOM_TRILINEAR; deal.II MappingQ1)
+// A straight-sided hex cell is the trilinear image of its eight vertices, V[v][e] with v = a + 2 b + 4 c the corner (xi, eta, zeta) = (a, b, c): 24 doubles
+// per cell instead of six planes.  With (eta, zeta) fixed the map is affine in xi, x = x0 + xi dx/dxi, and so is its Jacobian, J = A + xi B, where the
+// xi column is constant: 18 numbers per pencil.  Every coefficient is a convex combination of vertex or edge differences -- no alternating sum over the
+// eight corners -- so the rounding error stays the eps |x| / h of the stored planes.
+typedef double bp5_d2a __attribute__((ext_vector_type(2))); // 16-byte load from a 16-byte aligned address
+template <int n>
+struct TrilinearRule { // by value: the 1-D points and weights of the rule (the setup check: the nodes) and the handle's BP5_COEF_* function
+  double x[n], w[n];
+  int kappa_mode;
+};
+template <int n>
+struct TrilinearArg { // the operator kernel's tables: ShapeArg's N and D (the same packing) and the rule
+  double N[n * n];
+  double D[n * n];
+  TrilinearRule<n> rule;
+};
+struct TrilinearPencil {
+  double A[3][3]; // J[e][d] = dx_e / dxi_d at xi = 0
+  double B[3][2]; // its slope along xi in the columns d = 1, 2
+  double x0[3];   // x at xi = 0
+};
+__device__ __forceinline__ void trilinear_pencil(const double (&V)[24], double eta, double zeta, TrilinearPencil &p)
+{
+  const double e0 = 1.0 - eta, z0 = 1.0 - zeta;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+#define VX(a, b, c) V[3 * ((a) + 2 * (b) + 4 * (c)) + e]
+    p.x0[e] = z0 * (e0 * VX(0, 0, 0) + eta * VX(0, 1, 0)) + zeta * (e0 * VX(0, 0, 1) + eta * VX(0, 1, 1));
+    p.A[e][0] = z0 * (e0 * (VX(1, 0, 0) - VX(0, 0, 0)) + eta * (VX(1, 1, 0) - VX(0, 1, 0))) + zeta * (e0 * (VX(1, 0, 1) - VX(0, 0, 1)) + eta * (VX(1, 1, 1) - VX(0, 1, 1)));
+    const double f0 = z0 * (VX(0, 1, 0) - VX(0, 0, 0)) + zeta * (VX(0, 1, 1) - VX(0, 0, 1)), f1 = z0 * (VX(1, 1, 0) - VX(1, 0, 0)) + zeta * (VX(1, 1, 1) - VX(1, 0, 1));
+    const double g0 = e0 * (VX(0, 0, 1) - VX(0, 0, 0)) + eta * (VX(0, 1, 1) - VX(0, 1, 0)), g1 = e0 * (VX(1, 0, 1) - VX(1, 0, 0)) + eta * (VX(1, 1, 1) - VX(1, 1, 0));
+#undef VX
+    p.A[e][1] = f0; p.B[e][0] = f1 - f0;
+    p.A[e][2] = g0; p.B[e][1] = g1 - g0;
+  }
+}
+// The point formula, the ONE place the operator kernel, the diagonal kernel and the setup check take a point from: x at xi on the pencil, and (G != NULL)
+// the six entries kappa(x) JxW K K^T of geometry_kernel's planes, JxW = |det J| w3 -- the adjugate, one reciprocal, kkt6
+__device__ __forceinline__ void trilinear_point(const TrilinearPencil &p, double xi, double w3, int kappa_mode, double (&x)[3], double (*G)[6])
+{
+#pragma unroll
+  for (int e = 0; e < 3; ++e) x[e] = fma(xi, p.A[e][0], p.x0[e]);
+  if (!G) return;
+  double J[3][3], C[3][3];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    J[e][0] = p.A[e][0];
+    J[e][1] = fma(xi, p.B[e][0], p.A[e][1]);
+    J[e][2] = fma(xi, p.B[e][1], p.A[e][2]);
+  }
+  C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1]; C[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2]; C[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+  C[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2]; C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0]; C[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+  C[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0]; C[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1]; C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+  const double det = J[0][0] * C[0][0] + J[0][1] * C[1][0] + J[0][2] * C[2][0];
+  // K = C / det, JxW = |det| w3: kappa JxW K K^T = (kappa w3 / |det|) C C^T
+  const double s = kappa_eval(kappa_mode, x[0], x[1], x[2]) * w3 * (1.0 / fabs(det));
+  kkt6(C, *G);
+#pragma unroll
+  for (int c = 0; c < 6; ++c) (*G)[c] *= s;
+}
+
+// The operator on a trilinear handle: apply_pencil_kernel at the degree's DefaultPencil shape -- lanes, tiles, contractions, mirrored idle lanes, cell
+// range, XCD remap and atomic scatter are its -- but the x-owner lane loads no plane: it reads its cell's 24 vertex coordinates (a.coef, a.cell_stride = 24;
+// twelve 16-byte loads at one address per cell, 1.5 cache lines), forms its pencil's 18 numbers once and a point's six inside the quadrature-point loop
+template <int P, bool COLL, int TW, int LPC, int TPB>
+__global__ void __launch_bounds__(64 * TW * TPB) apply_pencil_trilinear_kernel(ApplyArgs a, TrilinearArg<P + 1> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= n2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  using L = LdsLayout<n, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // (the XCD remap of apply_pencil_kernel)
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < n2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  // idle lanes mirror a valid lane: every load below is unconditional and in bounds; only LDS writes and the final atomics are predicated
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < n2 ? ab : ab % n2;
+  const int a_ = abm % n, b_ = abm / n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * L::CS;
+#define TL(f, k, j, i) T[(f) * (n * L::PS) + (k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- gather (z-owner: a_ = i, b_ = j; registers hold k)
+  uint32_t idx[n];
+  double u[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+#pragma unroll
+  for (int k = 0; k < n; ++k) u[k] = a.src[idx[k]];
+
+  // ---- the pencil's geometry (x-owner: a_ = j, b_ = k; the quadrature-point loop walks i)
+  TrilinearPencil pen;
+  {
+    double V[24];
+    const bp5_d2a *vc = reinterpret_cast<const bp5_d2a *>(a.coef + cell * a.cell_stride);
+#pragma unroll
+    for (int m = 0; m < 12; ++m) {
+      const bp5_d2a v = vc[m];
+      V[2 * m] = v.x;
+      V[2 * m + 1] = v.y;
+    }
+    trilinear_pencil(V, sh.rule.x[a_], sh.rule.x[b_], pen);
+  }
+  const double wjk = sh.rule.w[a_] * sh.rule.w[b_];
+
+  double g0[n], g1[n], g2[n];
+  if constexpr (!COLL) {
+    // z-pass in registers
+    double aN[n], aD[n];
+    MV_N(sh.N, u, aN);
+    MV_D(sh.D, u, aD);
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = aN[k]; TL(1, k, b_, a_) = aD[k]; }
+    }
+    team_sync<TW>();
+    // y-owner: a_ = i, b_ = k
+    double vN[n], vD[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) { vN[j] = TL(0, b_, j, a_); vD[j] = TL(1, b_, j, a_); }
+    double c1[n], c2[n], c3[n];
+    MV_N(sh.N, vN, c1);
+    MV_D(sh.D, vN, c2);
+    MV_N(sh.N, vD, c3);
+    team_sync<TW>();
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = c1[j]; TL(1, b_, j, a_) = c2[j]; TL(2, b_, j, a_) = c3[j]; }
+    }
+    team_sync<TW>();
+    // x-owner: a_ = j, b_ = k
+    double r1[n], r2[n], r3[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      r1[i] = TL(0, b_, a_, i);
+      r2[i] = TL(1, b_, a_, i);
+      r3[i] = TL(2, b_, a_, i);
+    }
+    MV_D(sh.D, r1, g0);
+    MV_N(sh.N, r2, g1);
+    MV_N(sh.N, r3, g2);
+  } else {
+    // collocation: g0 = Dx u, g1 = Dy u, g2 = Dz u
+    double gz[n];
+    MV_D(sh.D, u, gz);
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = u[k]; TL(2, k, b_, a_) = gz[k]; }
+    }
+    team_sync<TW>();
+    double vN[n], c2[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) vN[j] = TL(0, b_, j, a_);
+    MV_D(sh.D, vN, c2);
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < n; ++j) TL(1, b_, j, a_) = c2[j];
+    }
+    team_sync<TW>();
+    double r1[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      r1[i] = TL(0, b_, a_, i);
+      g1[i] = TL(1, b_, a_, i);
+      g2[i] = TL(2, b_, a_, i);
+    }
+    MV_D(sh.D, r1, g0);
+  }
+
+  // ---- quadrature-point operation: t = S ghat, S = kappa JxW K K^T from the pencil's A + xi_i B
+#pragma unroll
+  for (int i = 0; i < n; ++i) {
+    double xq[3], S[6];
+    trilinear_point(pen, sh.rule.x[i], sh.rule.w[i] * wjk, sh.rule.kappa_mode, xq, &S);
+    const double x0 = g0[i], x1 = g1[i], x2 = g2[i];
+    g0[i] = S[0] * x0 + S[3] * x1 + S[4] * x2;
+    g1[i] = S[3] * x0 + S[1] * x1 + S[5] * x2;
+    g2[i] = S[4] * x0 + S[5] * x1 + S[2] * x2;
+  }
+
+  // ---- integrate (transpose sequence)
+  double y[n];
+  if constexpr (!COLL) {
+    double e1[n], e2[n], e3[n];
+    MV_DT(sh.D, g0, e1);
+    MV_NT(sh.N, g1, e2);
+    MV_NT(sh.N, g2, e3);
+    team_sync<TW>();
+    if (active) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = e2[i]; TL(2, b_, a_, i) = e3[i]; }
+    }
+    team_sync<TW>();
+    double w1[n], w2[n], w3[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      w1[j] = TL(0, b_, j, a_);
+      w2[j] = TL(1, b_, j, a_);
+      w3[j] = TL(2, b_, j, a_);
+    }
+    double f1[n], f2[n];
+    MV_NT(sh.N, w1, f1);
+    MV_DT_ADD(sh.D, w2, f1);
+    MV_NT(sh.N, w3, f2);
+    team_sync<TW>();
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = f1[j]; TL(1, b_, j, a_) = f2[j]; }
+    }
+    team_sync<TW>();
+    double z1[n], z2[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) { z1[k] = TL(0, k, b_, a_); z2[k] = TL(1, k, b_, a_); }
+    MV_NT(sh.N, z1, y);
+    MV_DT_ADD(sh.D, z2, y);
+  } else {
+    double e1[n];
+    MV_DT(sh.D, g0, e1);
+    team_sync<TW>();
+    if (active) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = g1[i]; TL(2, b_, a_, i) = g2[i]; }
+    }
+    team_sync<TW>();
+    double w1[n], w2[n];
+#pragma unroll
+    for (int j = 0; j < n; ++j) { w1[j] = TL(0, b_, j, a_); w2[j] = TL(1, b_, j, a_); }
+    MV_DT_ADD(sh.D, w2, w1);
+    if (active) { // each y-owner lane rewrites only the column it has just read
+#pragma unroll
+      for (int j = 0; j < n; ++j) TL(0, b_, j, a_) = w1[j];
+    }
+    team_sync<TW>();
+    double z2[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) { y[k] = TL(0, k, b_, a_); z2[k] = TL(2, k, b_, a_); }
+    MV_DT_ADD(sh.D, z2, y);
+  }
+
+  // ---- scatter-add
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) atomic_add_f64(a.dst + idx[k], y[k]);
+  }
+#undef TL
+}
+
+// Setup of a trilinear handle, one cell per workgroup and one thread per node: writes the cell's eight corners (its local entries (0|p, 0|p, 0|p)) to
+// vertices[cell][24] and checks the mesh -- deviation[cell] = the largest distance, over the cell's n^3 nodes, between the stored node and the trilinear
+// image of its reference position (nodes.x: the 1-D node positions), over the cell's shortest edge
+template <int n>
+__global__ void __launch_bounds__(n *n *n) trilinear_setup_kernel(const uint32_t *l2g, const double *coords, TrilinearRule<n> nodes, uint32_t n_cells, double *vertices,
+                                                                 double *deviation)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double Vs[24], dist[n3];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    const uint32_t g = l2g[cell * n3 + q];
+    double X[3];
+    for (int e = 0; e < 3; ++e) X[e] = coords[3 * (uint64_t)g + e];
+    if ((i == 0 || i == n - 1) && (j == 0 || j == n - 1) && (k == 0 || k == n - 1)) {
+      const int v = (i ? 1 : 0) + 2 * (j ? 1 : 0) + 4 * (k ? 1 : 0);
+      for (int e = 0; e < 3; ++e) Vs[3 * v + e] = X[e];
+    }
+    __syncthreads();
+    double V[24];
+    for (int m = 0; m < 24; ++m) V[m] = Vs[m];
+    for (int m = q; m < 24; m += n3) vertices[cell * 24 + m] = Vs[m];
+    TrilinearPencil pen;
+    trilinear_pencil(V, nodes.x[j], nodes.x[k], pen);
+    double x[3];
+    trilinear_point(pen, nodes.x[i], 0.0, 0, x, nullptr);
+    dist[q] = sqrt((X[0] - x[0]) * (X[0] - x[0]) + (X[1] - x[1]) * (X[1] - x[1]) + (X[2] - x[2]) * (X[2] - x[2]));
+    __syncthreads();
+    if (q == 0) {
+      double worst = 0.0, shortest = INFINITY;
+      for (int m = 0; m < n3; ++m) worst = fmax(worst, dist[m]);
+      for (int d = 0; d < 3; ++d) // the four edges along direction d
+        for (int v = 0; v < 8; ++v) {
+          if (v & (1 << d)) continue;
+          const double *p0 = Vs + 3 * v, *p1 = Vs + 3 * (v | (1 << d));
+          shortest = fmin(shortest, sqrt((p1[0] - p0[0]) * (p1[0] - p0[0]) + (p1[1] - p0[1]) * (p1[1] - p0[1]) + (p1[2] - p0[2]) * (p1[2] - p0[2])));
+        }
+      deviation[cell] = worst / shortest;
+    }
+    __syncthreads(); // Vs, dist are rewritten for the next cell
+  }
+}
+
+// diag(A) of a trilinear handle: the arithmetic of diagonal_kernel, one thread per local DoF, with the six entries of this thread's quadrature point
+// (a, b, c) = (i, j, k) from trilinear_point instead of the planes
+template <int n>
+__global__ void __launch_bounds__(n *n *n) trilinear_diagonal_kernel(const uint32_t *l2g, const double *vertices, TrilinearRule<n> rule, const double *tab, uint32_t n_cells,
+                                                                    double *diag)
+{
+  constexpr int n2 = n * n, n3 = n2 * n;
+  __shared__ double S[n3], t1[n3], t2[n3], NN[n2], DD[n2], ND[n2];
+  const int i = threadIdx.x, j = threadIdx.y, k = threadIdx.z;
+  const int q = i + n * (j + n * k);
+  diag_products<n>(tab, NN, DD, ND);
+  for (uint64_t cell = blockIdx.x; cell < n_cells; cell += gridDim.x) {
+    double V[24], xq[3], G[6];
+    for (int m = 0; m < 24; ++m) V[m] = vertices[cell * 24 + m];
+    TrilinearPencil pen;
+    trilinear_pencil(V, rule.x[j], rule.x[k], pen);
+    trilinear_point(pen, rule.x[i], rule.w[i] * rule.w[j] * rule.w[k], rule.kappa_mode, xq, &G);
+    double acc = 0.0;
+    for (int c = 0; c < 6; ++c) {
+      S[q] = G[c];
+      __syncthreads();
+      acc += diag_plane_term<n>(c, NN, DD, ND, S, t1, t2, i, j, k);
+    }
+    atomic_add_f64(diag + l2g[cell * n3 + q], acc);
+  }
+}
+
 } // namespace bp5

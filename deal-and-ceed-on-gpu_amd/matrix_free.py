@@ -158,7 +158,8 @@ class MatrixFree:
         self.stream = stream
 
     def set_geometry_mode(self, mode):
-        """BP5_GEOM_MERGED6 (reference representation, default) or BP5_GEOM_AFFINE (affine meshes)."""
+        """BP5_GEOM_MERGED6 (reference representation, default), BP5_GEOM_AFFINE (affine meshes) or BP5_GEOM_TRILINEAR (straight-sided
+        meshes, deal.II's MappingQ1: the metric from the cells' vertices inside the operator kernel)."""
         _lib.check(_lib.lib().bp5_mf_set_geometry_mode(self.handle, int(mode)))
 
     def set_overlap(self, mode=True):
@@ -324,7 +325,7 @@ class PoissonOperator:
         self.metric_precision = metric_precision
         if metric_precision != "float64":         # "float32": float planes, double arithmetic (MatrixFree.set_metric_precision)
             self.mf_data.set_metric_precision(metric_precision)
-        if geometry == _lib.GEOM_AFFINE:          # per-cell metric + one scalar plane, no 6-plane array at all
+        if geometry in (_lib.GEOM_AFFINE, _lib.GEOM_TRILINEAR):   # per-cell metric + one scalar plane / the cells' vertices: no 6-plane array at all
             self.mf_data.set_geometry_mode(geometry)
             self.coef = None
         else:

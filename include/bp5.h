@@ -294,8 +294,23 @@ int bp5_mf_compute_merged_metric(bp5_mf *mf, double *coef);
  *                     cubes, bp5/step-64.cu:656-663): K K^T is constant per cell, so the library keeps six
  *                     doubles per CELL and one scalar plane kappa*JxW per q-point (G = 1).  Same operator,
  *                     same results to rounding; the `coef` argument of apply/solve is then ignored.
- *                     Fails with BP5_ERR_UNSUPPORTED if K K^T varies by more than 1e-10 (relative) inside a cell. */
-enum { BP5_GEOM_MERGED6 = 0, BP5_GEOM_AFFINE = 1 };
+ *                     Fails with BP5_ERR_UNSUPPORTED if K K^T varies by more than 1e-10 (relative) inside a cell.
+ *   BP5_GEOM_TRILINEAR for straight-sided hex meshes, every cell the trilinear image of its eight vertices (deal.II's
+ *                     default mapping MappingQ1 / MappingQGeneric(1); what hex mesh generators write): the library
+ *                     keeps 24 doubles per CELL (its corners, the local entries (0|p, 0|p, 0|p)) and the operator
+ *                     kernel apply_pencil_trilinear_kernel computes kappa JxW K K^T at every q-point from them
+ *                     (G = 0: no plane is read).  Same operator, same results to rounding; the `coef` argument of
+ *                     apply / solve / diagonal / preconditioner entries may be NULL and is not read.  Runs
+ *                     bp5_apply, bp5_apply_cells, bp5_apply_distributed, bp5_compute_diagonal, every bp5_cg_solve*
+ *                     entry of scalar vectors (dot_products_fused = 0), bp5_chebyshev_create and bp5_mg_create levels.
+ *                     Fails with BP5_ERR_UNSUPPORTED "mesh is not trilinear" if a node lies further than 1e-10 (relative
+ *                     to the cell's shortest edge) from the trilinear image of its reference position; the handle
+ *                     then stays in its previous mode.  BP5_ERR_UNSUPPORTED naming "trilinear", decided before any
+ *                     launch and in either order of the two calls: BP5_OP_HELMHOLTZ, BP5_OP_MASS, BP5_QUAD_GAUSS_OVER,
+ *                     hanging-node masks, BP5_METRIC_F32, every apply variant other than 0 (bp5_mf_get_apply_variant
+ *                     reports 0 on brick meshes too), bp5_mf_get_data, bp5_apply_components* / bp5_cg_solve_components*
+ *                     and the bp5_elasticity_* entries. */
+enum { BP5_GEOM_MERGED6 = 0, BP5_GEOM_AFFINE = 1, BP5_GEOM_TRILINEAR = 2 };
 int bp5_mf_set_geometry_mode(bp5_mf *mf, int mode);
 /* permute to the reference layout [c][cell][qi + n(qj + n qk)] (tests / interop); coef_ref: 6 n_cells (p+1)^3 DOUBLES in either precision
  * (BP5_OP_HELMHOLTZ: 7 planes; BP5_OP_MASS: the one plane as [cell][q]; BP5_QUAD_GAUSS_OVER: [c][cell][qi + Q (qj + Q qk)], Q = p + 2) */
