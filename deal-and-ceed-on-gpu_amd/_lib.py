@@ -88,6 +88,16 @@ class CGResult(C.Structure):
                 ("exchange_schedule", C.c_int), ("apply_kernel", C.c_char * 96), ("phase_ms", C.c_double * 8)]
 
 
+class NewtonParams(C.Structure):
+    _fields_ = [("max_newton", C.c_int), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("cg", CGParams), ("cg_rel_tol", C.c_double),
+                ("max_backtracks", C.c_int)]
+
+
+class NewtonResult(C.Structure):
+    _fields_ = [("newton_iterations", C.c_int), ("total_cg_iterations", C.c_int), ("residual_history", C.c_double * 32), ("backtracks", C.c_int),
+                ("status", C.c_int)]
+
+
 VMULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)   # bp5_vmult_fn(ctx, dst, src)
 
 
@@ -200,6 +210,12 @@ def lib():
         "bp5_elasticity_compute_diagonal": (i32, [vp, vp, f64, f64, sz, vp, i32]),
         "bp5_cg_solve_elasticity": (i32, [vp, vp, f64, f64, sz, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
         "bp5_cg_solve_elasticity_preconditioned": (i32, [vp, vp, f64, f64, sz, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_hyperelasticity_state_size": (i32, [vp, C.POINTER(sz)]),
+        "bp5_hyperelasticity_residual": (i32, [vp, vp, vp, f64, f64, sz, vp, vp, i32]),
+        "bp5_hyperelasticity_apply": (i32, [vp, vp, vp, f64, f64, sz, vp, vp, i32]),
+        "bp5_hyperelasticity_apply_cells": (i32, [vp, vp, vp, f64, f64, sz, vp, vp, u32, u32]),
+        "bp5_cg_solve_hyperelasticity": (i32, [vp, vp, vp, f64, f64, sz, vp, vp, vp, vp, C.POINTER(CGParams), C.POINTER(CGResult)]),
+        "bp5_hyperelasticity_newton": (i32, [vp, vp, vp, f64, f64, sz, vp, vp, vp, vp, C.POINTER(NewtonParams), C.POINTER(NewtonResult)]),
         "bp5_elasticity_chebyshev_create": (i32, [vp, vp, f64, f64, sz, vp, C.POINTER(ChebyshevParams), C.POINTER(vp)]),
         "bp5_elasticity_mg_create": (i32, [i32, vp, vp, f64, f64, sz, vp, C.POINTER(MGParams), C.POINTER(vp)]),
         "bp5_mg_transfer_prolongate_add_components": (i32, [vp, i32, sz, vp, sz, vp]),

@@ -186,7 +186,7 @@ extern "C" int bp5_mf_destroy(bp5_mf *mf)
   hipStreamSynchronize(mf->stream);
   void *ptrs[] = {mf->d_constrained_bits, mf->d_l2g, mf->d_constrained, mf->d_send_idx, mf->d_coords, mf->d_tab, mf->d_tab_gauss, mf->d_l2g_padded,
                   mf->d_constraint_mask, mf->d_inv_jac, mf->d_JxW, mf->d_qpoints, mf->d_sendbuf, mf->d_recvbuf, mf->d_partials,
-                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_vertices, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->wsz_base, mf->hc_base, mf->d_hc_off};
+                  mf->d_sc, mf->d_scalar, mf->d_st, mf->ws_base, mf->d_stamps, mf->d_evec, mf->d_scalar_plane, mf->d_gcell, mf->d_vertices, mf->d_hang_mask, mf->d_hang_I, mf->d_send_dirichlet, mf->d_signal, mf->ws_z, mf->wsc_base, mf->wsz_base, mf->wsn_base, mf->hc_base, mf->d_hc_off};
   for (void *p : ptrs) if (p) hipFree(p);
   if (mf->h_sc) hipHostFree(mf->h_sc);
   if (mf->h_st) hipHostFree(mf->h_st);
@@ -2619,6 +2619,7 @@ struct PlainCG {
   // elasticity: the block operator is the coupled three-component one (coef: its ten planes; lambda, mu by value)
   bool elasticity = false;
   double lambda = 0.0, mu = 0.0;
+  const double *hyper_state = nullptr; // ... or, with the ten state planes of bp5_hyperelasticity_residual, the neo-Hookean tangent at that state
   // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g -- on scalar vectors (bp5_cg_solve_preconditioned) or on
   // block vectors of the solve's n_components and ld (bp5_cg_solve_elasticity_preconditioned); z is laid out like g (scalar: ws_z; block:
   // wsz_base, block_cg_workspace_z).  diag_ld: doubles between the diagonals of two components -- 0: ONE scalar diagonal applied to every block;
@@ -2657,6 +2658,7 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
   OperatorPlan op;
   if (!cg.block && !cg.precond) BP5_TRY(plan_operator(mf, !cg.user, true, ss, op));
   else op.schedule = cg.user || !mf->has_neighbors() ? 0 : overlap_wanted(mf) ? 3 : 1;
+  std::string operator_kernel; // block vectors with a callback preconditioner: the name of the solve's OWN operator kernel, for the result
   // h = A d, Dirichlet rows included (unless the dot-product kernel copies them).  Fused dot products: d.h lies in *n_cols columns of d_partials
   auto apply_A = [&](uint32_t *n_cols) -> int {
     if (cg.user) return user_vmult(prof, cg.user, cg.user_ctx, d, h);
@@ -2664,9 +2666,11 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     BP5_TRY(prof.mark(0));
     BP5_TRY(components_zero(mf, nc, ld, h));
     BP5_TRY(prof.mark(1));
-    if (cg.elasticity) BP5_TRY(elasticity_apply_cells(mf, cg.coef, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
+    if (cg.hyper_state) BP5_TRY(hyperelasticity_apply_cells(mf, cg.coef, cg.hyper_state, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
+    else if (cg.elasticity) BP5_TRY(elasticity_apply_cells(mf, cg.coef, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
     else if (cg.exchange) BP5_TRY(components_apply_exchanged(mf, cg.coef, nc, ld, d, h, false));
     else BP5_TRY(components_apply(mf, cg.coef, nc, ld, d, h, false));
+    if (cg.precond) operator_kernel = mf->last_apply_kernel; // (a preconditioner on the same handle launches operator kernels of its own)
     BP5_TRY(prof.mark(2));
     BP5_TRY(components_copy_constrained(mf, nc, ld, d, h));
     BP5_TRY(prof.mark(3));
@@ -2748,6 +2752,7 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
       }
     }
   }
+  if (!operator_kernel.empty()) snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "%s", operator_kernel.c_str());
   return solve_finish(mf, prof, op.fused_dots, op.schedule, !cg.user, res);
 }
 
@@ -3044,6 +3049,161 @@ extern "C" int bp5_cg_solve_elasticity_preconditioned(bp5_mf *mf, const double *
 {
   if (!precond) return elasticity_refuse(BP5_ERR_INVALID, "null argument (the preconditioner's vmult callback)");
   return cg_solve_elasticity_impl(mf, coef, lambda, mu, ld, nullptr, precond, precond_ctx, b, x, prm, res);
+}
+
+// ------------------------------------------------------------------------------------ neo-Hookean hyperelasticity (residual, tangent, Newton)
+// The vectors, the handle and the geometry planes are the elasticity operator's, and so is every refusal: its checks run as they are and their
+// reason ("elasticity: ...") is handed on under this operator's name
+static int hyperelasticity_refuse(int status, const char *what) { return fail(status, std::string("hyperelasticity: ") + what); }
+static int as_hyperelasticity(int status) { return status == BP5_OK ? BP5_OK : fail(status, std::string("hyper") + bp5_last_error()); }
+static int hyperelasticity_check(const bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, const double *dst)
+{
+  if (!state) return hyperelasticity_refuse(BP5_ERR_INVALID, "null argument (the state array)");
+  if (!aligned16(state)) return hyperelasticity_refuse(BP5_ERR_INVALID, "the state array must be 16-byte aligned");
+  return as_hyperelasticity(elasticity_check(mf, coef, lambda, mu, ld, src, dst, true));
+}
+extern "C" int bp5_hyperelasticity_state_size(const bp5_mf *mf, size_t *n_doubles)
+{
+  if (!n_doubles) return hyperelasticity_refuse(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(as_hyperelasticity(elasticity_handle_check(mf)));
+  *n_doubles = 10 * (size_t)mf->n_cells * mf->n3;
+  return BP5_OK;
+}
+// r = [0 +] F_int(u) with zeros on the Dirichlet rows of every block; validated arguments
+static int hyperelasticity_residual(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, const double *u, double *r, bool zero)
+{
+  if (zero) BP5_TRY(components_zero(mf, 3, ld, r));
+  BP5_TRY(hyperelasticity_residual_cells(mf, coef, state, lambda, mu, ld, u, r, 0, mf->n_cells));
+  for (int c = 0; c < 3; ++c) BP5_TRY(bp5_set_constrained(mf, 0.0, r + (size_t)c * ld));
+  return BP5_OK;
+}
+extern "C" int bp5_hyperelasticity_residual(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, const double *u, double *r, int zero_dst)
+{
+  BP5_TRY(hyperelasticity_check(mf, coef, state, lambda, mu, ld, u, r));
+  HIP_TRY(hipSetDevice(mf->device));
+  return hyperelasticity_residual(mf, coef, state, lambda, mu, ld, u, r, zero_dst != 0);
+}
+extern "C" int bp5_hyperelasticity_apply(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, double *dst,
+                                         int zero_dst)
+{
+  BP5_TRY(hyperelasticity_check(mf, coef, state, lambda, mu, ld, src, dst));
+  HIP_TRY(hipSetDevice(mf->device));
+  if (zero_dst) BP5_TRY(components_zero(mf, 3, ld, dst));
+  BP5_TRY(hyperelasticity_apply_cells(mf, coef, state, lambda, mu, ld, src, dst, 0, mf->n_cells));
+  return components_copy_constrained(mf, 3, ld, src, dst);
+}
+extern "C" int bp5_hyperelasticity_apply_cells(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, double *dst,
+                                               uint32_t cell_begin, uint32_t cell_end)
+{
+  BP5_TRY(hyperelasticity_check(mf, coef, state, lambda, mu, ld, src, dst));
+  if (cell_begin > cell_end || cell_end > mf->n_cells) return hyperelasticity_refuse(BP5_ERR_INVALID, "cell range outside [0, n_cells]");
+  HIP_TRY(hipSetDevice(mf->device));
+  return hyperelasticity_apply_cells(mf, coef, state, lambda, mu, ld, src, dst, cell_begin, cell_end);
+}
+// every refusal of the tangent solve, before any launch
+static int cg_solve_hyperelasticity_check(const bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *b, const double *x,
+                                          const bp5_cg_params *prm, const void *res)
+{
+  if (!prm || !res) return hyperelasticity_refuse(BP5_ERR_INVALID, "null argument");
+  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return hyperelasticity_refuse(BP5_ERR_INVALID, "unknown CG variant");
+  if (prm->max_iter < 0) return hyperelasticity_refuse(BP5_ERR_INVALID, "max_iter < 0");
+  BP5_TRY(hyperelasticity_check(mf, coef, state, lambda, mu, ld, b, x));
+  if (prm->variant == BP5_CG_MERGED) return hyperelasticity_refuse(BP5_ERR_UNSUPPORTED, "SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
+  return BP5_OK;
+}
+// the tangent solve on validated arguments: cg_solve_plain's block-vector path, the preconditioner a callback or the identity
+static int cg_solve_hyperelasticity(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                                    const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  PlainCG cg;
+  BP5_TRY(block_cg_workspace(mf, 3, ld, cg));
+  cg.coef = coef; cg.block = true; cg.elasticity = true; cg.hyper_state = state; cg.lambda = lambda; cg.mu = mu;
+  cg.allreduce = false;
+  if (precond) {
+    BP5_TRY(block_cg_workspace_z(mf, 3, ld, cg));
+    cg.precond = precond; cg.precond_ctx = precond_ctx;
+  }
+  return cg_solve_plain(mf, cg, b, x, prm, res);
+}
+extern "C" int bp5_cg_solve_hyperelasticity(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond,
+                                            void *precond_ctx, const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
+{
+  BP5_TRY(cg_solve_hyperelasticity_check(mf, coef, state, lambda, mu, ld, b, x, prm, res));
+  HIP_TRY(hipSetDevice(mf->device));
+  return cg_solve_hyperelasticity(mf, coef, state, lambda, mu, ld, precond, precond_ctx, b, x, prm, res);
+}
+
+// Newton's method with backtracking (bp5.h).  Every vector step is an existing kernel, block by block; one norm per residual
+extern "C" int bp5_hyperelasticity_newton(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                                          const double *f_ext, double *u, const bp5_newton_params *prm, bp5_newton_result *res)
+{
+  if (!prm || !res) return hyperelasticity_refuse(BP5_ERR_INVALID, "null argument");
+  if (prm->max_newton < 0 || prm->max_backtracks < 0) return hyperelasticity_refuse(BP5_ERR_INVALID, "max_newton < 0 or max_backtracks < 0");
+  if (!(prm->abs_tol >= 0.0) || !(prm->rel_tol >= 0.0) || !(prm->cg_rel_tol >= 0.0) || !std::isfinite(prm->abs_tol + prm->rel_tol + prm->cg_rel_tol))
+    return hyperelasticity_refuse(BP5_ERR_INVALID, "tolerances must be finite and >= 0");
+  bp5_cg_result cr;
+  BP5_TRY(cg_solve_hyperelasticity_check(mf, coef, state, lambda, mu, ld, f_ext, u, &prm->cg, &cr));
+  HIP_TRY(hipSetDevice(mf->device));
+  const size_t need = 9 * ld, nl = mf->n_local();
+  if (mf->wsn_cap < need) {
+    if (mf->wsn_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsn_base)); mf->wsn_base = nullptr; mf->wsn_cap = 0; }
+    HIP_TRY(hipMalloc((void **)&mf->wsn_base, need * sizeof(double)));
+    mf->wsn_cap = need;
+  }
+  HIP_TRY(hipMemsetAsync(mf->wsn_base, 0, need * sizeof(double), mf->stream)); // (the padding of the three work vectors)
+  double *delta = mf->wsn_base, *trial = delta + 3 * ld, *r = trial + 3 * ld;
+  // r = f_ext - F_int(v) with zeros on the Dirichlet rows, and its stacked l2 norm over the owned entries
+  auto residual = [&](const double *v, double *norm) -> int {
+    BP5_TRY(hyperelasticity_residual(mf, coef, state, lambda, mu, ld, v, r, true));
+    for (int c = 0; c < 3; ++c) BP5_TRY(bp5_vec_sadd(mf, r + (size_t)c * ld, -1.0, 1.0, f_ext + (size_t)c * ld, nl));
+    for (int c = 0; c < 3; ++c) BP5_TRY(bp5_set_constrained(mf, 0.0, r + (size_t)c * ld));
+    const dim3 grid(std::min(stream_grid(mf->n_owned, 2), PARTIAL_STRIDE / 3), 3);
+    BP5_TRY(blockvec_dot(mf->stream, grid, r, r, mf->n_owned, ld, mf->d_partials));
+    double s = 0.0;
+    BP5_TRY(reduce_to_host(mf, (int)grid.x * 3, &s));
+    *norm = sqrt(s);
+    return BP5_OK;
+  };
+  auto copy_blocks = [&](double *dst, const double *src) -> int { // (block by block: the padding of u is neither read nor written)
+    for (int c = 0; c < 3; ++c) HIP_TRY(hipMemcpyAsync(dst + (size_t)c * ld, src + (size_t)c * ld, nl * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
+    return BP5_OK;
+  };
+  memset(res, 0, sizeof(*res));
+  auto finish = [&](int status) { res->status = status; return status; };
+  auto record = [&](double norm) { if (res->newton_iterations < 32) res->residual_history[res->newton_iterations] = norm; };
+  double rn = 0.0;
+  BP5_TRY(residual(u, &rn));
+  record(rn);
+  if (!std::isfinite(rn)) return finish(hyperelasticity_refuse(BP5_ERR_BREAKDOWN, "Newton: the residual of the start vector is not finite (J <= 0 at a quadrature point?)"));
+  const double tol = std::max(prm->abs_tol, prm->rel_tol * rn);
+  for (int k = 0; k < prm->max_newton; ++k) {
+    if (rn <= tol) return finish(BP5_OK);
+    bp5_cg_params cp = prm->cg;
+    cp.abs_tol = prm->cg_rel_tol * rn;
+    const int st = cg_solve_hyperelasticity(mf, coef, state, lambda, mu, ld, precond, precond_ctx, r, delta, &cp, &cr);
+    res->total_cg_iterations += cr.iterations;
+    if (st != BP5_OK) return finish(st);
+    double alpha = 1.0, rt = 0.0;
+    for (int bt = 0;; ++bt) {
+      BP5_TRY(copy_blocks(trial, u));
+      for (int c = 0; c < 3; ++c) BP5_TRY(bp5_vec_axpy(mf, trial + (size_t)c * ld, alpha, delta + (size_t)c * ld, nl));
+      BP5_TRY(residual(trial, &rt));
+      if (std::isfinite(rt) && rt < rn) break;
+      if (bt == prm->max_backtracks) {
+        BP5_TRY(residual(u, &rt)); // the state of the last accepted iterate
+        return finish(hyperelasticity_refuse(BP5_ERR_BREAKDOWN, "Newton: backtracking exhausted, the residual norm does not decrease"));
+      }
+      alpha *= 0.5;
+      ++res->backtracks;
+    }
+    BP5_TRY(copy_blocks(u, trial));
+    rn = rt;
+    ++res->newton_iterations;
+    record(rn);
+  }
+  HIP_TRY(hipStreamSynchronize(mf->stream));
+  if (rn <= tol) return finish(BP5_OK);
+  return finish(hyperelasticity_refuse(BP5_ERR_NO_CONVERGENCE, "Newton: max_newton steps without reaching the tolerance"));
 }
 
 // cg.solve(A, x, b, P) for a P given by its vmult (deal.II SolverCG, bp5/step-64.cu:446-453): the plain recurrence with z = P g in place of D g

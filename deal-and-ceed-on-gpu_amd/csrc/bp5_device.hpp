@@ -123,6 +123,8 @@ struct bp5_mf {
   size_t wsc_cap = 0;         // ... doubles allocated
   double *wsz_base = nullptr; // bp5_cg_solve_elasticity_preconditioned: z = P g as a block vector (n_components ld doubles), grown on demand
   size_t wsz_cap = 0;
+  double *wsn_base = nullptr; // bp5_hyperelasticity_newton: delta, the trial u and r as block vectors (9 ld doubles), grown on demand
+  size_t wsn_cap = 0;
   // halo exchange of block vectors: four staging buffers in one allocation, grown on demand -- gather send / scatter receive (n_components
   // send_off.back() doubles each), gather receive / scatter send (n_components n_ghost each); a neighbour's message is contiguous and holds
   // all components, [neighbour][component][entry].  d_hc_off: send_off, then recv_off, for the kernels that place an entry in its message
@@ -354,6 +356,14 @@ inline int trilinear_refuse(const char *what) { return fail(BP5_ERR_UNSUPPORTED,
 int elasticity_compute_metric(bp5_mf *mf, double *coef);
 int elasticity_apply_cells(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0, uint32_t c1);
 int elasticity_diagonal(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, double *diag);
+
+// Neo-Hookean hyperelasticity (bp5_hyperelasticity_*), defined in hyperelasticity/bp5_hyperelasticity.hip -- likewise a translation unit and a
+// directory of its own: the residual (fills the ten state planes) and the tangent at the stored state over the cells [c0, c1), on the elasticity
+// operator's ten geometry planes (both accumulate; an empty range launches nothing).  The callers have validated handle, layout and parameters.
+int hyperelasticity_residual_cells(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, const double *u, double *r, uint32_t c0,
+                                   uint32_t c1);
+int hyperelasticity_apply_cells(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, double *dst, uint32_t c0,
+                                uint32_t c1);
 
 // The pointwise and transfer kernels of every vector shape (the Chebyshev step and the multigrid transfers of scalar and of block vectors, the dot
 // product of block vectors), defined in blockvec/bp5_blockvec.hip -- a translation unit of its own, the only one that instantiates them.

@@ -1798,6 +1798,322 @@ __global__ void __launch_bounds__(64 * TW * TPB, elasticity_waves_per_simd(P)) a
 #undef TL
 }
 
+// ------------------------------------------------------------------------------------ fused finite-strain neo-Hookean operator
+// The compressible neo-Hookean energy of the CEED "solids" mini-app (ElasFSInitialNH1F / its dF) and Holzapfel, on the elasticity operator's vectors
+// and TEN geometry planes:  Phi(F) = lambda / 2 (ln J)^2 - mu ln J + mu / 2 (tr F^T F - 3),  F = I + grad_x u,  J = det F,  B = F^-T,
+//   first Piola stress  P  = mu (F - B) + lambda ln J B                                      (MODE == HYPER_RESIDUAL: the source vector is u),
+//   its tangent         dP = mu G + (mu - lambda ln J) B G^T B + lambda (B : G) B,  G = grad_x du (MODE == HYPER_TANGENT:  the source vector is du).
+// The residual build STORES B (planes 0..8, B[c][e] at 3 c + e) and ln J (plane 9) of every quadrature point into the state array -- ten planes laid
+// out exactly as the geometry planes (plane-major, pair layout) -- and the tangent build only reads them: its quadrature-point function has no
+// inverse, determinant or logarithm.  J <= 0 gives NaN in the state and in the result (documented in bp5.h, not trapped).
+// Everything around the quadrature-point loop is apply_pencil_elasticity_kernel's: local_to_global once, three evaluates that keep nine x-owner
+// pencils, planes read pair by pair where they are used, three integrates, atomics; idle lanes mirror a valid lane (loads unconditional, LDS writes,
+// state stores and atomics predicated), every tile reuse is closed by lds_drain(); team_sync().
+enum : int { HYPER_RESIDUAL = 0, HYPER_TANGENT = 1 };
+struct HyperelasticityArgs {
+  double lambda, mu;
+  uint64_t ld;   // doubles between two components (even; >= n_owned + n_ghost)
+  double *state; // ten planes of n_cells n^3 doubles (strides: ApplyArgs::plane_stride / cell_stride of the geometry planes)
+};
+// waves per SIMD asked of the compiler, per degree and mode, from the ISA: the most each build holds without a spill.  With the
+// scheduling fence behind every point pair the builds take 138 / 204 / 276 / 334 VGPRs (residual) and 170 / 250 / 340 / 438 (tangent) at p = 1 .. 4:
+// three waves (two for the tangent, which spills 1 - 2 VGPRs when capped at 168) at p = 1, two at p = 2, one from p = 3.  p >= 6 (tangent) and
+// p >= 7 (residual) spill at one wave: the nine pencils, a pair of the twenty planes and the 3 x 3 temporaries pass 512.  The macro is the A/B knob.
+#ifndef BP5_HYPERELASTICITY_WAVES
+#define BP5_HYPERELASTICITY_WAVES(degree, mode) ((degree) == 1 ? ((mode) == HYPER_TANGENT ? 2 : 3) : (degree) == 2 ? 2 : 1)
+#endif
+constexpr int hyperelasticity_waves_per_simd(int degree, int mode) { return BP5_HYPERELASTICITY_WAVES(degree, mode); }
+template <int P, bool COLL, int TW, int LPC, int TPB, int MODE>
+__global__ void __launch_bounds__(64 * TW * TPB, hyperelasticity_waves_per_simd(P, MODE))
+apply_pencil_hyperelasticity_kernel(ApplyArgs a, HyperelasticityArgs ea, ShapeArg<P + 1> sh)
+{
+  constexpr int n = P + 1, n2 = n * n, n3 = n2 * n;
+  constexpr int TEAM = 64 * TW;
+  constexpr int CPT = TEAM / LPC;
+  static_assert(LPC >= n2 && CPT >= 1, "lanes per cell");
+  static_assert(TW == 1 || TPB == 1, "block-wide barrier needs one team per block");
+  static_assert(MODE == HYPER_RESIDUAL || MODE == HYPER_TANGENT, "mode");
+  using L = LdsLayout<n, LPC>;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+
+  const int tid = threadIdx.x;
+  const int team_in_block = tid / TEAM;
+  const int t = tid - team_in_block * TEAM;
+  const int c = t / LPC, ab = t - c * LPC;
+  const uint32_t blk = (blockIdx.x & 7u) * a.teams_per_xcd + (blockIdx.x >> 3); // XCD-aware mapping, as apply_pencil_kernel
+  const uint32_t team = blk * TPB + team_in_block;
+  const uint64_t cell_raw = (uint64_t)a.cell_begin + (uint64_t)team * CPT + c;
+  const bool active = (ab < n2) && (c < CPT) && (team < a.n_teams) && (cell_raw < a.cell_end);
+  // idle lanes mirror a valid lane: every load is unconditional and in bounds; LDS writes, state stores and the atomics are predicated
+  const uint64_t cell = cell_raw < a.cell_end ? cell_raw : (uint64_t)a.cell_end - 1;
+  const int abm = ab < n2 ? ab : ab % n2;
+  const int a_ = abm % n, b_ = abm / n;
+  double *T = lds + (team_in_block * CPT + (c < CPT ? c : 0)) * L::CS;
+#define TL(f, k, j, i) T[(f) * (n * L::PS) + (k) * L::PS + (j) * L::RS + (i)]
+
+  // ---- once per cell: indices (z-owner)
+  uint32_t idx[n];
+  const uint32_t *l2g_c = a.l2g + cell * n3 + abm;
+#pragma unroll
+  for (int k = 0; k < n; ++k) idx[k] = l2g_c[k * n2];
+
+  // ---- evaluate, component after component: g[comp][d] = the x-owner pencil of the reference gradient along d
+  double g[3][3][n];
+#pragma unroll
+  for (int comp = 0; comp < 3; ++comp) {
+    const double *src_c = a.src + (uint64_t)comp * ea.ld;
+    double u[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) u[k] = src_c[idx[k]];
+    if constexpr (!COLL) {
+      double aN[n], aD[n];
+      MV_N(sh.N, u, aN);
+      MV_D(sh.D, u, aD);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = aN[k]; TL(1, k, b_, a_) = aD[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], vD[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { vN[j] = TL(0, b_, j, a_); vD[j] = TL(1, b_, j, a_); }
+      double c1[n], c2[n], c3[n];
+      MV_N(sh.N, vN, c1);
+      MV_D(sh.D, vN, c2);
+      MV_N(sh.N, vD, c3);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = c1[j]; TL(1, b_, j, a_) = c2[j]; TL(2, b_, j, a_) = c3[j]; }
+      }
+      team_sync<TW>();
+      double r1[n], r2[n], r3[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        r2[i] = TL(1, b_, a_, i);
+        r3[i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g[comp][0]);
+      MV_N(sh.N, r2, g[comp][1]);
+      MV_N(sh.N, r3, g[comp][2]);
+    } else {
+      double gz[n];
+      MV_D(sh.D, u, gz);
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) { TL(0, k, b_, a_) = u[k]; TL(2, k, b_, a_) = gz[k]; }
+      }
+      team_sync<TW>();
+      double vN[n], c2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) vN[j] = TL(0, b_, j, a_);
+      MV_D(sh.D, vN, c2);
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(1, b_, j, a_) = c2[j];
+      }
+      team_sync<TW>();
+      double r1[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        r1[i] = TL(0, b_, a_, i);
+        g[comp][1][i] = TL(1, b_, a_, i);
+        g[comp][2][i] = TL(2, b_, a_, i);
+      }
+      MV_D(sh.D, r1, g[comp][0]);
+    }
+    // the next component's (or the integrate's) first tile write follows this component's last tile read
+    lds_drain();
+    team_sync<TW>();
+  }
+
+  // ---- quadrature-point operation (x-owner: a_ = qj, b_ = qk; registers hold qi): geometry and state planes pair by pair
+  {
+    const double *cf = a.coef + cell * a.cell_stride;
+    double *st = ea.state + cell * a.cell_stride;
+    const double lambda = ea.lambda, mu = ea.mu;
+    // G[c][e] = sum_d K[d][e] ghat_c[d] at point i
+    auto phys_grad = [&](int i, const double (&K)[10], double (&G)[3][3]) {
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) G[cc][e] = K[e] * g[cc][0][i] + K[3 + e] * g[cc][1][i] + K[6 + e] * g[cc][2][i];
+    };
+    // t_c[d] = s sum_e K[d][e] T[c][e] over the nine pencils at point i
+    auto pull_back = [&](int i, const double (&K)[10], const double (&S)[3][3]) {
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) g[cc][d][i] = K[9] * (K[3 * d] * S[cc][0] + K[3 * d + 1] * S[cc][1] + K[3 * d + 2] * S[cc][2]);
+    };
+    // residual: F, J, B = cof(F) / J, ln J into W (the ten state entries of the point), P into the pencils
+    auto qpoint_residual = [&](int i, const double (&K)[10], double (&W)[10]) {
+      double F[3][3];
+      phys_grad(i, K, F);
+      F[0][0] += 1.0; F[1][1] += 1.0; F[2][2] += 1.0;
+      double Cf[3][3]; // cofactors: F^-T = Cf / J
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {
+        const int c1 = (cc + 1) % 3, c2 = (cc + 2) % 3;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          const int e1 = (e + 1) % 3, e2 = (e + 2) % 3;
+          Cf[cc][e] = F[c1][e1] * F[c2][e2] - F[c1][e2] * F[c2][e1];
+        }
+      }
+      const double J = F[0][0] * Cf[0][0] + F[0][1] * Cf[0][1] + F[0][2] * Cf[0][2];
+      const bool ok = J > 0.0;
+      const double nan = __builtin_nan("");
+      const double inv_J = ok ? 1.0 / J : nan, ln_J = ok ? log(J) : nan;
+      const double llj = lambda * ln_J;
+      double Pk[3][3];
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          const double Bce = Cf[cc][e] * inv_J;
+          W[3 * cc + e] = Bce;
+          Pk[cc][e] = mu * (F[cc][e] - Bce) + llj * Bce;
+        }
+      W[9] = ln_J;
+      pull_back(i, K, Pk);
+    };
+    // tangent at the stored state W
+    auto qpoint_tangent = [&](int i, const double (&K)[10], const double (&W)[10]) {
+      double G[3][3];
+      phys_grad(i, K, G);
+      double M[3][3]; // G^T B
+#pragma unroll
+      for (int aa = 0; aa < 3; ++aa)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) M[aa][e] = G[0][aa] * W[e] + G[1][aa] * W[3 + e] + G[2][aa] * W[6 + e];
+      double BG = 0.0; // B : G
+#pragma unroll
+      for (int q = 0; q < 9; ++q) BG += W[q] * G[q / 3][q % 3];
+      const double cb = mu - lambda * W[9], lbg = lambda * BG;
+      double dP[3][3];
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+          dP[cc][e] = mu * G[cc][e] + cb * (W[3 * cc] * M[0][e] + W[3 * cc + 1] * M[1][e] + W[3 * cc + 2] * M[2][e]) + lbg * W[3 * cc + e];
+      pull_back(i, K, dP);
+    };
+#pragma unroll
+    for (int m = 0; m < n / 2; ++m) {
+      double K0[10], K1[10], W0[10], W1[10];
+#pragma unroll
+      for (int pl = 0; pl < 10; ++pl) load_pencil_pair<n>(cf + pl * a.plane_stride, abm, m, K0[pl], K1[pl]);
+      if constexpr (MODE == HYPER_TANGENT) {
+#pragma unroll
+        for (int pl = 0; pl < 10; ++pl) load_pencil_pair<n>(st + pl * a.plane_stride, abm, m, W0[pl], W1[pl]);
+        qpoint_tangent(2 * m, K0, W0);
+        qpoint_tangent(2 * m + 1, K1, W1);
+      } else {
+        qpoint_residual(2 * m, K0, W0);
+        qpoint_residual(2 * m + 1, K1, W1);
+        if (active) { // the pair as one 16-byte store (the address load_pencil_pair reads)
+#pragma unroll
+          for (int pl = 0; pl < 10; ++pl) {
+            bp5_d2u v;
+            v.x = W0[pl];
+            v.y = W1[pl];
+            *reinterpret_cast<bp5_d2u *>(st + pl * a.plane_stride + m * (2 * n * n) + 2 * abm) = v;
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0); // two points in flight, not more: the next pair's loads and arithmetic hoisted above this one's spill at p <= 4
+    }
+    if constexpr (n & 1) {
+      double K0[10], W0[10];
+#pragma unroll
+      for (int pl = 0; pl < 10; ++pl) K0[pl] = load_pencil_tail<n>(cf + pl * a.plane_stride, abm);
+      if constexpr (MODE == HYPER_TANGENT) {
+#pragma unroll
+        for (int pl = 0; pl < 10; ++pl) W0[pl] = load_pencil_tail<n>(st + pl * a.plane_stride, abm);
+        qpoint_tangent(n - 1, K0, W0);
+      } else {
+        qpoint_residual(n - 1, K0, W0);
+        if (active) {
+#pragma unroll
+          for (int pl = 0; pl < 10; ++pl) st[pl * a.plane_stride + (n / 2) * (2 * n * n) + abm] = W0[pl];
+        }
+      }
+    }
+  }
+
+  // ---- integrate (transpose sequence) and scatter-add, component after component
+#pragma unroll
+  for (int comp = 0; comp < 3; ++comp) {
+    double y[n];
+    if constexpr (!COLL) {
+      double e1[n], e2[n], e3[n];
+      MV_DT(sh.D, g[comp][0], e1);
+      MV_NT(sh.N, g[comp][1], e2);
+      MV_NT(sh.N, g[comp][2], e3);
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = e2[i]; TL(2, b_, a_, i) = e3[i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n], w3[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        w1[j] = TL(0, b_, j, a_);
+        w2[j] = TL(1, b_, j, a_);
+        w3[j] = TL(2, b_, j, a_);
+      }
+      double f1[n], f2[n];
+      MV_NT(sh.N, w1, f1);
+      MV_DT_ADD(sh.D, w2, f1);
+      MV_NT(sh.N, w3, f2);
+      team_sync<TW>();
+      if (active) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) { TL(0, b_, j, a_) = f1[j]; TL(1, b_, j, a_) = f2[j]; }
+      }
+      team_sync<TW>();
+      double z1[n], z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { z1[k] = TL(0, k, b_, a_); z2[k] = TL(1, k, b_, a_); }
+      MV_NT(sh.N, z1, y);
+      MV_DT_ADD(sh.D, z2, y);
+    } else {
+      double e1[n];
+      MV_DT(sh.D, g[comp][0], e1);
+      if (active) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) { TL(0, b_, a_, i) = e1[i]; TL(1, b_, a_, i) = g[comp][1][i]; TL(2, b_, a_, i) = g[comp][2][i]; }
+      }
+      team_sync<TW>();
+      double w1[n], w2[n];
+#pragma unroll
+      for (int j = 0; j < n; ++j) { w1[j] = TL(0, b_, j, a_); w2[j] = TL(1, b_, j, a_); }
+      MV_DT_ADD(sh.D, w2, w1);
+      if (active) { // each y-owner lane rewrites only the column it has just read
+#pragma unroll
+        for (int j = 0; j < n; ++j) TL(0, b_, j, a_) = w1[j];
+      }
+      team_sync<TW>();
+      double z2[n];
+#pragma unroll
+      for (int k = 0; k < n; ++k) { y[k] = TL(0, k, b_, a_); z2[k] = TL(2, k, b_, a_); }
+      MV_DT_ADD(sh.D, z2, y);
+    }
+    if (active) {
+      double *dst_c = a.dst + (uint64_t)comp * ea.ld;
+#pragma unroll
+      for (int k = 0; k < n; ++k) atomic_add_f64(dst_c + idx[k], y[k]);
+    }
+    if (comp < 2) { // the next component's first tile write follows this component's last tile read
+      lds_drain();
+      team_sync<TW>();
+    }
+  }
+#undef TL
+}
+
 // degrees whose block-kernel cells span waves (n^2 lanes per cell: p = 2, 5, 8) and exchange their tiles through the workgroup barrier: two
 // tiles used alternately halve the barriers of a pass (BlockPass::PP) where the second tile still fits the LDS share of the workgroup
 #ifndef BP5_PINGPONG_P2

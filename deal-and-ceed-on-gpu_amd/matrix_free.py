@@ -469,8 +469,65 @@ class ElasticityOperator:
         return r.value
 
 
+class HyperelasticityOperator:
+    """Finite-strain compressible neo-Hookean elasticity on three-component block vectors (the CEED "solids" mini-app's ElasFSInitialNH1F; deal.II
+    step-44 / step-72): Phi(F) = lam / 2 (ln J)^2 - mu ln J + mu / 2 (tr F^T F - 3) as the library's native residual and tangent kernels
+    (bp5_hyperelasticity_*, include/bp5.h).  residual(r, u) evaluates F_int(u) and stores the state (B = F^-T and ln J at every quadrature point);
+    vmult(dst, src) is the tangent AT THAT STATE.  `linear` is the ElasticityOperator on the same handle and geometry planes -- the tangent at u = 0:
+    build ElasticityPreconditionChebyshev / ElasticityPreconditionMG from it and hand them to SolverCG.solve(op, x, b, P)
+    (bp5_cg_solve_hyperelasticity; None = no preconditioner) or NewtonSolver.solve(op, u, f_ext, P)."""
+
+    n_components = 3
+
+    def __init__(self, mesh, quadrature=QUAD_GAUSS, coefficient=COEF_ONE, lam=1.0, mu=1.0, device=0, stream=None):
+        torch = _torch()
+        self.linear = ElasticityOperator(mesh, quadrature, coefficient, lam, mu, device, stream)
+        self.lam, self.mu, self.mf_data, self.coef = self.linear.lam, self.linear.mu, self.linear.mf_data, self.linear.coef
+        n = C.c_size_t()
+        _lib.check(_lib.lib().bp5_hyperelasticity_state_size(self.mf_data.handle, C.byref(n)))
+        self.state = torch.zeros(max(n.value, 2), dtype=torch.float64, device=f"cuda:{device}")
+        self.n_owned_cells = mesh.n_cells
+        self.do_zero_out = True
+        self.distributed = False
+        self.residual(self.initialize_block_vector(), self.initialize_block_vector())      # the state of u = 0: vmult is the linear operator until residual is called
+
+    def initialize_block_vector(self):
+        return self.mf_data.initialize_block_vector(3)
+
+    def assemble_rhs(self):
+        """the scalar load vector b_i = int phi_i (bp5_assemble_rhs): a body force f is b_c = f_c * assemble_rhs()"""
+        return self.linear.assemble_rhs()
+
+    def _args(self, *vectors):
+        nc, ld = _block_args(self.mf_data, *vectors)
+        if nc != 3:
+            raise BP5Error(1, f"hyperelasticity: block vectors of three components expected, got {nc}")
+        return ld
+
+    def residual(self, r, u):
+        """r = [0 +] F_int(u) on (3, ld) tensors, r_c = 0 on Dirichlet DoFs; stores the state of u (bp5_hyperelasticity_residual)."""
+        r, u = _vals(r), _vals(u)
+        ld = self._args(r, u)
+        _lib.check(_lib.lib().bp5_hyperelasticity_residual(self.mf_data.handle, _ptr(self.coef), _ptr(self.state), self.lam, self.mu, ld, _ptr(u), _ptr(r),
+                                                           1 if self.do_zero_out else 0))
+
+    def vmult(self, dst, src):
+        """dst = [0 +] T(state) src; dst_c = src_c on Dirichlet DoFs (bp5_hyperelasticity_apply)."""
+        dst, src = _vals(dst), _vals(src)
+        ld = self._args(dst, src)
+        _lib.check(_lib.lib().bp5_hyperelasticity_apply(self.mf_data.handle, _ptr(self.coef), _ptr(self.state), self.lam, self.mu, ld, _ptr(src), _ptr(dst),
+                                                        1 if self.do_zero_out else 0))
+
+    def cell_loop(self, src, dst, cell_begin=0, cell_end=None):
+        """dst += T(state) src over the cells [cell_begin, cell_end), no Dirichlet copy (bp5_hyperelasticity_apply_cells)."""
+        ld = self._args(dst, src)
+        cell_end = self.n_owned_cells if cell_end is None else cell_end
+        _lib.check(_lib.lib().bp5_hyperelasticity_apply_cells(self.mf_data.handle, _ptr(self.coef), _ptr(self.state), self.lam, self.mu, ld, _ptr(src), _ptr(dst),
+                                                              cell_begin, cell_end))
+
+
 def _refuse_elasticity(who, A):
-    if isinstance(A, ElasticityOperator):
+    if isinstance(A, (ElasticityOperator, HyperelasticityOperator)):
         raise BP5Error(5, f"{who} does not take the elasticity operator: SolverCG with None / DiagonalMatrix does")
 
 
@@ -1127,6 +1184,8 @@ class _SolverBase:
         (bp5_cg_solve_elasticity_preconditioned with their native vmult; SolverCG only); anything else is refused (BP5Error 5)."""
         mf = A.mf_data
         x, b = _vals(x), _vals(b)
+        if isinstance(A, HyperelasticityOperator):
+            return self._solve_hyperelasticity(A, x, b, preconditioner)
         general = preconditioner is not None and not hasattr(preconditioner, "get_vector")
         # the elasticity preconditioners (SolverCG): bp5_cg_solve_elasticity_preconditioned with their native vmult
         el_precond = (isinstance(A, ElasticityOperator) and self.variant == CG_PLAIN
@@ -1189,6 +1248,19 @@ class _SolverBase:
                 status = _lib.lib().bp5_cg_solve_operator(mf.handle, cb, None, dptr, _ptr(b, mf.n_local), _ptr(x, mf.n_local), C.byref(prm), C.byref(res))
         if failure:
             raise failure[0]
+        return self._finish(res, status)
+
+    def _solve_hyperelasticity(self, A, x, b, preconditioner):
+        """the tangent at A's stored state (bp5_cg_solve_hyperelasticity): None, or an elasticity preconditioner of A.linear with its native vmult"""
+        ld = A._args(x, b)
+        pfn, pctx = _elasticity_precond(preconditioner, ld)
+        prm = _lib.CGParams(self.variant, self.control.max_steps, self.control.tolerance, self.check_every, int(self.profile))
+        res = _lib.CGResult()
+        status = _lib.lib().bp5_cg_solve_hyperelasticity(A.mf_data.handle, _ptr(A.coef), _ptr(A.state), A.lam, A.mu, ld, pfn, pctx, _ptr(b), _ptr(x), C.byref(prm),
+                                                         C.byref(res))
+        return self._finish(res, status)
+
+    def _finish(self, res, status):
         c = self.control
         c._last_step, c._last_value, c._initial_value = res.iterations, res.residual, res.initial_residual
         c.solve_ms, c.apply_ms_avg, c.apply_launches = res.solve_ms, res.apply_ms_avg, res.apply_launches
@@ -1201,6 +1273,49 @@ class _SolverBase:
 
 class SolverCG(_SolverBase):
     variant = CG_PLAIN
+
+
+def _elasticity_precond(preconditioner, ld):
+    """(callback, context) of the preconditioners the hyperelastic solves take: None (identity), ElasticityPreconditionChebyshev, ElasticityPreconditionMG"""
+    if preconditioner is None:
+        return None, None
+    if not isinstance(preconditioner, (ElasticityPreconditionChebyshev, ElasticityPreconditionMG)):
+        raise BP5Error(5, "hyperelasticity: the preconditioner is None, an ElasticityPreconditionChebyshev or an ElasticityPreconditionMG (of op.linear)")
+    if ld != preconditioner.ld:
+        raise BP5Error(1, f"hyperelasticity: the preconditioner was initialised for ld = {preconditioner.ld}, the vectors have {ld}")
+    fn = _lib.lib().bp5_mg_vmult if isinstance(preconditioner, ElasticityPreconditionMG) else _lib.lib().bp5_chebyshev_vmult
+    return C.cast(fn, C.c_void_p), preconditioner.handle
+
+
+class NewtonSolver:
+    """Newton's method with backtracking on F_int(u) = f_ext for a HyperelasticityOperator (bp5_hyperelasticity_newton, include/bp5.h).
+    control: SolverControl(max Newton steps, absolute tolerance on ||r||); cg_control: SolverControl(max CG iterations per step, unused tolerance --
+    every tangent solve runs to cg_rel_tol ||r||).  After solve: newton_iterations, total_cg_iterations, backtracks, residual_history."""
+
+    def __init__(self, control, cg_control, rel_tol=1e-10, cg_rel_tol=1e-12, max_backtracks=8, check_every=0):
+        self.control, self.cg_control = control, cg_control
+        self.rel_tol, self.cg_rel_tol, self.max_backtracks, self.check_every = rel_tol, cg_rel_tol, max_backtracks, check_every
+        self.newton_iterations = self.total_cg_iterations = self.backtracks = 0
+        self.residual_history = []
+
+    def solve(self, op, u, f_ext, preconditioner=None):
+        """u: the start vector (its Dirichlet values are the prescribed displacement) -> the solution.  Raises BP5Error 7 (no convergence) or
+        6 (backtracking exhausted); the counters and the history are set either way."""
+        if not isinstance(op, HyperelasticityOperator):
+            raise BP5Error(1, "NewtonSolver needs a HyperelasticityOperator")
+        u, f_ext = _vals(u), _vals(f_ext)
+        ld = op._args(u, f_ext)
+        pfn, pctx = _elasticity_precond(preconditioner, ld)
+        cg = _lib.CGParams(CG_PLAIN, self.cg_control.max_steps, 0.0, self.check_every, 0)
+        prm = _lib.NewtonParams(self.control.max_steps, self.control.tolerance, self.rel_tol, cg, self.cg_rel_tol, self.max_backtracks)
+        res = _lib.NewtonResult()
+        status = _lib.lib().bp5_hyperelasticity_newton(op.mf_data.handle, _ptr(op.coef), _ptr(op.state), op.lam, op.mu, ld, pfn, pctx, _ptr(f_ext), _ptr(u),
+                                                       C.byref(prm), C.byref(res))
+        self.newton_iterations, self.total_cg_iterations, self.backtracks = res.newton_iterations, res.total_cg_iterations, res.backtracks
+        self.residual_history = list(res.residual_history[:min(res.newton_iterations + 1, 32)])
+        self.control._last_step, self.control._last_value = res.newton_iterations, self.residual_history[-1] if self.residual_history else 0.0
+        _lib.check(status)
+        return res
 
 
 class SolverCGFullMerge(_SolverBase):

@@ -662,6 +662,72 @@ int bp5_cg_solve_elasticity(bp5_mf *mf, const double *coef, double lambda, doubl
 int bp5_cg_solve_elasticity_preconditioned(bp5_mf *mf, const double *coef, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
                                            const double *b, double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
 
+/* ---- Finite-strain hyperelasticity: the compressible neo-Hookean material of the CEED "solids" mini-app (ElasFSInitialNH1F) and Holzapfel,
+ *   Phi(F) = lambda / 2 (ln J)^2 - mu ln J + mu / 2 (tr F^T F - 3),   F = I + grad_x u,   J = det F,   B = F^-T,
+ *   first Piola stress  P  = mu (F - B) + lambda ln J B,
+ *   its tangent         dP = mu G + (mu - lambda ln J) B G^T B + lambda (B : G) B     for an increment with G = grad_x du,
+ * on the vectors, the handle and the TEN geometry planes of the linear elasticity entries above (coef: bp5_elasticity_compute_metric's array;
+ * kappa scales the energy: s = kappa JxW).  At F = I the tangent is the operator of bp5_elasticity_apply; it is symmetric (it comes from a
+ * potential).  A quadrature point computes G[c][e] = sum_d K[d][e] ghat_c[d] and t_c[d] = s sum_e K[d][e] T[c][e], T = P (residual) or dP (tangent).
+ * state: ten planes of n_cells (p+1)^3 doubles, plane-major, each in the pair layout of the metric planes -- planes 0..8 B[c][e] at 3 c + e,
+ * plane 9 ln J.  The residual WRITES it, the tangent only READS it (no inverse, determinant or logarithm in the tangent's quadrature-point function):
+ * a tangent application belongs to the u of the last residual call on that array.  A point with J <= 0 yields NaN in the state and in r: documented,
+ * not trapped (bp5_hyperelasticity_newton backtracks on a non-finite norm).
+ * One rank, conforming meshes, FP64 planes, constant lambda and mu.  Refused before any launch and in either call order, bp5_last_error names
+ * "hyperelasticity": everything bp5_elasticity_apply refuses, with the same status (the trilinear geometry mode among them), and a null state
+ * (BP5_ERR_INVALID).  The entries sit beside the handle's others and change none of them. */
+/* Doubles of the state array: 10 n_cells (p+1)^3. */
+int bp5_hyperelasticity_state_size(const bp5_mf *mf, size_t *n_doubles);
+/* r = [0 +] F_int(u), r_c = 0 on Dirichlet DoFs in every block, and the state of u is stored.  u may carry non-zero values on Dirichlet DoFs (a
+ * prescribed displacement).  Per-block zero-fill, ONE launch of apply_pencil_hyperelasticity_kernel<.., residual> (the degree's default pencil
+ * shape, both quadratures), the Dirichlet zeros.  Scatter by atomics: not bitwise reproducible.  Entries [n_owned + n_ghost, ld) are never read or
+ * written.  (replaces CEED solids' ElasFSInitialNH1F residual QFunction; deal.II step-44's assemble_system_rhs) */
+int bp5_hyperelasticity_residual(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, const double *u, double *r, int zero_dst);
+/* dst = [0 +] T(state) src, the tangent at the stored state; dst_c = src_c on Dirichlet DoFs.  ONE launch of
+ * apply_pencil_hyperelasticity_kernel<.., tangent>.  (replaces CEED solids' ElasFSInitialNH1F_dF Jacobian QFunction; deal.II step-44's tangent matrix
+ * assembly, applied matrix-free as in step-72) */
+int bp5_hyperelasticity_apply(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, double *dst, int zero_dst);
+/* dst += T(state) src over the cells [cell_begin, cell_end) (any range, also ragged against the kernel's teams; empty: nothing is launched); no
+ * zero-fill, no Dirichlet step: the contract of bp5_elasticity_apply_cells.  (replaces one colour of MatrixFree::cell_loop on the tangent) */
+int bp5_hyperelasticity_apply_cells(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *src, double *dst,
+                                    uint32_t cell_begin, uint32_t cell_end);
+/* SolverCG on T(state) x = b: the BP5_CG_PLAIN recurrence of bp5_cg_solve_elasticity_preconditioned with the tangent as operator step.  precond ==
+ * NULL: identity; otherwise any bp5_vmult_fn on three-block vectors of this ld -- intended: bp5_chebyshev_vmult / bp5_mg_vmult with handles of
+ * bp5_elasticity_chebyshev_create / bp5_elasticity_mg_create on the same handle and ld, i.e. the LINEAR operator as preconditioner of the tangent.
+ * Stop rule, check_every, breakdown status and result fields as there (dot_products_fused == 0); BP5_CG_MERGED: BP5_ERR_UNSUPPORTED.
+ * (replaces the linear solve inside CEED solids' SNES / step-44's solve_linear_system) */
+int bp5_cg_solve_hyperelasticity(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                                 const double *b, double *x, const bp5_cg_params *params, bp5_cg_result *result_host);
+
+/* Newton's method with backtracking on F_int(u) = f_ext (replaces CEED solids' SNES with a line search; deal.II step-44's solve_nonlinear_timestep).
+ * From the given u (Dirichlet values as prescribed; they stay):
+ *   r = f_ext - F_int(u), Dirichlet rows 0;   stop on ||r|| <= max(abs_tol, rel_tol ||r_0||);
+ *   T(state) delta = r by bp5_cg_solve_hyperelasticity with cg (its abs_tol is REPLACED by cg_rel_tol ||r||; a solve that ends at cg.max_iter is used
+ *   as it is) and the given preconditioner;
+ *   u_new = u + alpha delta, alpha = 1, halved while the new ||r|| is non-finite or not smaller than the old (at most max_backtracks halvings);
+ *   the accepted residual has refilled the state.
+ * Synchronous; ONE norm per residual (the stacked l2 norm over the owned entries of all blocks).  residual_history[k]: ||r|| after k steps (k = 0:
+ * the start), the first 32.  status / return value: BP5_OK, BP5_ERR_NO_CONVERGENCE after max_newton steps (u: the last accepted iterate),
+ * BP5_ERR_BREAKDOWN when backtracking is exhausted (u: the last accepted iterate, the state refilled for it), the inner solve breaks down or the residual of the start vector is not finite.
+ * The work vectors (delta, the trial u and r: 9 ld doubles) belong to the handle.  Refusals: those of bp5_cg_solve_hyperelasticity; max_newton < 0,
+ * max_backtracks < 0, a negative or non-finite tolerance, u overlapping f_ext: BP5_ERR_INVALID. */
+typedef struct {
+  int max_newton;
+  double abs_tol, rel_tol;
+  bp5_cg_params cg;
+  double cg_rel_tol;
+  int max_backtracks;
+} bp5_newton_params;
+typedef struct {
+  int newton_iterations;        /* accepted steps */
+  int total_cg_iterations;
+  double residual_history[32];
+  int backtracks;               /* halvings of alpha over all steps */
+  int status;                   /* the return value */
+} bp5_newton_result;
+int bp5_hyperelasticity_newton(bp5_mf *mf, const double *coef, double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond, void *precond_ctx,
+                               const double *f_ext, double *u, const bp5_newton_params *params, bp5_newton_result *result_host);
+
 /* BP5_CG_MERGED on the packed block kernel (cell bricks, one rank's cells, diag == NULL): by default the operator's
  * write-out and combine pass also form the v-dependent dot products of update_b (bp5/solver.h:142-311: p.v, v.v, r.v, r.r)
  * and write the Dirichlet rows, so the separate pass over p, r, v and the copy_constrained launch disappear.  Same
