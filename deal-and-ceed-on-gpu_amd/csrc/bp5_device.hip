@@ -2603,26 +2603,59 @@ static int plan_operator(bp5_mf *mf, bool own_operator, bool fusable, SolveState
   return BP5_OK;
 }
 
-// ---- the plain recurrence (deal.II SolverCG): ONE driver for scalar vectors, block vectors and any preconditioner.  Its entry points have
-// checked their arguments and made the work vectors; they describe the solve by this struct
-struct PlainCG {
-  // vectors: n_components blocks ld apart (a scalar vector: one block) and the workspace triple g, d, h
-  int n_components = 1;
-  size_t ld = 0;
-  double *g = nullptr, *d = nullptr, *h = nullptr;
-  // operator: the library's (coef) or the caller's callback (an operator callback: scalar vectors only); block: the block-vector application, with
-  // the halo exchange or without
+// ---- which operator a solve or a preconditioner applies, and on what vector shape: the ONE description that PlainCG, bp5_chebyshev and bp5_mg hold.
+// Its makers (the entry points) have checked the arguments
+struct LinearOp {
+  // NATIVE: the handle's scalar operator on coef (Poisson, Helmholtz, mass); CALLBACK: the caller's vmult (scalar vectors only); BLOCK_POISSON: the
+  // scalar operator block by block; ELASTICITY: the coupled three-component operator (coef: its ten planes); HYPERELASTIC_TANGENT: the neo-Hookean
+  // tangent at `state` (the ten state planes of bp5_hyperelasticity_residual)
+  enum Kind { NATIVE, CALLBACK, BLOCK_POISSON, ELASTICITY, HYPERELASTIC_TANGENT } kind = NATIVE;
   const double *coef = nullptr;
   bp5_vmult_fn user = nullptr;
   void *user_ctx = nullptr;
-  bool block = false, exchange = false;
-  // elasticity: the block operator is the coupled three-component one (coef: its ten planes; lambda, mu by value)
-  bool elasticity = false;
+  // vectors: n_components blocks ld apart; a scalar vector: 1 and 0
+  int n_components = 1;
+  size_t ld = 0;
+  bool exchange = false; // BLOCK_POISSON: every application carries the halo exchange
   double lambda = 0.0, mu = 0.0;
-  const double *hyper_state = nullptr; // ... or, with the ten state planes of bp5_hyperelasticity_residual, the neo-Hookean tangent at that state
+  const double *state = nullptr;
+  bool block() const { return kind >= BLOCK_POISSON; }
+};
+static LinearOp scalar_op(const double *coef, bp5_vmult_fn user, void *user_ctx) { return {user ? LinearOp::CALLBACK : LinearOp::NATIVE, coef, user, user_ctx}; }
+static LinearOp elasticity_op(const double *coef, double lambda, double mu, size_t ld, const double *state = nullptr)
+{
+  return {state ? LinearOp::HYPERELASTIC_TANGENT : LinearOp::ELASTICITY, coef, nullptr, nullptr, 3, ld, false, lambda, mu, state};
+}
+// dst = A src for a block operator on validated arguments, Dirichlet rows included: the zero-fill, the cell loop, the Dirichlet copy, with the four
+// marks of a profiled application around them
+static int block_op_apply(bp5_mf *mf, const LinearOp &A, double *src, double *dst, ApplyProfile &prof)
+{
+  const int nc = A.n_components;
+  BP5_TRY(prof.mark(0));
+  BP5_TRY(components_zero(mf, nc, A.ld, dst));
+  BP5_TRY(prof.mark(1));
+  switch (A.kind) {
+    case LinearOp::HYPERELASTIC_TANGENT: BP5_TRY(hyperelasticity_apply_cells(mf, A.coef, A.state, A.lambda, A.mu, A.ld, src, dst, 0, mf->n_cells)); break;
+    case LinearOp::ELASTICITY: BP5_TRY(elasticity_apply_cells(mf, A.coef, A.lambda, A.mu, A.ld, src, dst, 0, mf->n_cells)); break;
+    default:
+      if (A.exchange) BP5_TRY(components_apply_exchanged(mf, A.coef, nc, A.ld, src, dst, false));
+      else BP5_TRY(components_apply(mf, A.coef, nc, A.ld, src, dst, false));
+  }
+  BP5_TRY(prof.mark(2));
+  BP5_TRY(components_copy_constrained(mf, nc, A.ld, src, dst));
+  BP5_TRY(prof.mark(3));
+  if (prof.on) prof.used += 4;
+  return BP5_OK;
+}
+
+// ---- the plain recurrence (deal.II SolverCG): ONE driver for scalar vectors, block vectors and any preconditioner.  Its entry points have
+// checked their arguments and made the work vectors; they describe the solve by this struct
+struct PlainCG {
+  LinearOp op;                                     // the operator and the shape of every vector of the solve
+  double *g = nullptr, *d = nullptr, *h = nullptr; // the workspace triple
   // preconditioner: an inverse diagonal (NULL == 1), or a callback that writes z = P g -- on scalar vectors (bp5_cg_solve_preconditioned) or on
   // block vectors of the solve's n_components and ld (bp5_cg_solve_elasticity_preconditioned); z is laid out like g (scalar: ws_z; block:
-  // wsz_base, block_cg_workspace_z).  diag_ld: doubles between the diagonals of two components -- 0: ONE scalar diagonal applied to every block;
+  // wsz_base, block_cg_workspace).  diag_ld: doubles between the diagonals of two components -- 0: ONE scalar diagonal applied to every block;
   // ld: a block inverse diagonal
   const double *diag = nullptr;
   size_t diag_ld = 0;
@@ -2640,8 +2673,9 @@ struct PlainCG {
 static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
   hipStream_t s = mf->stream;
-  const size_t n = mf->n_owned, ld = cg.ld;
-  const int nc = cg.n_components;
+  const LinearOp &A = cg.op;
+  const size_t n = mf->n_owned, ld = A.ld;
+  const int nc = A.n_components;
   double *g = cg.g, *d = cg.d, *h = cg.h, *z = cg.z;
   const double *diag = cg.diag;
   const size_t dld = cg.diag_ld;
@@ -2649,32 +2683,22 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
   // vector: all of them, stream_grid never asks for more).  Scalar vectors launch the direction kernel, which reduces nothing, flat
   const int cols = PARTIAL_STRIDE / nc;
   const dim3 grid1(std::min(stream_grid(n, 1), cols), nc), grid2(std::min(stream_grid(n, 2), cols), nc), block(VB);
-  const dim3 gridd = cg.block ? grid2 : dim3(stream_grid_flat(mf, n, 2));
+  const dim3 gridd = A.block() ? grid2 : dim3(stream_grid_flat(mf, n, 2));
   const int nblk1 = (int)grid1.x * nc, nblk2 = (int)grid2.x * nc;
   const int *no_flag = nullptr; // (the stop flag is the last solve's until the control step of the initialisation)
   SolveState ss{ApplyProfile{mf, prm->profile != 0 && !cg.precond}}; // (a callback preconditioner: the applications are not bracketed)
   ApplyProfile &prof = ss.prof;
   BP5_TRY(solve_begin(mf, prm, prof)); // (the plan below may build the block kernel's tables on a handle's first solve: inside solve_ms)
   OperatorPlan op;
-  if (!cg.block && !cg.precond) BP5_TRY(plan_operator(mf, !cg.user, true, ss, op));
-  else op.schedule = cg.user || !mf->has_neighbors() ? 0 : overlap_wanted(mf) ? 3 : 1;
+  if (!A.block() && !cg.precond) BP5_TRY(plan_operator(mf, !A.user, true, ss, op));
+  else op.schedule = A.user || !mf->has_neighbors() ? 0 : overlap_wanted(mf) ? 3 : 1;
   std::string operator_kernel; // block vectors with a callback preconditioner: the name of the solve's OWN operator kernel, for the result
   // h = A d, Dirichlet rows included (unless the dot-product kernel copies them).  Fused dot products: d.h lies in *n_cols columns of d_partials
   auto apply_A = [&](uint32_t *n_cols) -> int {
-    if (cg.user) return user_vmult(prof, cg.user, cg.user_ctx, d, h);
-    if (!cg.block) return solver_vmult(mf, ss, cg.coef, d, h, true, nullptr, op.fused_dots ? n_cols : nullptr); // (no residual vector: the write-out does not read g)
-    BP5_TRY(prof.mark(0));
-    BP5_TRY(components_zero(mf, nc, ld, h));
-    BP5_TRY(prof.mark(1));
-    if (cg.hyper_state) BP5_TRY(hyperelasticity_apply_cells(mf, cg.coef, cg.hyper_state, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
-    else if (cg.elasticity) BP5_TRY(elasticity_apply_cells(mf, cg.coef, cg.lambda, cg.mu, ld, d, h, 0, mf->n_cells));
-    else if (cg.exchange) BP5_TRY(components_apply_exchanged(mf, cg.coef, nc, ld, d, h, false));
-    else BP5_TRY(components_apply(mf, cg.coef, nc, ld, d, h, false));
+    if (A.user) return user_vmult(prof, A.user, A.user_ctx, d, h);
+    if (!A.block()) return solver_vmult(mf, ss, A.coef, d, h, true, nullptr, op.fused_dots ? n_cols : nullptr); // (no residual vector: the write-out does not read g)
+    BP5_TRY(block_op_apply(mf, A, d, h, prof));
     if (cg.precond) operator_kernel = mf->last_apply_kernel; // (a preconditioner on the same handle launches operator kernels of its own)
-    BP5_TRY(prof.mark(2));
-    BP5_TRY(components_copy_constrained(mf, nc, ld, d, h));
-    BP5_TRY(prof.mark(3));
-    if (prof.on) prof.used += 4;
     return BP5_OK;
   };
   auto apply_P = [&]() -> int {
@@ -2687,7 +2711,7 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk1, mf->d_sc + SC_GG, no_flag);
     KERNEL_CHECK();
     BP5_TRY(apply_P());
-    if (cg.block) BP5_TRY(blockvec_dot(s, grid2, g, z, n, ld, mf->d_partials)); // g.z over the owned entries of all blocks
+    if (A.block()) BP5_TRY(blockvec_dot(s, grid2, g, z, n, ld, mf->d_partials)); // g.z over the owned entries of all blocks
     else hipLaunchKernelGGL(dot_kernel, grid2, block, 0, s, g, z, n, mf->d_partials);
     hipLaunchKernelGGL(finalize_kernel<1>, dim3(1), block, 0, s, mf->d_partials, nblk2, mf->d_sc + SC_GDG, no_flag);
   } else {
@@ -2753,7 +2777,7 @@ static int cg_solve_plain(bp5_mf *mf, const PlainCG &cg, const double *b, double
     }
   }
   if (!operator_kernel.empty()) snprintf(mf->last_apply_kernel, sizeof(mf->last_apply_kernel), "%s", operator_kernel.c_str());
-  return solve_finish(mf, prof, op.fused_dots, op.schedule, !cg.user, res);
+  return solve_finish(mf, prof, op.fused_dots, op.schedule, !A.user, res);
 }
 
 // ---- SolverCGFullMerge on scalar vectors (bp5/solver.h:343-542): g == r, d == p, h == v
@@ -2929,7 +2953,7 @@ static int cg_solve_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn user, void
   if (prm->variant == BP5_CG_MERGED) return cg_solve_merged(mf, coef, user, user_ctx, diag, b, x, prm, res);
   PlainCG cg;
   cg.g = mf->ws_g; cg.d = mf->ws_d; cg.h = mf->ws_h;
-  cg.coef = coef; cg.user = user; cg.user_ctx = user_ctx;
+  cg.op = scalar_op(coef, user, user_ctx);
   cg.diag = diag;
   cg.history = history; cg.history_cap = history_cap;
   return cg_solve_plain(mf, cg, b, x, prm, res);
@@ -2947,32 +2971,43 @@ extern "C" int bp5_cg_solve_operator(bp5_mf *mf, bp5_vmult_fn vmult, void *ctx, 
   return cg_solve_impl(mf, nullptr, vmult, ctx, diag, b, x, prm, res);
 }
 
-// the work vectors g, d, h of a plain solve on block vectors: 3 n_components ld doubles of the handle, grown on demand and zero-filled (the ghost
-// entries of d are read by the operator: defined, zero); sets the vector part of `cg`
-static int block_cg_workspace(bp5_mf *mf, int n_components, size_t ld, PlainCG &cg)
+// a work array of the handle (base, cap) of `need` doubles: grown on demand -- freed only to grow, behind a synchronisation of the stream -- and
+// zero-filled on every call
+static int grown_workspace(double *&base, size_t &cap, size_t need, hipStream_t stream)
 {
-  const size_t block = (size_t)n_components * ld, need = 3 * block;
-  if (mf->wsc_cap < need) {
-    if (mf->wsc_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsc_base)); mf->wsc_base = nullptr; mf->wsc_cap = 0; }
-    HIP_TRY(hipMalloc((void **)&mf->wsc_base, need * sizeof(double)));
-    mf->wsc_cap = need;
+  if (cap < need) {
+    if (base) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(base)); base = nullptr; cap = 0; }
+    HIP_TRY(hipMalloc((void **)&base, need * sizeof(double)));
+    cap = need;
   }
-  HIP_TRY(hipMemsetAsync(mf->wsc_base, 0, need * sizeof(double), mf->stream));
-  cg.n_components = n_components; cg.ld = ld;
-  cg.g = mf->wsc_base; cg.d = cg.g + block; cg.h = cg.d + block;
+  HIP_TRY(hipMemsetAsync(base, 0, need * sizeof(double), stream));
   return BP5_OK;
 }
-// ... and z = P g of a solve with a callback preconditioner: a vector of its own, grown on demand, zero-filled (the padding of z is the callback's)
-static int block_cg_workspace_z(bp5_mf *mf, int n_components, size_t ld, PlainCG &cg)
+// the work vectors g, d, h of a plain solve on the block vectors of cg.op: 3 n_components ld doubles (the ghost entries of d are read by the
+// operator: defined, zero); with_z: and z = P g of a solve with a callback preconditioner, a vector of its own (the padding of z is the callback's)
+static int block_cg_workspace(bp5_mf *mf, PlainCG &cg, bool with_z)
 {
-  const size_t need = (size_t)n_components * ld;
-  if (mf->wsz_cap < need) {
-    if (mf->wsz_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsz_base)); mf->wsz_base = nullptr; mf->wsz_cap = 0; }
-    HIP_TRY(hipMalloc((void **)&mf->wsz_base, need * sizeof(double)));
-    mf->wsz_cap = need;
+  const size_t block = (size_t)cg.op.n_components * cg.op.ld;
+  BP5_TRY(grown_workspace(mf->wsc_base, mf->wsc_cap, 3 * block, mf->stream));
+  cg.g = mf->wsc_base; cg.d = cg.g + block; cg.h = cg.d + block;
+  if (with_z) {
+    BP5_TRY(grown_workspace(mf->wsz_base, mf->wsz_cap, block, mf->stream));
+    cg.z = mf->wsz_base;
   }
-  HIP_TRY(hipMemsetAsync(mf->wsz_base, 0, need * sizeof(double), mf->stream));
-  cg.z = mf->wsz_base;
+  return BP5_OK;
+}
+// what every CG entry point checks first, in the words of its refusing function: prm and res, the variant (plain_only: the refusal of everything
+// but BP5_CG_PLAIN, in these words), max_iter, and the 16-byte alignment of v0 and v1 (NULL: not there)
+typedef int (*Refuse)(int status, const char *what);
+static int plainly_refuse(int status, const char *what) { return fail(status, what); }
+static int cg_preamble(Refuse refuse, const bp5_cg_params *prm, const void *res, const double *v0, const double *v1, const char *misaligned,
+                       const char *plain_only = nullptr)
+{
+  if (!prm || !res) return refuse(BP5_ERR_INVALID, "null argument");
+  if (plain_only ? prm->variant != BP5_CG_PLAIN : prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED)
+    return refuse(BP5_ERR_INVALID, plain_only ? plain_only : "unknown CG variant");
+  if (prm->max_iter < 0) return refuse(BP5_ERR_INVALID, "max_iter < 0");
+  if ((v0 && !aligned16(v0)) || (v1 && !aligned16(v1))) return refuse(BP5_ERR_INVALID, misaligned);
   return BP5_OK;
 }
 // cg.solve(A, x, b, DiagonalMatrix) on a block vector: the plain recurrence on the stacked system, one launch per BLAS-1 step
@@ -2981,16 +3016,14 @@ static int block_cg_workspace_z(bp5_mf *mf, int n_components, size_t ld, PlainCG
 static int cg_solve_components_impl(bp5_mf *mf, const double *coef, int n_components, size_t ld, const double *diag, const double *b, double *x,
                                     const bp5_cg_params *prm, bp5_cg_result *res, bool with_exchange)
 {
-  if (!b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
-  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return fail(BP5_ERR_INVALID, "unknown CG variant");
-  if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
-  if (diag && !aligned16(diag)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  if (!b || !x) return fail(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(cg_preamble(plainly_refuse, prm, res, diag, nullptr, "vectors must be 16-byte aligned"));
   BP5_TRY(components_check(mf, coef, n_components, ld, b, x, with_exchange));
   if (prm->variant == BP5_CG_MERGED) return fail(BP5_ERR_UNSUPPORTED, "block vectors: SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   HIP_TRY(hipSetDevice(mf->device));
   PlainCG cg;
-  BP5_TRY(block_cg_workspace(mf, n_components, ld, cg));
-  cg.coef = coef; cg.block = true; cg.exchange = with_exchange && mf->has_neighbors();
+  cg.op = {LinearOp::BLOCK_POISSON, coef, nullptr, nullptr, n_components, ld, with_exchange && mf->has_neighbors()};
+  BP5_TRY(block_cg_workspace(mf, cg, false));
   cg.diag = diag;
   cg.allreduce = with_exchange;
   return cg_solve_plain(mf, cg, b, x, prm, res);
@@ -3014,10 +3047,7 @@ static int cg_solve_elasticity_impl(bp5_mf *mf, const double *coef, double lambd
                                     void *precond_ctx, const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res, double *history = nullptr,
                                     int history_cap = 0)
 {
-  if (!prm || !res) return elasticity_refuse(BP5_ERR_INVALID, "null argument");
-  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return elasticity_refuse(BP5_ERR_INVALID, "unknown CG variant");
-  if (prm->max_iter < 0) return elasticity_refuse(BP5_ERR_INVALID, "max_iter < 0");
-  if (inv_diag && !aligned16(inv_diag)) return elasticity_refuse(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
+  BP5_TRY(cg_preamble(elasticity_refuse, prm, res, inv_diag, nullptr, "block vectors must be 16-byte aligned"));
   BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, b, x, true));
   if (inv_diag) { // the update kernels read it while they write x
     const size_t extent = 2 * ld + mf->n_local();
@@ -3026,14 +3056,11 @@ static int cg_solve_elasticity_impl(bp5_mf *mf, const double *coef, double lambd
   if (prm->variant == BP5_CG_MERGED) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   HIP_TRY(hipSetDevice(mf->device));
   PlainCG cg;
-  BP5_TRY(block_cg_workspace(mf, 3, ld, cg));
-  cg.coef = coef; cg.block = true; cg.elasticity = true; cg.lambda = lambda; cg.mu = mu;
+  cg.op = elasticity_op(coef, lambda, mu, ld);
+  BP5_TRY(block_cg_workspace(mf, cg, precond != nullptr));
   cg.diag = inv_diag; cg.diag_ld = ld;
   cg.allreduce = false;
-  if (precond) {
-    BP5_TRY(block_cg_workspace_z(mf, 3, ld, cg));
-    cg.precond = precond; cg.precond_ctx = precond_ctx;
-  }
+  cg.precond = precond; cg.precond_ctx = precond_ctx;
   cg.history = history; cg.history_cap = history_cap;
   return cg_solve_plain(mf, cg, b, x, prm, res);
 }
@@ -3104,9 +3131,7 @@ extern "C" int bp5_hyperelasticity_apply_cells(bp5_mf *mf, const double *coef, c
 static int cg_solve_hyperelasticity_check(const bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, const double *b, const double *x,
                                           const bp5_cg_params *prm, const void *res)
 {
-  if (!prm || !res) return hyperelasticity_refuse(BP5_ERR_INVALID, "null argument");
-  if (prm->variant != BP5_CG_PLAIN && prm->variant != BP5_CG_MERGED) return hyperelasticity_refuse(BP5_ERR_INVALID, "unknown CG variant");
-  if (prm->max_iter < 0) return hyperelasticity_refuse(BP5_ERR_INVALID, "max_iter < 0");
+  BP5_TRY(cg_preamble(hyperelasticity_refuse, prm, res, nullptr, nullptr, ""));
   BP5_TRY(hyperelasticity_check(mf, coef, state, lambda, mu, ld, b, x));
   if (prm->variant == BP5_CG_MERGED) return hyperelasticity_refuse(BP5_ERR_UNSUPPORTED, "SolverCGFullMerge (BP5_CG_MERGED) is not offered, use BP5_CG_PLAIN");
   return BP5_OK;
@@ -3116,13 +3141,10 @@ static int cg_solve_hyperelasticity(bp5_mf *mf, const double *coef, const double
                                     const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
   PlainCG cg;
-  BP5_TRY(block_cg_workspace(mf, 3, ld, cg));
-  cg.coef = coef; cg.block = true; cg.elasticity = true; cg.hyper_state = state; cg.lambda = lambda; cg.mu = mu;
+  cg.op = elasticity_op(coef, lambda, mu, ld, state);
+  BP5_TRY(block_cg_workspace(mf, cg, precond != nullptr));
   cg.allreduce = false;
-  if (precond) {
-    BP5_TRY(block_cg_workspace_z(mf, 3, ld, cg));
-    cg.precond = precond; cg.precond_ctx = precond_ctx;
-  }
+  cg.precond = precond; cg.precond_ctx = precond_ctx;
   return cg_solve_plain(mf, cg, b, x, prm, res);
 }
 extern "C" int bp5_cg_solve_hyperelasticity(bp5_mf *mf, const double *coef, const double *state, double lambda, double mu, size_t ld, bp5_vmult_fn precond,
@@ -3144,13 +3166,8 @@ extern "C" int bp5_hyperelasticity_newton(bp5_mf *mf, const double *coef, double
   bp5_cg_result cr;
   BP5_TRY(cg_solve_hyperelasticity_check(mf, coef, state, lambda, mu, ld, f_ext, u, &prm->cg, &cr));
   HIP_TRY(hipSetDevice(mf->device));
-  const size_t need = 9 * ld, nl = mf->n_local();
-  if (mf->wsn_cap < need) {
-    if (mf->wsn_base) { HIP_TRY(hipStreamSynchronize(mf->stream)); HIP_TRY(hipFree(mf->wsn_base)); mf->wsn_base = nullptr; mf->wsn_cap = 0; }
-    HIP_TRY(hipMalloc((void **)&mf->wsn_base, need * sizeof(double)));
-    mf->wsn_cap = need;
-  }
-  HIP_TRY(hipMemsetAsync(mf->wsn_base, 0, need * sizeof(double), mf->stream)); // (the padding of the three work vectors)
+  const size_t nl = mf->n_local();
+  BP5_TRY(grown_workspace(mf->wsn_base, mf->wsn_cap, 9 * ld, mf->stream)); // (zero-filled: the padding of the three work vectors)
   double *delta = mf->wsn_base, *trial = delta + 3 * ld, *r = trial + 3 * ld;
   // r = f_ext - F_int(v) with zeros on the Dirichlet rows, and its stacked l2 norm over the owned entries
   auto residual = [&](const double *v, double *norm) -> int {
@@ -3210,10 +3227,9 @@ extern "C" int bp5_hyperelasticity_newton(bp5_mf *mf, const double *coef, double
 extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, bp5_vmult_fn precond, void *precond_ctx,
                                            const double *b, double *x, const bp5_cg_params *prm, bp5_cg_result *res)
 {
-  if (!mf || (!vmult && !coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !precond || !b || !x || !prm || !res) return fail(BP5_ERR_INVALID, "null argument");
-  if (prm->variant != BP5_CG_PLAIN) return fail(BP5_ERR_INVALID, "a general preconditioner needs BP5_CG_PLAIN (SolverCGFullMerge takes a diagonal only)");
-  if (prm->max_iter < 0) return fail(BP5_ERR_INVALID, "max_iter < 0");
-  if (!aligned16(b) || !aligned16(x)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
+  if (!mf || (!vmult && !coef && mf->geometry_mode == BP5_GEOM_MERGED6) || !precond || !b || !x) return fail(BP5_ERR_INVALID, "null argument");
+  BP5_TRY(cg_preamble(plainly_refuse, prm, res, b, x, "vectors must be 16-byte aligned",
+                      "a general preconditioner needs BP5_CG_PLAIN (SolverCGFullMerge takes a diagonal only)"));
   HIP_TRY(hipSetDevice(mf->device));
   BP5_TRY(ensure_ws(mf));
   if (!mf->ws_z) {
@@ -3222,7 +3238,7 @@ extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_v
   }
   PlainCG cg;
   cg.g = mf->ws_g; cg.d = mf->ws_d; cg.h = mf->ws_h;
-  cg.coef = coef; cg.user = vmult; cg.user_ctx = ctx;
+  cg.op = scalar_op(coef, vmult, ctx);
   cg.precond = precond; cg.precond_ctx = precond_ctx; cg.z = mf->ws_z;
   return cg_solve_plain(mf, cg, b, x, prm, res);
 }
@@ -3230,33 +3246,33 @@ extern "C" int bp5_cg_solve_preconditioned(bp5_mf *mf, const double *coef, bp5_v
 // ------------------------------------------------------------------------------------ PreconditionChebyshev
 struct bp5_chebyshev {
   bp5_mf *mf = nullptr;
-  const double *coef = nullptr;
-  bp5_vmult_fn vmult = nullptr;
-  void *ctx = nullptr;
+  // the operator: native, a callback, or (bp5_elasticity_chebyshev_create) the coupled elasticity one -- then every vector is three blocks op.ld
+  // apart, w and t too, and inv_diag a BLOCK inverse diagonal (blocks op.ld apart)
+  LinearOp op;
   const double *inv_diag = nullptr;
   int degree = 1;
   double min_est = 0.0, max_est = 0.0, min_used = 0.0, max_used = 0.0, theta = 1.0, delta = 0.0;
   int cg_its = 0;
   std::vector<double> f1, f2; // step k = 1 .. degree-1
   double *w = nullptr, *t = nullptr; // the other iterate and t = A x_k: owned + ghost each (one allocation)
-  // bp5_elasticity_chebyshev_create: the operator is the coupled elasticity one (coef: its ten planes) and every vector three blocks ld apart --
-  // w and t too; inv_diag is then a BLOCK inverse diagonal (blocks ld apart)
-  bool elasticity = false;
-  double lambda = 0.0, mu = 0.0;
-  size_t ld = 0;
 };
 
 // t = A x in overwrite mode (zero_dst = 1 and the Dirichlet copy); the distributed apply when there are neighbours
 static int cheb_apply(bp5_chebyshev *c, double *x, double *t)
 {
-  if (c->elasticity) return bp5_elasticity_apply(c->mf, c->coef, c->lambda, c->mu, c->ld, x, t, 1);
-  if (c->vmult) {
-    const int st = c->vmult(c->ctx, t, x);
+  bp5_mf *mf = c->mf;
+  const LinearOp &A = c->op;
+  if (A.block()) { // (the arguments were checked when the handle was made)
+    ApplyProfile none{mf, false};
+    HIP_TRY(hipSetDevice(mf->device));
+    return block_op_apply(mf, A, x, t, none);
+  }
+  if (A.user) {
+    const int st = A.user(A.user_ctx, t, x);
     return st == BP5_OK ? BP5_OK : fail(st, "the operator's vmult callback reported a failure");
   }
-  bp5_mf *mf = c->mf;
-  if (mf->has_neighbors()) return bp5_apply_distributed(mf, c->coef, x, t, 1);
-  return bp5_apply(mf, c->coef, x, t, 1);
+  if (mf->has_neighbors()) return bp5_apply_distributed(mf, A.coef, x, t, 1);
+  return bp5_apply(mf, A.coef, x, t, 1);
 }
 
 // one Chebyshev step kernel (blockvec/bp5_blockvec.hip): FORM as chebyshev_step_kernel, the streaming policy (BP5_TUNE_UPDATE_NT) and the flat launch
@@ -3268,16 +3284,16 @@ static int cheb_step_launch(bp5_chebyshev *c, double *x_new, const double *x, co
   const size_t n = mf->n_owned;
   if (!n) return BP5_OK;
   const unsigned grid_x = stream_grid_flat(mf, n, 2);
-  return blockvec_chebyshev_step(mf->stream, FORM, grid_x, c->elasticity ? 3 : 1, mf->tune[BP5_TUNE_UPDATE_NT] != 0, x_new, x, x_old, src, c->t, c->inv_diag, n, c->ld,
-                                 c->ld, f1, f2);
+  return blockvec_chebyshev_step(mf->stream, FORM, grid_x, c->op.n_components, mf->tune[BP5_TUNE_UPDATE_NT] != 0, x_new, x, x_old, src, c->t, c->inv_diag, n, c->op.ld,
+                                 c->op.ld, f1, f2);
 }
 
-// el_ld != 0 (bp5_elasticity_chebyshev_create, which has checked handle, layout and parameters): the elasticity operator on three-block vectors
-// el_ld apart, inv_diag a block inverse diagonal
-static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag, const bp5_chebyshev_params *prm,
-                                 bp5_chebyshev **out, size_t el_ld = 0, double lambda = 0.0, double mu = 0.0)
+// op: a scalar operator, or the elasticity one (bp5_elasticity_chebyshev_create, which has checked handle, layout and parameters) on three-block
+// vectors op.ld apart, inv_diag then a block inverse diagonal
+static int chebyshev_create_impl(bp5_mf *mf, const LinearOp &op, const double *inv_diag, const bp5_chebyshev_params *prm, bp5_chebyshev **out)
 {
-  if (!mf || !prm || !out || (!vmult && !coef && mf->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "null argument");
+  const size_t el_ld = op.ld;
+  if (!mf || !prm || !out || (!op.user && !op.coef && mf->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "null argument");
   *out = nullptr;
   if (prm->degree < 1) return fail(BP5_ERR_INVALID, "Chebyshev degree < 1");
   const bool given = prm->max_eigenvalue > 0.0 && prm->min_eigenvalue > 0.0;
@@ -3286,8 +3302,7 @@ static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vm
   if (inv_diag && !aligned16(inv_diag)) return fail(BP5_ERR_INVALID, "vectors must be 16-byte aligned");
   HIP_TRY(hipSetDevice(mf->device));
   std::unique_ptr<bp5_chebyshev> c(new bp5_chebyshev);
-  c->mf = mf; c->coef = coef; c->vmult = vmult; c->ctx = ctx; c->inv_diag = inv_diag; c->degree = prm->degree;
-  c->elasticity = el_ld != 0; c->ld = el_ld; c->lambda = lambda; c->mu = mu;
+  c->mf = mf; c->op = op; c->inv_diag = inv_diag; c->degree = prm->degree;
   const size_t nb = (std::max<size_t>(el_ld ? 3 * el_ld : mf->n_local(), 2) * sizeof(double) + 4095) / 4096 * 4096;
   char *base = nullptr;
   HIP_TRY(hipMalloc((void **)&base, 2 * nb));
@@ -3301,7 +3316,7 @@ static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vm
   } else {
     // Jacobi-PCG on A x = v (x_0 = 0) with the alpha / beta history on the device; one copy to the host at the end
     const int m = prm->eig_cg_n_iterations;
-    const int n_blocks = el_ld ? 3 : 1;
+    const int n_blocks = op.n_components;
     std::vector<double> v(std::max<size_t>(mf->n_owned, 1) * n_blocks, 0.0);
     for (int cb = 0; cb < n_blocks; ++cb)
       for (uint32_t i = 0; i < mf->n_owned; ++i) {
@@ -3325,8 +3340,8 @@ static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vm
     bp5_cg_params cp{};
     cp.variant = BP5_CG_PLAIN; cp.max_iter = m; cp.abs_tol = 1e-5 * vnorm; cp.check_every = 0; cp.profile = 0;
     bp5_cg_result cr{};
-    if (el_ld) BP5_TRY(cg_solve_elasticity_impl(mf, coef, lambda, mu, el_ld, inv_diag, nullptr, nullptr, vb, xs, &cp, &cr, hist, m));
-    else BP5_TRY(cg_solve_impl(mf, coef, vmult, ctx, inv_diag, vb, xs, &cp, &cr, hist, m));
+    if (op.block()) BP5_TRY(cg_solve_elasticity_impl(mf, op.coef, op.lambda, op.mu, el_ld, inv_diag, nullptr, nullptr, vb, xs, &cp, &cr, hist, m));
+    else BP5_TRY(cg_solve_impl(mf, op.coef, op.user, op.user_ctx, inv_diag, vb, xs, &cp, &cr, hist, m));
     std::vector<double> h(2 * (size_t)m);
     HIP_TRY(hipMemcpy(h.data(), hist, h.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int k = cr.iterations;
@@ -3361,7 +3376,7 @@ static int chebyshev_create_impl(bp5_mf *mf, const double *coef, bp5_vmult_fn vm
 extern "C" int bp5_chebyshev_create(bp5_mf *mf, const double *coef, bp5_vmult_fn vmult, void *ctx, const double *inv_diag,
                                     const bp5_chebyshev_params *prm, bp5_chebyshev **out)
 {
-  return chebyshev_create_impl(mf, coef, vmult, ctx, inv_diag, prm, out);
+  return chebyshev_create_impl(mf, scalar_op(coef, vmult, ctx), inv_diag, prm, out);
 }
 // PreconditionChebyshev for the elasticity operator: the same handle type, every vector three blocks ld apart, the estimate Jacobi-PCG on the
 // stacked system (one Krylov space) with the block inverse diagonal
@@ -3373,7 +3388,7 @@ extern "C" int bp5_elasticity_chebyshev_create(bp5_mf *mf, const double *coef, d
   if (inv_diag && !aligned16(inv_diag)) return elasticity_refuse(BP5_ERR_INVALID, "block vectors must be 16-byte aligned");
   if (inv_diag) BP5_TRY(elasticity_check(mf, coef, lambda, mu, ld, inv_diag, nullptr, false));
   else BP5_TRY(elasticity_check_no_vector(mf, coef, lambda, mu, ld));
-  return chebyshev_create_impl(mf, coef, nullptr, nullptr, inv_diag, prm, out, ld, lambda, mu);
+  return chebyshev_create_impl(mf, elasticity_op(coef, lambda, mu, ld), inv_diag, prm, out);
 }
 
 extern "C" int bp5_chebyshev_eigenvalues(const bp5_chebyshev *c, double *min_est, double *max_est, double *min_used, double *max_used, int *cg_its)
@@ -3416,8 +3431,8 @@ extern "C" int bp5_chebyshev_step(bp5_chebyshev *c, double *dst, double *src)
   bp5_mf *mf = c->mf;
   double *a = dst, *b = c->w; // a: x_0, x_2, ...   b: x_1, x_3, ...
   if (c->degree & 1) {
-    for (int cb = 0; cb < (c->elasticity ? 3 : 1); ++cb) // (block by block: the padding of dst is not read)
-      HIP_TRY(hipMemcpyAsync(c->w + (size_t)cb * c->ld, dst + (size_t)cb * c->ld, mf->n_owned * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
+    for (int cb = 0; cb < c->op.n_components; ++cb) // (block by block: the padding of dst is not read)
+      HIP_TRY(hipMemcpyAsync(c->w + (size_t)cb * c->op.ld, dst + (size_t)cb * c->op.ld, mf->n_owned * sizeof(double), hipMemcpyDeviceToDevice, mf->stream));
     a = c->w; b = dst;
   }
   BP5_TRY(cheb_apply(c, a, c->t));
@@ -3778,16 +3793,13 @@ extern "C" int bp5_mg_transfer_destroy(bp5_mg_transfer *t)
 struct bp5_mg {
   int n_levels = 0;
   std::vector<bp5_mf *> mf;
-  std::vector<const double *> coef;
+  // per level: its operator on its own metric.  bp5_elasticity_mg_create: the elasticity one with (lambda, mu), every vector three blocks op[l].ld
+  // apart (op[0].ld: the caller's; below: the level's n_local rounded up to even); scalar levels: ld = 0
+  std::vector<LinearOp> op;
   std::vector<bp5_mg_transfer *> tr;
   std::vector<bp5_chebyshev *> cheb;          // [l]: the smoother; [n_levels - 1]: the coarse solver
   std::vector<double *> inv_diag, x, b, t;    // per level; x, b of levels >= 1 (level 0: the caller's dst, src); t of levels < n_levels - 1
   std::vector<void *> allocs;
-  // bp5_elasticity_mg_create: every level's operator is the elasticity one with (lambda, mu), coef its ten planes, every vector three blocks
-  // ld[l] apart (ld[0]: the caller's; below: the level's n_local rounded up to even)
-  bool elasticity = false;
-  double lambda = 0.0, mu = 0.0;
-  std::vector<size_t> ld;
 };
 
 extern "C" void bp5_mg_params_default(bp5_mg_params *p)
@@ -3815,25 +3827,33 @@ extern "C" int bp5_mg_destroy(bp5_mg *mg)
   return BP5_OK;
 }
 
-extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, bp5_mg_transfer *const *transfers, const bp5_mg_params *prm,
-                             bp5_mg **out)
+// what both constructors check first (null arguments -- in the words `null_words` --, *out = NULL, the Chebyshev degrees) ...
+static int mg_arguments_check(Refuse refuse, const char *null_words, int n_levels, bp5_mf *const *mfs, const double *const *coefs,
+                              bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
 {
-  if (n_levels < 1 || !mfs || !coefs || !prm || !out || (n_levels > 1 && !transfers)) return fail(BP5_ERR_INVALID, "null argument or n_levels < 1");
+  if (n_levels < 1 || !mfs || !coefs || !prm || !out || (n_levels > 1 && !transfers)) return refuse(BP5_ERR_INVALID, null_words);
   *out = nullptr;
-  if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return fail(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
-  for (int l = 0; l < n_levels; ++l) {
-    if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
-    if (mfs[l]->stream != mfs[0]->stream) return fail(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
-    if (mfs[l]->overint()) return overint_refuse("multigrid levels are not supported");
-  }
+  if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return refuse(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
+  return BP5_OK;
+}
+// ... and last
+static int mg_transfers_check(Refuse refuse, int n_levels, bp5_mf *const *mfs, bp5_mg_transfer *const *transfers)
+{
   for (int l = 0; l + 1 < n_levels; ++l)
     if (!transfers[l] || transfers[l]->fine != mfs[l] || transfers[l]->coarse != mfs[l + 1])
-      return fail(BP5_ERR_INVALID, "multigrid: transfers[l] must connect mfs[l] (fine) and mfs[l + 1] (coarse)");
+      return refuse(BP5_ERR_INVALID, "multigrid: transfers[l] must connect mfs[l] (fine) and mfs[l + 1] (coarse)");
+  return BP5_OK;
+}
+// the V-cycle handle of checked arguments: per level the inverse diagonal, the work vectors (op[l].n_components blocks op[l].ld apart; scalar
+// levels: n_local doubles), the transfer's slots and the Chebyshev smoother (the last level: the coarse solver) of the level's operator
+static int mg_create_impl(int n_levels, bp5_mf *const *mfs, const std::vector<LinearOp> &ops, bp5_mg_transfer *const *transfers, const bp5_mg_params *prm,
+                          bp5_mg **out)
+{
   HIP_TRY(hipSetDevice(mfs[0]->device));
   std::unique_ptr<bp5_mg, int (*)(bp5_mg *)> mg(new bp5_mg, bp5_mg_destroy);
   mg->n_levels = n_levels;
   mg->mf.assign(mfs, mfs + n_levels);
-  mg->coef.assign(coefs, coefs + n_levels);
+  mg->op = ops;
   mg->tr.assign(transfers, transfers + (n_levels - 1));
   mg->inv_diag.assign(n_levels, nullptr);
   mg->x.assign(n_levels, nullptr);
@@ -3847,11 +3867,17 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   };
   for (int l = 0; l < n_levels; ++l) {
     bp5_mf *m = mfs[l];
-    const size_t nl = m->n_local();
-    BP5_TRY(alloc(&mg->inv_diag[l], nl));
-    if (l > 0) { BP5_TRY(alloc(&mg->x[l], nl)); BP5_TRY(alloc(&mg->b[l], nl)); }
-    if (l + 1 < n_levels) BP5_TRY(alloc(&mg->t[l], nl));
-    BP5_TRY(bp5_compute_diagonal(m, coefs[l], mg->inv_diag[l], 1));
+    const LinearOp &A = ops[l];
+    const size_t len = A.block() ? A.n_components * A.ld : m->n_local();
+    BP5_TRY(alloc(&mg->inv_diag[l], len));
+    if (l > 0) { BP5_TRY(alloc(&mg->x[l], len)); BP5_TRY(alloc(&mg->b[l], len)); }
+    if (l + 1 < n_levels) {
+      BP5_TRY(alloc(&mg->t[l], len));
+      double *slots = nullptr;
+      BP5_TRY(mg_reserve_slots(mg->tr[l], A.n_components, &slots)); // at setup: nothing allocates inside vmult (one component: the transfer's own)
+    }
+    if (A.block()) BP5_TRY(bp5_elasticity_compute_diagonal(m, A.coef, A.lambda, A.mu, A.ld, mg->inv_diag[l], 1));
+    else BP5_TRY(bp5_compute_diagonal(m, A.coef, mg->inv_diag[l], 1));
     const bool coarsest = l + 1 == n_levels;
     bp5_chebyshev_params cp{};
     cp.degree = coarsest ? prm->coarse_degree : prm->smoother_degree;
@@ -3859,7 +3885,7 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
     cp.eig_cg_n_iterations = coarsest ? prm->coarse_eig_cg_n_iterations : prm->eig_cg_n_iterations;
     cp.start_ids_host = prm->start_ids_host ? prm->start_ids_host[l] : nullptr;
     bp5_chebyshev *c = nullptr;
-    BP5_TRY(bp5_chebyshev_create(m, coefs[l], nullptr, nullptr, mg->inv_diag[l], &cp, &c));
+    BP5_TRY(chebyshev_create_impl(m, A, mg->inv_diag[l], &cp, &c));
     mg->cheb.push_back(c);
   }
   HIP_TRY(hipStreamSynchronize(mfs[0]->stream));
@@ -3867,13 +3893,26 @@ extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *con
   return BP5_OK;
 }
 
-// The elasticity V-cycle (bp5_elasticity_mg_create): mg_level on three-block vectors
-static int elasticity_mg_create_check(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
-                                      bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
+extern "C" int bp5_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, bp5_mg_transfer *const *transfers, const bp5_mg_params *prm,
+                             bp5_mg **out)
 {
-  if (n_levels < 1 || !mfs || !coefs || !prm || !out || (n_levels > 1 && !transfers)) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: null argument or n_levels < 1");
-  *out = nullptr;
-  if (prm->smoother_degree < 1 || prm->coarse_degree < 1) return elasticity_refuse(BP5_ERR_INVALID, "multigrid: Chebyshev degrees must be >= 1");
+  BP5_TRY(mg_arguments_check(plainly_refuse, "null argument or n_levels < 1", n_levels, mfs, coefs, transfers, prm, out));
+  for (int l = 0; l < n_levels; ++l) {
+    if (!mfs[l] || (!coefs[l] && mfs[l]->geometry_mode == BP5_GEOM_MERGED6)) return fail(BP5_ERR_INVALID, "multigrid: null level handle or metric");
+    if (mfs[l]->stream != mfs[0]->stream) return fail(BP5_ERR_INVALID, "multigrid: the levels must share one stream");
+    if (mfs[l]->overint()) return overint_refuse("multigrid levels are not supported");
+  }
+  BP5_TRY(mg_transfers_check(plainly_refuse, n_levels, mfs, transfers));
+  std::vector<LinearOp> ops;
+  for (int l = 0; l < n_levels; ++l) ops.push_back(scalar_op(coefs[l], nullptr, nullptr));
+  return mg_create_impl(n_levels, mfs, ops, transfers, prm, out);
+}
+
+// The elasticity V-cycle: mg_level on three-block vectors
+extern "C" int bp5_elasticity_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
+                                        bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
+{
+  BP5_TRY(mg_arguments_check(elasticity_refuse, "multigrid: null argument or n_levels < 1", n_levels, mfs, coefs, transfers, prm, out));
   if (ld & 1) return elasticity_refuse(BP5_ERR_INVALID, "ld must be even (every block 16-byte aligned)");
   BP5_TRY(elasticity_parameter_check(lambda, mu));
   for (int l = 0; l < n_levels; ++l) {
@@ -3887,66 +3926,19 @@ static int elasticity_mg_create_check(int n_levels, bp5_mf *const *mfs, const do
     // the coarse polynomial is no solver for a singular level (the rigid-body modes), and a smoother's estimate has no meaning on one
     if (!mfs[l]->n_constrained) return elasticity_refuse(BP5_ERR_UNSUPPORTED, "multigrid: a level without Dirichlet DoFs is singular (rigid-body modes)");
   }
-  for (int l = 0; l + 1 < n_levels; ++l)
-    if (!transfers[l] || transfers[l]->fine != mfs[l] || transfers[l]->coarse != mfs[l + 1])
-      return elasticity_refuse(BP5_ERR_INVALID, "multigrid: transfers[l] must connect mfs[l] (fine) and mfs[l + 1] (coarse)");
-  return BP5_OK;
-}
-extern "C" int bp5_elasticity_mg_create(int n_levels, bp5_mf *const *mfs, const double *const *coefs, double lambda, double mu, size_t ld,
-                                        bp5_mg_transfer *const *transfers, const bp5_mg_params *prm, bp5_mg **out)
-{
-  BP5_TRY(elasticity_mg_create_check(n_levels, mfs, coefs, lambda, mu, ld, transfers, prm, out));
-  HIP_TRY(hipSetDevice(mfs[0]->device));
-  std::unique_ptr<bp5_mg, int (*)(bp5_mg *)> mg(new bp5_mg, bp5_mg_destroy);
-  mg->n_levels = n_levels;
-  mg->elasticity = true; mg->lambda = lambda; mg->mu = mu;
-  mg->mf.assign(mfs, mfs + n_levels);
-  mg->coef.assign(coefs, coefs + n_levels);
-  mg->tr.assign(transfers, transfers + (n_levels - 1));
-  mg->inv_diag.assign(n_levels, nullptr);
-  mg->x.assign(n_levels, nullptr);
-  mg->b.assign(n_levels, nullptr);
-  mg->t.assign(n_levels, nullptr);
-  mg->ld.assign(n_levels, 0);
-  auto alloc = [&](double **p, size_t n) -> int {
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 2) * sizeof(double)));
-    mg->allocs.push_back(*p);
-    HIP_TRY(hipMemsetAsync(*p, 0, std::max<size_t>(n, 2) * sizeof(double), mfs[0]->stream));
-    return BP5_OK;
-  };
-  for (int l = 0; l < n_levels; ++l) {
-    bp5_mf *m = mfs[l];
-    const size_t ldl = l == 0 ? ld : std::max<size_t>((m->n_local() + 1) & ~(size_t)1, 2);
-    mg->ld[l] = ldl;
-    BP5_TRY(alloc(&mg->inv_diag[l], 3 * ldl));
-    if (l > 0) { BP5_TRY(alloc(&mg->x[l], 3 * ldl)); BP5_TRY(alloc(&mg->b[l], 3 * ldl)); }
-    if (l + 1 < n_levels) {
-      BP5_TRY(alloc(&mg->t[l], 3 * ldl));
-      double *slots = nullptr;
-      BP5_TRY(mg_reserve_slots(mg->tr[l], 3, &slots)); // at setup: nothing allocates inside vmult
-    }
-    BP5_TRY(bp5_elasticity_compute_diagonal(m, coefs[l], lambda, mu, ldl, mg->inv_diag[l], 1));
-    const bool coarsest = l + 1 == n_levels;
-    bp5_chebyshev_params cp{};
-    cp.degree = coarsest ? prm->coarse_degree : prm->smoother_degree;
-    cp.smoothing_range = coarsest ? prm->coarse_range : prm->smoothing_range;
-    cp.eig_cg_n_iterations = coarsest ? prm->coarse_eig_cg_n_iterations : prm->eig_cg_n_iterations;
-    cp.start_ids_host = prm->start_ids_host ? prm->start_ids_host[l] : nullptr;
-    bp5_chebyshev *c = nullptr;
-    BP5_TRY(bp5_elasticity_chebyshev_create(m, coefs[l], lambda, mu, ldl, mg->inv_diag[l], &cp, &c));
-    mg->cheb.push_back(c);
-  }
-  HIP_TRY(hipStreamSynchronize(mfs[0]->stream));
-  *out = mg.release();
-  return BP5_OK;
+  BP5_TRY(mg_transfers_check(elasticity_refuse, n_levels, mfs, transfers));
+  std::vector<LinearOp> ops;
+  for (int l = 0; l < n_levels; ++l)
+    ops.push_back(elasticity_op(coefs[l], lambda, mu, l == 0 ? ld : std::max<size_t>((mfs[l]->n_local() + 1) & ~(size_t)1, 2)));
+  return mg_create_impl(n_levels, mfs, ops, transfers, prm, out);
 }
 // one level of the V-cycle.  The scalar and the elasticity cycle are the same steps: the level's Chebyshev handle knows its operator (elasticity,
-// distributed or plain apply on the level's own metric), and the vectors are 1 block or 3 blocks ld[l] apart
+// distributed or plain apply on the level's own metric), and the vectors are the op[l].n_components blocks, op[l].ld apart, of its descriptor
 static int mg_level(bp5_mg *mg, int l, double *x, double *b)
 {
   if (l + 1 == mg->n_levels) return bp5_chebyshev_vmult(mg->cheb[l], x, b);
-  const int nc = mg->elasticity ? 3 : 1;
-  const size_t ld = mg->elasticity ? mg->ld[l] : 0, ldc = mg->elasticity ? mg->ld[l + 1] : 0;
+  const int nc = mg->op[l].n_components;
+  const size_t ld = mg->op[l].ld, ldc = mg->op[l + 1].ld;
   BP5_TRY(bp5_chebyshev_vmult(mg->cheb[l], x, b));                                   // pre-smoothing from zero
   BP5_TRY(cheb_apply(mg->cheb[l], x, mg->t[l]));                                     // t = A x
   BP5_TRY(mg_restrict(mg->tr[l], nc, ldc, mg->b[l + 1], ld, b, mg->t[l], false));    // b_c = P^T (w (.) (b - t)), Dirichlet rows 0

@@ -703,66 +703,88 @@ def _callback(obj, mf, failure):
     return _lib.VMULT_FN(callback)
 
 
-class PreconditionChebyshev:
-    """== PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (deal.II): a Chebyshev polynomial of degree `degree` in D^-1 A on the
-    eigenvalue bounds of D^-1 A, estimated at initialize() by a few CG-Lanczos steps (bp5_chebyshev_create, include/bp5.h).  vmult is
-    degree-1 operator applications and degree pointwise step launches, with no dot product: only the operator's halo exchanges.
+def _even_ld(mf):
+    return mf.n_local + (mf.n_local & 1)
 
-    A: a PoissonOperator / HelmholtzOperator (its coef, natively) or any object with `mf_data` and `vmult(dst, src)` (through a
-    callback).  AdditionalData.preconditioner: a DiagonalMatrix holding the INVERSE diagonal (compute_diagonal(invert=True)), None = identity."""
 
-    class AdditionalData:
-        def __init__(self, degree=1, smoothing_range=0.0, eig_cg_n_iterations=8, max_eigenvalue=0.0, min_eigenvalue=0.0, preconditioner=None):
-            self.degree, self.smoothing_range, self.eig_cg_n_iterations = int(degree), float(smoothing_range), int(eig_cg_n_iterations)
-            self.max_eigenvalue, self.min_eigenvalue = float(max_eigenvalue), float(min_eigenvalue)
-            self.preconditioner = preconditioner
+def _global_ids(mf):
+    ids = getattr(mf.mesh, "global_ids", None)
+    return np.ascontiguousarray(ids[:mf.n_owned], dtype=np.uint64) if ids is not None else None
+
+
+class _NativePreconditioner:
+    """A preconditioner that lives in the library: the handle, its end, and the (callback pointer, context) pair the C solvers take.
+    Subclasses: _VMULT / _DESTROY (the C entries), _NO_HANDLE (what a missing handle means), _vectors (the vector shape they accept)."""
+
+    _failure = ()                    # (exceptions of a Python operator callback: PreconditionChebyshev only)
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise BP5Error(1, self._NO_HANDLE.format(type(self).__name__))
+        return self._h
+
+    def _native(self):
+        return C.cast(getattr(_lib.lib(), self._VMULT), C.c_void_p), self.handle
+
+    def _vectors(self, dst, src):
+        """the pointers of scalar vectors (owned + ghost); block vectors are refused"""
+        n = self.mf_data.n_local
+        _refuse_blocks(type(self).__name__, dst, src)
+        return _ptr(_vals(dst), n), _ptr(_vals(src), n)
+
+    def _run(self, fn, dst, src):
+        pdst, psrc = self._vectors(dst, src)
+        status = fn(self.handle, pdst, psrc)
+        if self._failure:
+            raise self._failure.pop(0)
+        _lib.check(status)
+
+    def clear(self):
+        if self._h:
+            getattr(_lib.lib(), self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.clear()
+        except Exception:
+            pass
+
+
+def _elasticity_vectors(pre, op, dst, src):
+    """_vectors of the elasticity preconditioners: (3, ld) tensors of the ld `pre` was initialised for"""
+    dst, src = _vals(dst), _vals(src)
+    if op._args(dst, src) != pre.ld:
+        raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {pre.ld}, the vectors have {dst.shape[1]}")
+    return _ptr(dst), _ptr(src)
+
+
+class _ChebyshevBase(_NativePreconditioner):
+    _VMULT, _DESTROY, _NO_HANDLE = "bp5_chebyshev_vmult", "bp5_chebyshev_destroy", "{}.initialize has not been called"
 
     def __init__(self):
         self._h = None
         self._keep = []
 
-    def initialize(self, A, data=None):
-        self.clear()
-        _refuse_elasticity("PreconditionChebyshev", A)
-        data = data if data is not None else PreconditionChebyshev.AdditionalData()
+    def _create(self, A, data, keep, create):
+        """the end of initialize(): create(prm, h) is the subclass's C create call; `keep` lives as long as the handle"""
         mf = A.mf_data
         self.A, self.mf_data, self.data = A, mf, data
-        inv = _vals(data.preconditioner.get_vector()) if data.preconditioner is not None else None
-        ids = getattr(mf.mesh, "global_ids", None)
-        ids = np.ascontiguousarray(ids[:mf.n_owned], dtype=np.uint64) if ids is not None else None
+        ids = _global_ids(mf)
         prm = _lib.ChebyshevParams(data.degree, data.smoothing_range, data.eig_cg_n_iterations, data.max_eigenvalue, data.min_eigenvalue,
                                    ids.ctypes.data if ids is not None else None)
-        self._failure = []
-        if isinstance(A, PoissonOperator):
-            coef, cb = _ptr(A.coef), None
-        else:
-            coef, cb = None, _callback(A, mf, self._failure)
         h = C.c_void_p()
-        status = _lib.lib().bp5_chebyshev_create(mf.handle, coef, C.cast(cb, C.c_void_p) if cb is not None else None, None,
-                                                 _ptr(inv, mf.n_owned) if inv is not None else None, C.byref(prm), C.byref(h))
+        status = create(prm, h)
         if self._failure:
             raise self._failure[0]
         _lib.check(status)
         self._h = h
-        self._keep = [inv, cb]           # the inverse diagonal and the callback live as long as the handle
+        self._keep = keep
         return self
 
-    @property
-    def handle(self):
-        if not self._h:
-            raise BP5Error(1, "PreconditionChebyshev.initialize has not been called")
-        return self._h
-
-    def _run(self, fn, dst, src):
-        mf = self.mf_data
-        _refuse_blocks("PreconditionChebyshev", dst, src)
-        status = fn(self.handle, _ptr(_vals(dst), mf.n_local), _ptr(_vals(src), mf.n_local))
-        if self._failure:
-            raise self._failure.pop(0)
-        _lib.check(status)
-
     def vmult(self, dst, src):
-        """dst = P src (dst's prior content ignored); enqueued on the handle's stream."""
+        """dst = P src (dst's prior content ignored; the elasticity class: on (3, ld) tensors); enqueued on the handle's stream."""
         self._run(_lib.lib().bp5_chebyshev_vmult, dst, src)
 
     def step(self, dst, src):
@@ -777,16 +799,37 @@ class PreconditionChebyshev:
         return dict(min_est=v[0].value, max_est=v[1].value, min_used=v[2].value, max_used=v[3].value, cg_its=k.value)
 
     def clear(self):
-        if self._h:
-            _lib.lib().bp5_chebyshev_destroy(self._h)
-            self._h = None
+        super().clear()
         self._keep = []
 
-    def __del__(self):
-        try:
-            self.clear()
-        except Exception:
-            pass
+
+class PreconditionChebyshev(_ChebyshevBase):
+    """== PreconditionChebyshev<Operator, Vector, DiagonalMatrix> (deal.II): a Chebyshev polynomial of degree `degree` in D^-1 A on the
+    eigenvalue bounds of D^-1 A, estimated at initialize() by a few CG-Lanczos steps (bp5_chebyshev_create, include/bp5.h).  vmult is
+    degree-1 operator applications and degree pointwise step launches, with no dot product: only the operator's halo exchanges.
+
+    A: a PoissonOperator / HelmholtzOperator (its coef, natively) or any object with `mf_data` and `vmult(dst, src)` (through a
+    callback).  AdditionalData.preconditioner: a DiagonalMatrix holding the INVERSE diagonal (compute_diagonal(invert=True)), None = identity."""
+
+    class AdditionalData:
+        def __init__(self, degree=1, smoothing_range=0.0, eig_cg_n_iterations=8, max_eigenvalue=0.0, min_eigenvalue=0.0, preconditioner=None):
+            self.degree, self.smoothing_range, self.eig_cg_n_iterations = int(degree), float(smoothing_range), int(eig_cg_n_iterations)
+            self.max_eigenvalue, self.min_eigenvalue = float(max_eigenvalue), float(min_eigenvalue)
+            self.preconditioner = preconditioner
+
+    def initialize(self, A, data=None):
+        self.clear()
+        _refuse_elasticity(type(self).__name__, A)
+        data = data if data is not None else PreconditionChebyshev.AdditionalData()
+        mf = A.mf_data
+        inv = _vals(data.preconditioner.get_vector()) if data.preconditioner is not None else None
+        self._failure = []
+        if isinstance(A, PoissonOperator):
+            coef, cb = _ptr(A.coef), None
+        else:
+            coef, cb = None, _callback(A, mf, self._failure)
+        return self._create(A, data, [inv, cb], lambda prm, h: _lib.lib().bp5_chebyshev_create(
+            mf.handle, coef, C.cast(cb, C.c_void_p) if cb is not None else None, None, _ptr(inv, mf.n_owned) if inv is not None else None, C.byref(prm), C.byref(h)))
 
 
 class MGTwoLevelTransfer:
@@ -859,36 +902,16 @@ def mg_coarse_degrees(degree):
     return degrees
 
 
-def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4, metric_precision=None):
-    """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same operator class, cells, block order
-    and numbering scheme, coefficient, quadrature, geometry mode, device, stream and communicator at degrees p // 2, ..., 1; then, at
-    degree 1, up to
-    h_levels geometric levels (an int, or "max": as many as the mesh allows), each on BrickMesh.coarsen(min_cells) of the one above
-    (half the cells per direction, twice h, the same domain), stopping where coarsen returns None.  h_levels = 0 (default): the p-levels
-    only.  Returns [fine_op, ...].
-    metric_precision = None (default): nothing changes -- the coarse levels are built with FP64 planes whatever fine_op's own planes are (a
-    fine_op that is itself float32 gets FP64 levels below it; pass "float32" for an all-float hierarchy).  "float32": EVERY level operator keeps its metric planes as floats (deal.II's
-    mixed-precision multigrid, step-37 / step-75, as far as the planes go: arithmetic and vectors stay double) -- level 0 included, which
-    is then NOT fine_op but a new float32 twin of it on the same mesh object, quadrature, coefficient, stream and communicator.  The caller
-    keeps fine_op as the outer CG's operator (the solution is then the FP64 solution) and passes the returned list to PreconditionMG."""
-    from .mesh import BrickMesh
+def _check_h_levels(who, h_levels):
     if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
-        raise BP5Error(1, f"make_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
-    mf, m = fine_op.mf_data, fine_op.mf_data.mesh
-    stream = mf.stream                # the levels share fine_op's stream (bp5_mg_create refuses anything else), whatever torch's current one is
+        raise BP5Error(1, f"{who}: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
 
-    geometry = dict(geometry=fine_op.geometry) if fine_op.geometry else {}     # (HelmholtzOperator: six-plane geometry only)
-    if metric_precision is not None:
-        if metric_precision not in MatrixFree.METRIC_PRECISION:
-            raise BP5Error(1, f"make_mg_hierarchy: metric_precision must be None, 'float64' or 'float32', not {metric_precision!r}")
-        if type(fine_op) is not PoissonOperator:
-            raise BP5Error(5, "make_mg_hierarchy: metric_precision needs a PoissonOperator")
-        geometry["metric_precision"] = metric_precision
 
-    def level(mesh):
-        return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream, **geometry)
-
-    ops = [fine_op if metric_precision in (None, getattr(fine_op, "metric_precision", "float64")) else level(m)]
+def _mg_levels(top, h_levels, min_cells, level):
+    """[top, ...]: below `top`, level(mesh) at the degrees p // 2, ..., 1 on top's cells, then up to h_levels times on the coarsened mesh of the one above"""
+    from .mesh import BrickMesh
+    m = top.mf_data.mesh
+    ops = [top]
     for p in mg_coarse_degrees(m.degree)[1:]:
         ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
                                    dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)))
@@ -902,44 +925,55 @@ def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4, metric_precision=None):
     return ops
 
 
-class PreconditionMG:
-    """== PreconditionMG<dim, Vector, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a
-    Chebyshev coarse solver (step-37), coarsening in the polynomial degree and then in the mesh (bp5_mg_*, include/bp5.h).  operators:
-    PoissonOperators from fine to coarse, degrees p, max(1, p // 2), ..., 1 on the same cells, then optionally degree-1 levels on
-    2:1 coarser BrickMeshes (make_mg_hierarchy builds them).  A pair of different degrees gets the p-transfer, a pair of equal degrees
-    the geometric one.  vmult is one symmetric V-cycle,
-    enqueued on the operators' stream without a host synchronisation; SolverCG.solve passes it natively (bp5_mg_vmult)."""
+def make_mg_hierarchy(fine_op, h_levels=0, min_cells=4, metric_precision=None):
+    """The operators of the multigrid levels below fine_op (a PoissonOperator on a BrickMesh): the same operator class, cells, block order
+    and numbering scheme, coefficient, quadrature, geometry mode, device, stream and communicator at degrees p // 2, ..., 1; then, at
+    degree 1, up to
+    h_levels geometric levels (an int, or "max": as many as the mesh allows), each on BrickMesh.coarsen(min_cells) of the one above
+    (half the cells per direction, twice h, the same domain), stopping where coarsen returns None.  h_levels = 0 (default): the p-levels
+    only.  Returns [fine_op, ...].
+    metric_precision = None (default): nothing changes -- the coarse levels are built with FP64 planes whatever fine_op's own planes are (a
+    fine_op that is itself float32 gets FP64 levels below it; pass "float32" for an all-float hierarchy).  "float32": EVERY level operator keeps its metric planes as floats (deal.II's
+    mixed-precision multigrid, step-37 / step-75, as far as the planes go: arithmetic and vectors stay double) -- level 0 included, which
+    is then NOT fine_op but a new float32 twin of it on the same mesh object, quadrature, coefficient, stream and communicator.  The caller
+    keeps fine_op as the outer CG's operator (the solution is then the FP64 solution) and passes the returned list to PreconditionMG."""
+    _check_h_levels("make_mg_hierarchy", h_levels)
+    mf = fine_op.mf_data
+    stream = mf.stream                # the levels share fine_op's stream (bp5_mg_create refuses anything else), whatever torch's current one is
 
-    class AdditionalData:
-        def __init__(self, smoother_degree=4, smoothing_range=20.0, eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0,
-                     coarse_eig_cg_n_iterations=30):
-            self.smoother_degree, self.smoothing_range, self.eig_cg_n_iterations = int(smoother_degree), float(smoothing_range), int(eig_cg_n_iterations)
-            self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
-            self.coarse_eig_cg_n_iterations = int(coarse_eig_cg_n_iterations)
+    geometry = dict(geometry=fine_op.geometry) if fine_op.geometry else {}     # (HelmholtzOperator: six-plane geometry only)
+    if metric_precision is not None:
+        if metric_precision not in MatrixFree.METRIC_PRECISION:
+            raise BP5Error(1, f"make_mg_hierarchy: metric_precision must be None, 'float64' or 'float32', not {metric_precision!r}")
+        if type(fine_op) is not PoissonOperator:
+            raise BP5Error(5, "make_mg_hierarchy: metric_precision needs a PoissonOperator")
+        geometry["metric_precision"] = metric_precision
 
-    def __init__(self, operators, data=None):
-        self._h = None
-        self.transfers = []
-        self.initialize(operators, data)
+    def level(mesh):
+        return type(fine_op)(mesh, mf.quadrature, mf.coefficient, device=mf.device, comm=mf.comm, stream=stream, **geometry)
 
-    def initialize(self, operators, data=None):
+    top = fine_op if metric_precision in (None, getattr(fine_op, "metric_precision", "float64")) else level(mf.mesh)
+    return _mg_levels(top, h_levels, min_cells, level)
+
+
+class _MGBase(_NativePreconditioner):
+    _VMULT, _DESTROY, _NO_HANDLE = "bp5_mg_vmult", "bp5_mg_destroy", "{} has been cleared"
+
+    def _initialize(self, operators, data, ld=None):
+        """initialize() of both classes: the checks, the transfers, the parameters; _level_arguments and _c_create are the subclass's"""
+        name = type(self).__name__
         self.clear()
         data = data if data is not None else PreconditionMG.AdditionalData()
         ops = list(operators)
-        for o in ops:
-            _refuse_elasticity("PreconditionMG", o)
-        if not ops or not all(isinstance(o, PoissonOperator) for o in ops):
-            raise BP5Error(1, "PreconditionMG needs a list of PoissonOperators, fine to coarse")
+        self._check_operators(ops)
         # bp5_mg_create checks the handles themselves, but the transfers it takes are built first, and bp5_mg_transfer_create refuses such a
         # pair with words of its own: the same refusal here, in bp5_mg_create's words (from MatrixFree.stream, which set_stream keeps current)
         if len({o.mf_data.stream for o in ops}) > 1:
-            raise BP5Error(1, "PreconditionMG: the levels must share one stream (MatrixFree.set_stream moves each of them)")
+            raise BP5Error(1, f"{name}: the levels must share one stream (MatrixFree.set_stream moves each of them)")
+        self._level_arguments(ops, ld)
         self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
         self.transfers = [MGTwoLevelTransfer(f, c, geometric=f.mf_data.mesh.degree == c.mf_data.mesh.degree) for f, c in zip(ops[:-1], ops[1:])]
-        ids = []
-        for o in ops:
-            g = getattr(o.mf_data.mesh, "global_ids", None)
-            ids.append(np.ascontiguousarray(g[:o.mf_data.n_owned], dtype=np.uint64) if g is not None else None)
+        ids = [_global_ids(o.mf_data) for o in ops]
         id_ptrs = (C.c_void_p * len(ops))(*[a.ctypes.data if a is not None else None for a in ids])
         prm = _lib.MGParams(data.smoother_degree, data.smoothing_range, data.eig_cg_n_iterations, data.coarse_degree, data.coarse_range,
                             data.coarse_eig_cg_n_iterations, C.cast(id_ptrs, C.c_void_p))
@@ -948,21 +982,20 @@ class PreconditionMG:
         coefs = (C.c_void_p * n)(*[o.coef.data_ptr() if o.coef is not None else None for o in ops])
         trs = (C.c_void_p * max(n - 1, 1))(*[t.handle.value for t in self.transfers])
         h = C.c_void_p()
-        _lib.check(_lib.lib().bp5_mg_create(n, mfs, coefs, trs, C.byref(prm), C.byref(h)))
+        _lib.check(self._c_create(n, mfs, coefs, trs, C.byref(prm), C.byref(h)))
         self._h = h
         return self
 
-    @property
-    def handle(self):
-        if not self._h:
-            raise BP5Error(1, "PreconditionMG has been cleared")
-        return self._h
+    def _check_operators(self, ops):
+        if not ops or not all(isinstance(o, self._OPERATOR) for o in ops):
+            raise BP5Error(1, f"{type(self).__name__} needs a list of {self._OPERATOR.__name__}s, fine to coarse")
+
+    def _level_arguments(self, ops, ld):
+        pass
 
     def vmult(self, dst, src):
-        """dst = V src: one V-cycle (dst's prior content ignored); enqueued on the operators' stream."""
-        n = self.mf_data.n_local
-        _refuse_blocks("PreconditionMG", dst, src)
-        _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(_vals(dst), n), _ptr(_vals(src), n)))
+        """dst = V src: one V-cycle (dst's prior content ignored; the elasticity class: on (3, ld) tensors); enqueued on the operators' stream."""
+        self._run(_lib.lib().bp5_mg_vmult, dst, src)
 
     def level_info(self):
         """Per level, fine to coarse: dict(degree, cells, n_owned, n_global_dofs, min_est, max_est, min_used, max_used, cg_its,
@@ -977,30 +1010,47 @@ class PreconditionMG:
         return out
 
     def clear(self):
-        if self._h:
-            _lib.lib().bp5_mg_destroy(self._h)
-            self._h = None
+        super().clear()
         for t in self.transfers:
             t.clear()
         self.transfers = []
 
-    def __del__(self):
-        try:
-            self.clear()
-        except Exception:
-            pass
+
+class PreconditionMG(_MGBase):
+    """== PreconditionMG<dim, Vector, MGTransferMatrixFree> around Multigrid (V-cycle) with PreconditionChebyshev smoothers and a
+    Chebyshev coarse solver (step-37), coarsening in the polynomial degree and then in the mesh (bp5_mg_*, include/bp5.h).  operators:
+    PoissonOperators from fine to coarse, degrees p, max(1, p // 2), ..., 1 on the same cells, then optionally degree-1 levels on
+    2:1 coarser BrickMeshes (make_mg_hierarchy builds them).  A pair of different degrees gets the p-transfer, a pair of equal degrees
+    the geometric one.  vmult is one symmetric V-cycle,
+    enqueued on the operators' stream without a host synchronisation; SolverCG.solve passes it natively (bp5_mg_vmult)."""
+
+    _OPERATOR = PoissonOperator
+
+    class AdditionalData:
+        def __init__(self, smoother_degree=4, smoothing_range=20.0, eig_cg_n_iterations=10, coarse_degree=60, coarse_range=1000.0,
+                     coarse_eig_cg_n_iterations=30):
+            self.smoother_degree, self.smoothing_range, self.eig_cg_n_iterations = int(smoother_degree), float(smoothing_range), int(eig_cg_n_iterations)
+            self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
+            self.coarse_eig_cg_n_iterations = int(coarse_eig_cg_n_iterations)
+
+    def __init__(self, operators, data=None):
+        self._h = None
+        self.transfers = []
+        self.initialize(operators, data)
+
+    def initialize(self, operators, data=None):
+        return self._initialize(operators, data)
+
+    def _check_operators(self, ops):
+        for o in ops:
+            _refuse_elasticity(type(self).__name__, o)
+        super()._check_operators(ops)
+
+    def _c_create(self, n, mfs, coefs, trs, prm, h):
+        return _lib.lib().bp5_mg_create(n, mfs, coefs, trs, prm, h)
 
 
-def _even_ld(mf):
-    return mf.n_local + (mf.n_local & 1)
-
-
-def _global_ids(mf):
-    ids = getattr(mf.mesh, "global_ids", None)
-    return np.ascontiguousarray(ids[:mf.n_owned], dtype=np.uint64) if ids is not None else None
-
-
-class ElasticityPreconditionChebyshev:
+class ElasticityPreconditionChebyshev(_ChebyshevBase):
     """== PreconditionChebyshev<ElasticityOperator, BlockVector, DiagonalMatrix>: the Chebyshev polynomial of PreconditionChebyshev for an
     ElasticityOperator on (3, ld) tensors (bp5_elasticity_chebyshev_create, include/bp5.h).  AdditionalData: PreconditionChebyshev's, its
     preconditioner a DiagonalMatrix holding the BLOCK inverse diagonal (ElasticityOperator.compute_diagonal(invert=True)) or None = identity.
@@ -1009,14 +1059,10 @@ class ElasticityPreconditionChebyshev:
 
     AdditionalData = PreconditionChebyshev.AdditionalData
 
-    def __init__(self):
-        self._h = None
-        self._keep = []
-
     def initialize(self, A, data=None, ld=None):
         self.clear()
         if not isinstance(A, ElasticityOperator):
-            raise BP5Error(1, "ElasticityPreconditionChebyshev needs an ElasticityOperator (PreconditionChebyshev takes the scalar operators)")
+            raise BP5Error(1, f"{type(self).__name__} needs an ElasticityOperator (PreconditionChebyshev takes the scalar operators)")
         data = data if data is not None else PreconditionChebyshev.AdditionalData()
         mf = A.mf_data
         inv = _vals(data.preconditioner.get_vector()) if data.preconditioner is not None else None
@@ -1025,86 +1071,36 @@ class ElasticityPreconditionChebyshev:
         self.ld = int(ld) if ld is not None else (int(inv.shape[1]) if inv is not None else _even_ld(mf))
         if inv is not None and int(inv.shape[1]) != self.ld:
             raise BP5Error(1, f"elasticity: the inverse diagonal has ld = {inv.shape[1]}, the preconditioner ld = {self.ld}")
-        self.A, self.mf_data, self.data = A, mf, data
-        ids = _global_ids(mf)
-        prm = _lib.ChebyshevParams(data.degree, data.smoothing_range, data.eig_cg_n_iterations, data.max_eigenvalue, data.min_eigenvalue,
-                                   ids.ctypes.data if ids is not None else None)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().bp5_elasticity_chebyshev_create(mf.handle, _ptr(A.coef), A.lam, A.mu, self.ld, _ptr(inv), C.byref(prm), C.byref(h)))
-        self._h = h
-        self._keep = [inv]               # the inverse diagonal lives as long as the handle
-        return self
+        return self._create(A, data, [inv], lambda prm, h: _lib.lib().bp5_elasticity_chebyshev_create(
+            mf.handle, _ptr(A.coef), A.lam, A.mu, self.ld, _ptr(inv), C.byref(prm), C.byref(h)))
 
-    @property
-    def handle(self):
-        if not self._h:
-            raise BP5Error(1, "ElasticityPreconditionChebyshev.initialize has not been called")
-        return self._h
-
-    def _run(self, fn, dst, src):
-        dst, src = _vals(dst), _vals(src)
-        if self.A._args(dst, src) != self.ld:
-            raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {self.ld}, the vectors have {dst.shape[1]}")
-        _lib.check(fn(self.handle, _ptr(dst), _ptr(src)))
-
-    def vmult(self, dst, src):
-        """dst = P src on (3, ld) tensors (dst's prior content ignored); enqueued on the handle's stream."""
-        self._run(_lib.lib().bp5_chebyshev_vmult, dst, src)
-
-    def step(self, dst, src):
-        """Smoother: dst improved from its current value by `degree` Chebyshev steps on A dst = src."""
-        self._run(_lib.lib().bp5_chebyshev_step, dst, src)
-
-    estimated_eigenvalues = PreconditionChebyshev.estimated_eigenvalues
-
-    def clear(self):
-        if self._h:
-            _lib.lib().bp5_chebyshev_destroy(self._h)
-            self._h = None
-        self._keep = []
-
-    def __del__(self):
-        try:
-            self.clear()
-        except Exception:
-            pass
+    def _vectors(self, dst, src):
+        return _elasticity_vectors(self, self.A, dst, src)
 
 
 def make_elasticity_mg_hierarchy(fine_op, h_levels=0, min_cells=4):
     """The ElasticityOperators of the multigrid levels below fine_op (on a BrickMesh): the same lam, mu, quadrature, coefficient, device and
     stream at degrees p // 2, ..., 1 on the same cells, then at the last degree up to h_levels geometric levels (an int, or "max") on
     BrickMesh.coarsen(min_cells) of the one above -- make_mg_hierarchy's rule.  Returns [fine_op, ...] for ElasticityPreconditionMG."""
-    from .mesh import BrickMesh
     if not isinstance(fine_op, ElasticityOperator):
         raise BP5Error(1, "make_elasticity_mg_hierarchy needs an ElasticityOperator")
-    if h_levels != "max" and (isinstance(h_levels, bool) or not isinstance(h_levels, int) or h_levels < 0):
-        raise BP5Error(1, f"make_elasticity_mg_hierarchy: h_levels must be an int >= 0 or 'max', not {h_levels!r}")
-    mf, m = fine_op.mf_data, fine_op.mf_data.mesh
+    _check_h_levels("make_elasticity_mg_hierarchy", h_levels)
+    mf = fine_op.mf_data
 
     def level(mesh):
         return ElasticityOperator(mesh, mf.quadrature, mf.coefficient, lam=fine_op.lam, mu=fine_op.mu, device=mf.device, stream=mf.stream)
 
-    ops = [fine_op]
-    for p in mg_coarse_degrees(m.degree)[1:]:
-        ops.append(level(BrickMesh(p, m.cells, h=m.h, deform_amp=m.deform_amp, rank=m.rank, n_ranks=m.n_ranks, cell_block=m.cell_block,
-                                   dof_numbering=m.dof_numbering, cell_block_order=m.cell_block_order)))
-    n_h = 0
-    while h_levels == "max" or n_h < h_levels:
-        coarse = ops[-1].mf_data.mesh.coarsen(min_cells)
-        if coarse is None:
-            break
-        ops.append(level(coarse))
-        n_h += 1
-    return ops
+    return _mg_levels(fine_op, h_levels, min_cells, level)
 
 
-class ElasticityPreconditionMG:
+class ElasticityPreconditionMG(_MGBase):
     """== PreconditionMG<dim, BlockVector, MGTransferMatrixFree> for ElasticityOperators, fine to coarse (make_elasticity_mg_hierarchy builds
     them): PreconditionMG's V-cycle -- Chebyshev smoothers on the block inverse diagonals, the fused residual restriction, the scalar transfer
     handles on all three blocks, the coarse polynomial -- on (3, ld) tensors (bp5_elasticity_mg_create, include/bp5.h).  ld: the row length of
     the vectors vmult will see (default: n_local of the fine level rounded up to even).  SolverCG.solve(op, x, b, this) runs
     bp5_cg_solve_elasticity_preconditioned with bp5_mg_vmult."""
 
+    _OPERATOR = ElasticityOperator
     AdditionalData = PreconditionMG.AdditionalData
 
     def __init__(self, operators, data=None, ld=None):
@@ -1113,59 +1109,18 @@ class ElasticityPreconditionMG:
         self.initialize(operators, data, ld)
 
     def initialize(self, operators, data=None, ld=None):
-        self.clear()
-        data = data if data is not None else PreconditionMG.AdditionalData()
-        ops = list(operators)
-        if not ops or not all(isinstance(o, ElasticityOperator) for o in ops):
-            raise BP5Error(1, "ElasticityPreconditionMG needs a list of ElasticityOperators, fine to coarse")
-        if len({o.mf_data.stream for o in ops}) > 1:
-            raise BP5Error(1, "ElasticityPreconditionMG: the levels must share one stream (MatrixFree.set_stream moves each of them)")
+        return self._initialize(operators, data, ld)
+
+    def _level_arguments(self, ops, ld):
         if len({(o.lam, o.mu) for o in ops}) > 1:
-            raise BP5Error(1, "ElasticityPreconditionMG: the levels must share lam and mu")
-        self.operators, self.data, self.mf_data = ops, data, ops[0].mf_data
-        self.ld = int(ld) if ld is not None else _even_ld(self.mf_data)
-        self.transfers = [MGTwoLevelTransfer(f, c, geometric=f.mf_data.mesh.degree == c.mf_data.mesh.degree) for f, c in zip(ops[:-1], ops[1:])]
-        ids = [_global_ids(o.mf_data) for o in ops]
-        id_ptrs = (C.c_void_p * len(ops))(*[a.ctypes.data if a is not None else None for a in ids])
-        prm = _lib.MGParams(data.smoother_degree, data.smoothing_range, data.eig_cg_n_iterations, data.coarse_degree, data.coarse_range,
-                            data.coarse_eig_cg_n_iterations, C.cast(id_ptrs, C.c_void_p))
-        n = len(ops)
-        mfs = (C.c_void_p * n)(*[o.mf_data.handle.value for o in ops])
-        coefs = (C.c_void_p * n)(*[o.coef.data_ptr() for o in ops])
-        trs = (C.c_void_p * max(n - 1, 1))(*[t.handle.value for t in self.transfers])
-        h = C.c_void_p()
-        _lib.check(_lib.lib().bp5_elasticity_mg_create(n, mfs, coefs, ops[0].lam, ops[0].mu, self.ld, trs, C.byref(prm), C.byref(h)))
-        self._h = h
-        return self
+            raise BP5Error(1, f"{type(self).__name__}: the levels must share lam and mu")
+        self.ld = int(ld) if ld is not None else _even_ld(ops[0].mf_data)
 
-    @property
-    def handle(self):
-        if not self._h:
-            raise BP5Error(1, "ElasticityPreconditionMG has been cleared")
-        return self._h
+    def _c_create(self, n, mfs, coefs, trs, prm, h):
+        return _lib.lib().bp5_elasticity_mg_create(n, mfs, coefs, self.operators[0].lam, self.operators[0].mu, self.ld, trs, prm, h)
 
-    def vmult(self, dst, src):
-        """dst = V src on (3, ld) tensors: one V-cycle (dst's prior content ignored); enqueued on the operators' stream."""
-        dst, src = _vals(dst), _vals(src)
-        if self.operators[0]._args(dst, src) != self.ld:
-            raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {self.ld}, the vectors have {dst.shape[1]}")
-        _lib.check(_lib.lib().bp5_mg_vmult(self.handle, _ptr(dst), _ptr(src)))
-
-    level_info = PreconditionMG.level_info
-
-    def clear(self):
-        if self._h:
-            _lib.lib().bp5_mg_destroy(self._h)
-            self._h = None
-        for t in self.transfers:
-            t.clear()
-        self.transfers = []
-
-    def __del__(self):
-        try:
-            self.clear()
-        except Exception:
-            pass
+    def _vectors(self, dst, src):
+        return _elasticity_vectors(self, self.operators[0], dst, src)
 
 
 class _SolverBase:
@@ -1205,9 +1160,8 @@ class _SolverBase:
             ld = A._args(x, b)
             if ld != preconditioner.ld:
                 raise BP5Error(1, f"elasticity: the preconditioner was initialised for ld = {preconditioner.ld}, the vectors have {ld}")
-            fn = _lib.lib().bp5_mg_vmult if isinstance(preconditioner, ElasticityPreconditionMG) else _lib.lib().bp5_chebyshev_vmult
-            status = _lib.lib().bp5_cg_solve_elasticity_preconditioned(mf.handle, _ptr(A.coef), A.lam, A.mu, ld, C.cast(fn, C.c_void_p), preconditioner.handle,
-                                                                       _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
+            status = _lib.lib().bp5_cg_solve_elasticity_preconditioned(mf.handle, _ptr(A.coef), A.lam, A.mu, ld, *preconditioner._native(), _ptr(b), _ptr(x),
+                                                                       C.byref(prm), C.byref(res))
         elif isinstance(A, ElasticityOperator):
             # the coupled three-component system: ONE Krylov space, a BLOCK inverse diagonal (bp5_cg_solve_elasticity)
             ld = A._args(x, b)
@@ -1225,10 +1179,8 @@ class _SolverBase:
             fn = _lib.lib().bp5_cg_solve_components_distributed if A.distributed else _lib.lib().bp5_cg_solve_components
             status = fn(mf.handle, _ptr(A.coef), nc, ld, _ptr(diag, mf.n_owned) if diag is not None else None, _ptr(b), _ptr(x), C.byref(prm), C.byref(res))
         elif general:
-            if isinstance(preconditioner, PreconditionChebyshev):
-                pfn, pctx = C.cast(_lib.lib().bp5_chebyshev_vmult, C.c_void_p), preconditioner.handle
-            elif isinstance(preconditioner, PreconditionMG):
-                pfn, pctx = C.cast(_lib.lib().bp5_mg_vmult, C.c_void_p), preconditioner.handle
+            if isinstance(preconditioner, (PreconditionChebyshev, PreconditionMG)):
+                pfn, pctx = preconditioner._native()
             else:
                 pcb = _callback(preconditioner, mf, failure)
                 pfn, pctx = C.cast(pcb, C.c_void_p), None
@@ -1283,8 +1235,7 @@ def _elasticity_precond(preconditioner, ld):
         raise BP5Error(5, "hyperelasticity: the preconditioner is None, an ElasticityPreconditionChebyshev or an ElasticityPreconditionMG (of op.linear)")
     if ld != preconditioner.ld:
         raise BP5Error(1, f"hyperelasticity: the preconditioner was initialised for ld = {preconditioner.ld}, the vectors have {ld}")
-    fn = _lib.lib().bp5_mg_vmult if isinstance(preconditioner, ElasticityPreconditionMG) else _lib.lib().bp5_chebyshev_vmult
-    return C.cast(fn, C.c_void_p), preconditioner.handle
+    return preconditioner._native()
 
 
 class NewtonSolver:
